@@ -11,16 +11,32 @@ the HIP kernels behind ``gh_ctx_decode`` (include/gaphuff.h).  Default ``cfg4`` 
 configs[3]: 10^9 bytes of generate.cpp-distributed data, redundancy 0.1, per GPU
 (compressed payload 1.01 GB: the north star's "1 GB compressed.huff"; it does not fit
 the 256 MiB Infinity Cache, so every decode streams from HBM).  ``--workload
-cfg2|cfg3|cfg5`` selects the others.  The same run then times a second workload (``--sub``,
-default ``cfg5``: redundancy 0.5, 1 GB per GPU, so 8 GB over 8 GPUs = configs[4] literally,
-with its own bit-exact check and RCCL gather) and reports it under ``sub``; ``--sub none``
-skips it.
+cfg2|cfg3|cfg5`` selects the others.
+
+A plain run does only what ``value`` needs: it builds the stream, loads it, runs the W
+untimed and K timed decodes, writes the outputs when ``--dump-outputs DIR`` is given and
+prints the line (``roofline`` comes from the timed decodes' own kernel times).  Everything
+else is behind ``--full``: the byte-for-byte check against the generator (``bitexact``), the
+RCCL gather, the ``sustained`` decodes, the streaming-copy yardstick, the end-to-end
+file-to-file timing, the CPU baselines and a second workload timed in the same run
+(``--sub``, default ``cfg5``: redundancy 0.5, 1 GB per GPU, so 8 GB over 8 GPUs =
+configs[4] literally, with its own bit-exact check and RCCL gather), reported under
+``sub``; ``--sub none`` skips it.  Without ``--full`` those keys are null and the options
+that shape them have no effect.
+
+``--dump-outputs DIR`` writes what the last timed decode left for a caller, copied out
+right after the timed steps: ``DIR/decoded.npy`` (float32; the whole decoded shard up to
+2^23 bytes, else the bytes at 2^23 sorted positions drawn by ``numpy.random.default_rng``
+seeded with ``--seed``) and ``DIR/histogram.npy`` (float64[256], byte counts of the whole
+shard).  At N>1 each rank writes its own shard as ``decoded_rank<k>.npy`` /
+``histogram_rank<k>.npy``.  The inputs depend only on the arguments, so two builds can be
+compared output for output.
 
 Weak scaling: at N GPUs the global input is N x 10^9 bytes.  Rank 0 generates and
 encodes the global stream ONCE (v2 header when N, W or G >= 2^31) into a file under
 /dev/shm; every rank streams only its own shard of gap segments (``gh_plan_shards``)
-from that file to its GPU (``gh_ctx_load_file``) — no data-path collective.  After
-the timed region each rank checks its decoded shard byte-for-byte against the
+from that file to its GPU (``gh_ctx_load_file``) — no data-path collective.  With
+``--full``, after the timed region each rank checks its decoded shard byte-for-byte against the
 generator's slice at the shard's output offset (exclusive scan of the shard sizes),
 and the shards are gathered to rank 0 over RCCL send/recv (timed separately,
 ``gather_ms``) and checked again there.
@@ -242,10 +258,36 @@ def end_to_end(img: np.ndarray, args, r: float, dev, threads: int) -> dict:
     return res
 
 
-def run_workload(args, name: str, per_gpu: int, r: float, ctx: dict, keep_image: bool) -> dict:
+DUMP_SAMPLE = 1 << 23  # decoded bytes kept by --dump-outputs (float32: 32 MiB per rank)
+
+
+def dump_outputs(dirname: str, out, nbytes: int, seed: int, rank: int, world: int) -> None:
+    """--dump-outputs: the decoded shard (`out`, a uint8 tensor on the GPU) as
+    decoded.npy (float32; whole, or a fixed seeded sample of DUMP_SAMPLE positions) and
+    histogram.npy (float64[256], counts over the whole shard)."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    out = out[:nbytes]
+    if nbytes > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(seed).integers(0, nbytes, size=DUMP_SAMPLE, dtype=np.int64))
+        sample = out[torch.from_numpy(idx).to(out.device)]
+    else:
+        sample = out
+    hist = torch.zeros(256, dtype=torch.int64, device=out.device)
+    step = 1 << 27
+    for off in range(0, nbytes, step):
+        hist += torch.bincount(out[off:off + step].to(torch.int64), minlength=256)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(dirname, f"decoded{sfx}.npy"), sample.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(dirname, f"histogram{sfx}.npy"), hist.cpu().numpy().astype(np.float64))
+
+
+def run_workload(args, name: str, per_gpu: int, r: float, ctx: dict, keep_image: bool,
+                 dump_dir: str = "") -> dict:
     """One timed workload: build (or share) the stream, load this rank's shard, W untimed
-    and K timed decodes between barriers, then the correctness checks and the RCCL
-    gather.  Returns the measurements (rank-local values plus max/sum over ranks)."""
+    and K timed decodes between barriers, then (--full) the sustained decodes, the
+    correctness checks and the RCCL gather.  Returns the measurements (rank-local values plus max/sum over ranks)."""
     import torch
 
     world, rank, dev, dist, use_dist, threads = (ctx[k] for k in ("world", "rank", "dev", "dist", "use_dist",
@@ -325,13 +367,20 @@ def run_workload(args, name: str, per_gpu: int, r: float, ctx: dict, keep_image:
         barrier()
         rep = dec.report(dstream)
         shard_bytes = int(rep.out_bytes)
+        if dump_dir:  # the last timed decode's output, before anything else decodes again
+            out = torch.empty(max(1, shard_bytes), dtype=torch.uint8, device=dev)
+            dec.copy_output(out.data_ptr(), shard_bytes, 0, stream)
+            torch.cuda.synchronize()
+            dump_outputs(dump_dir, out, shard_bytes, args.seed, rank, world)
+            del out
+            torch.cuda.empty_cache()
         # Sustained rate, untimed by the contract and reported beside it: the kernel time of
         # a GPU that has just come out of idle dips for ~40 launches (the clock settles under
         # the new load: per-dispatch 456 -> 615 -> 430 us on cfg4, profiles/r05_burst_series.txt),
         # and K = 20 after W = 5 sits in that dip.  S more back-to-back decodes, the mean of
         # all and of the second half.
         sustained = None
-        if args.sustain > 0:
+        if args.full and args.sustain > 0:
             halves = []
             for part in (args.sustain // 2, args.sustain - args.sustain // 2):
                 dec.reset_timing()
@@ -345,34 +394,38 @@ def run_workload(args, name: str, per_gpu: int, r: float, ctx: dict, keep_image:
         kern_ms = float(rep.kernel_ms)
         mx, sm = gh_dist.reduce_max_sum(dist, [elapsed, kern_ms, float(shard_bytes)], dev)
 
-        # ---- correctness: each shard vs the generator's slice at its output offset
-        off, sizes = gh_dist.exclusive_offsets(dist, shard_bytes, dev)
-        out = torch.empty(max(1, shard_bytes), dtype=torch.uint8, device=dev)
-        dec.copy_output(out.data_ptr(), shard_bytes, 0, stream)
-        torch.cuda.synchronize()
-        ok = (sum(sizes) == hdr["n"]) and gh_dist.verify_slice(out[:shard_bytes].cpu().numpy(), args.seed, r, off,
-                                                               threads=threads)
         status_ok = rep.status == 0 and rep0.status == 0
+        ok, checked = True, False
         gather_ms = None
         gather_ok = None
-        if dist is not None and not args.no_gather:
-            full, gather_ms = gh_dist.gather_to_root(dist, out, shard_bytes, dev)
-            if rank == 0:
-                gather_ok = full is not None and full.numel() == hdr["n"]
-                for k in range(world):  # gathered shard k == generator slice, compared on the GPU
-                    if not gather_ok:
-                        break
-                    lo = sum(sizes[:k])
-                    want = torch.from_numpy(gh.generate(args.seed, r, sizes[k], offset=lo, threads=threads)).to(dev)
-                    gather_ok = bool(torch.equal(full[lo:lo + sizes[k]], want))
-                    del want
-                del full
-            ok = ok and (gather_ok is not False)
+        if args.full:
+            # ---- correctness: each shard vs the generator's slice at its output offset
+            off, sizes = gh_dist.exclusive_offsets(dist, shard_bytes, dev)
+            out = torch.empty(max(1, shard_bytes), dtype=torch.uint8, device=dev)
+            dec.copy_output(out.data_ptr(), shard_bytes, 0, stream)
+            torch.cuda.synchronize()
+            ok = (sum(sizes) == hdr["n"]) and gh_dist.verify_slice(out[:shard_bytes].cpu().numpy(), args.seed, r, off,
+                                                                   threads=threads)
+            if dist is not None and not args.no_gather:
+                full, gather_ms = gh_dist.gather_to_root(dist, out, shard_bytes, dev)
+                if rank == 0:
+                    gather_ok = full is not None and full.numel() == hdr["n"]
+                    for k in range(world):  # gathered shard k == generator slice, compared on the GPU
+                        if not gather_ok:
+                            break
+                        lo = sum(sizes[:k])
+                        want = torch.from_numpy(gh.generate(args.seed, r, sizes[k], offset=lo, threads=threads)).to(dev)
+                        gather_ok = bool(torch.equal(full[lo:lo + sizes[k]], want))
+                        del want
+                    del full
+                ok = ok and (gather_ok is not False)
+            checked = True
+            del out
+            torch.cuda.empty_cache()
         ok = gh_dist.all_true(dist, bool(ok and status_ok), dev)
-        del out
-        torch.cuda.empty_cache()
         res.update({"hdr": hdr, "b": b, "e": e, "rep": rep, "alg": alg, "kern_ms": kern_ms,
                     "max_elapsed": mx[0], "max_kern": mx[1], "sum_bytes": sm[2], "ok": ok,
+                    "bitexact": bool(ok) if checked else None,
                     "gather_ms": gather_ms, "gather_ok": gather_ok, "load_ms": load_ms, "total": total,
                     "sustained": sustained})
         return res
@@ -419,8 +472,14 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: bit-exact check, RCCL gather, "
+                         "sustained decodes, copy yardstick, end-to-end timing, CPU baselines, --sub workload")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed decode's output to DIR/decoded.npy (float32, whole or a "
+                         "fixed seeded sample) and DIR/histogram.npy (float64 byte counts)")
     ap.add_argument("--sustain", type=int, default=200,
-                    help="after the timed steps: this many more decodes, reported as 'sustained' (0: skip)")
+                    help="--full: after the timed steps, this many more decodes, reported as 'sustained' (0: skip)")
     ap.add_argument("--workload", default="cfg4", choices=sorted(WORKLOADS))
     ap.add_argument("--sub", default="cfg5", choices=sorted(WORKLOADS) + ["none"],
                     help="second workload timed in the same run, reported under 'sub' (default cfg5: "
@@ -440,6 +499,8 @@ def main() -> int:
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end file-to-file timing")
     ap.add_argument("--out-json", default="", help="also write the JSON line to this file (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 
@@ -466,7 +527,8 @@ def main() -> int:
     per_gpu, r, desc = WORKLOADS[args.workload]
     if args.size:
         per_gpu = args.size
-    res = run_workload(args, args.workload, per_gpu, r, ctx, keep_image=not use_dist and not args.no_e2e)
+    res = run_workload(args, args.workload, per_gpu, r, ctx,
+                       keep_image=args.full and not use_dist and not args.no_e2e, dump_dir=args.dump_outputs)
     e2e_img = res.pop("image")
     rep, alg, kern_ms = res["rep"], res["alg"], res["kern_ms"]
     hdr, shard_bytes = res["hdr"], int(res["rep"].out_bytes)
@@ -474,7 +536,7 @@ def main() -> int:
 
     stream = torch.cuda.current_stream().cuda_stream
     copy_gbps = None
-    if rank == 0 and not args.no_copy:
+    if args.full and rank == 0 and not args.no_copy:
         try:
             copy_gbps = copy_yardstick(alg, stream, dev)
         except Exception as ex:  # the yardstick must not hide the decode number
@@ -490,7 +552,7 @@ def main() -> int:
 
     # the second workload (default configs[4]'s r=0.5 stream: 1 GB per GPU, RCCL gather)
     sub = None
-    if args.sub != "none" and args.sub != args.workload:
+    if args.full and args.sub != "none" and args.sub != args.workload:
         s_per_gpu, s_r, s_desc = WORKLOADS[args.sub]
         if args.size:
             s_per_gpu = args.size
@@ -543,7 +605,8 @@ def main() -> int:
                          "alg_bytes_per_launch": alg,
                          "traffic_source": tsrc,
                          "kernel_timing": KERNEL_TIMING.get(int(rep.mode))},
-            "bitexact": bool(res["ok"]),
+            "full": bool(args.full),
+            "bitexact": res["bitexact"],
             "gather_ms": None if res["gather_ms"] is None else round(res["gather_ms"], 3),
             "gather_bitexact": res["gather_ok"],
             "load_ms": round(res["load_ms"], 2),
@@ -558,7 +621,7 @@ def main() -> int:
             "sustained": sustained_record(res),
             "sub": sub,
         }
-        if world == 1 and not use_dist and args.cpu_sample > 0:
+        if args.full and world == 1 and not use_dist and args.cpu_sample > 0:
             try:
                 line["cpu_baseline"] = cpu_baseline(r, args.seed, args.cpu_sample)
             except Exception as ex:  # a missing baseline must not hide the GPU number

@@ -10,7 +10,7 @@
 #   perf WL...                quick_one.py per workload (kernel ms, frac, bit-exact)
 #   cmp WL[,WL] LIB...        cmp_libs.py: build variants side by side (LIB = base | name[@VAR=v...])
 #   cmpss WL[,WL] LIB...      the same in the steady state (60 untimed + 100 timed decodes each)
-#   bench NAME [ARGS...]      bench.py ARGS --out-json OUT/NAME.json
+#   bench NAME [ARGS...]      bench.py --full ARGS --out-json OUT/NAME.json
 #   stats NAME WL             rocprofv3 --kernel-trace --stats of quick_one.py WL
 #   sq NAME WL [LIB]          two SQ counter passes (issue / wait / LDS) of quick_one.py WL
 #                             (LIB: a build variant's name, lib/libgaphuff_LIB.so)
@@ -69,7 +69,7 @@ for spec in "$@"; do
       unset QO_WARM CMP_REPS
       cat "$O/${kind}_${a[1]//,/_}.log" ;;
     bench)
-      step "bench-${a[1]}" 600 "$O/bench_${a[1]}.err" python bench.py "${a[@]:2}" --out-json "$O/${a[1]}.json" || true
+      step "bench-${a[1]}" 600 "$O/bench_${a[1]}.err" python bench.py --full "${a[@]:2}" --out-json "$O/${a[1]}.json" || true
       cat "$O/${a[1]}.json" 2> /dev/null || tail -20 "$O/bench_${a[1]}.err" ;;
     stats)
       step "stats-${a[1]}" 400 "$O/stats_${a[1]}.log" rocprofv3 --kernel-trace --stats --output-format csv \

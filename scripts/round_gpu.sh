@@ -14,7 +14,7 @@ O=gpurun_out/$R
 case ${1:-a} in
   a)
     bash scripts/lease.sh "$O" tests slow smoke "bench cfg4" \
-      "cmd dist1 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --force-dist --out-json $O/dist1.json" \
+      "cmd dist1 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --full --force-dist --out-json $O/dist1.json" \
       "bench cfg3 --workload cfg3 --sub none --cpu-sample 0" "bench cfg2 --workload cfg2 --sub none --cpu-sample 0" ;;
   b)
     bash scripts/lease.sh "$O" "stats cfg4 cfg4" "stats cfg3 cfg3" "stats cfg5 cfg5" "stats cfg2 cfg2" \

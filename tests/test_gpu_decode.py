@@ -194,13 +194,14 @@ def test_tile_mode_refuses_other_codes(gpu, monkeypatch):
 
 @pytest.mark.gpu
 def test_bench_contract_small(gpu):
-    """bench.py prints one JSON line with the contract keys (small size, no CPU leg)."""
+    """bench.py --full prints one JSON line with the contract keys, the bit-exact verdict and
+    the second workload's record (small size, no CPU leg)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
-                        "--size", "3000000", "--cpu-sample", "0"], capture_output=True, text=True,
+                        "--size", "3000000", "--cpu-sample", "0", "--full"], capture_output=True, text=True,
                        timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
