@@ -61,58 +61,123 @@ static uint32_t tile_u_for(uint32_t minlen) { return minlen >= 4 ? (uint32_t)TIL
 #ifndef GH_TILE_OW7
 #define GH_TILE_OW7 1  // codes of >= 5-bit codewords: 7 output words per segment (<= 26 codewords)
 #endif
-static const void* tile_kernel_for(uint32_t minlen, uint32_t g) {
+// A picked kernel: its launch pointer and the name of its template instantiation
+// (gh_ctx_kernel_shape, gh_kernel_shapes).  Both come from the one template argument list
+// of the *_kern functions below, so the name cannot drift from the pointer.
+struct Kern {
+  const void* fn;
+  const char* name;
+};
+template <class... A>
+static std::string kern_name(const char* fmt, A... a) {
+  char b[96];
+  snprintf(b, sizeof(b), fmt, a...);
+  return b;
+}
+template <int TB, int U, int G, int OW, int MINL>
+static Kern tile_kern() {
+  static const std::string n = kern_name("tile<%d,%d,%d,%d,%d>", TB, U, G, OW, MINL);
+  return {(const void*)gh_tile_kernel<TB, U, G, OW, MINL>, n.c_str()};
+}
+template <int TB, int GL, int NS, bool FB, int NP = 1>
+static Kern mtile_kern() {
+  static const std::string n = kern_name("mtile<%d,%d,%d,fb=%d,np=%d>", TB, GL, NS, (int)FB, NP);
+  return {(const void*)gh_mtile_kernel<TB, GL, NS, FB, NP>, n.c_str()};
+}
+template <int U, int TB, int GL, bool FB>
+static Kern ws_count_kern() {
+  static const std::string n = kern_name("ws_count<%d,%d,%d,fb=%d>", U, TB, GL, (int)FB);
+  return {(const void*)gh_ws_count_kernel<U, TB, GL, FB>, n.c_str()};
+}
+template <int U, int TB, int GL, int NS, bool FB>
+static Kern ws_write_kern() {
+  static const std::string n = kern_name("ws_write<%d,%d,%d,%d,fb=%d>", U, TB, GL, NS, (int)FB);
+  return {(const void*)gh_ws_write_kernel<U, TB, GL, NS, FB>, n.c_str()};
+}
+
+static Kern tile_kernel_for(uint32_t minlen, uint32_t g) {
   if (minlen >= 5 && GH_TILE_OW7)
-    return g >= 4 ? (const void*)gh_tile_kernel<TILE_TB, TILE_U, 4, 7, 5>
-         : g == 3 ? (const void*)gh_tile_kernel<TILE_TB, TILE_U, 3, 7, 5>
-                  : (const void*)gh_tile_kernel<TILE_TB, TILE_U, 2, 7, 5>;
+    return g >= 4 ? tile_kern<TILE_TB, TILE_U, 4, 7, 5>()
+         : g == 3 ? tile_kern<TILE_TB, TILE_U, 3, 7, 5>()
+                  : tile_kern<TILE_TB, TILE_U, 2, 7, 5>();
   if (minlen >= 4)
-    return g >= 4 ? (const void*)gh_tile_kernel<TILE_TB, TILE_U, 4, 8, 4>
-         : g == 3 ? (const void*)gh_tile_kernel<TILE_TB, TILE_U, 3, 8, 4>
-                  : (const void*)gh_tile_kernel<TILE_TB, TILE_U, 2, 8, 4>;
-  return g >= 4 ? (const void*)gh_tile_kernel<TILE_TB, TILE_U3, 4, 11, 3>
-       : g == 3 ? (const void*)gh_tile_kernel<TILE_TB, TILE_U3, 3, 11, 3>
-                : (const void*)gh_tile_kernel<TILE_TB, TILE_U3, 2, 11, 3>;
+    return g >= 4 ? tile_kern<TILE_TB, TILE_U, 4, 8, 4>()
+         : g == 3 ? tile_kern<TILE_TB, TILE_U, 3, 8, 4>()
+                  : tile_kern<TILE_TB, TILE_U, 2, 8, 4>();
+  return g >= 4 ? tile_kern<TILE_TB, TILE_U3, 4, 11, 3>()
+       : g == 3 ? tile_kern<TILE_TB, TILE_U3, 3, 11, 3>()
+                : tile_kern<TILE_TB, TILE_U3, 2, 11, 3>();
 }
 
 // Two-pass tile kernel by lookups per window shift and 16-byte stores per copy-out.
 template <int GL, bool FB>
-static const void* mtile_ns(int ns) {
-  return ns <= 4 ? (const void*)gh_mtile_kernel<MT_TB, GL, 4, FB>
-       : ns <= 6 ? (const void*)gh_mtile_kernel<MT_TB, GL, 6, FB>
-       : ns <= 8 ? (const void*)gh_mtile_kernel<MT_TB, GL, 8, FB>
-                 : (const void*)gh_mtile_kernel<MT_TB, GL, 5, FB, 2>;  // (10: two copy-out parts of 5 x 64 chunks)
+static Kern mtile_ns(int ns) {
+  return ns <= 4 ? mtile_kern<MT_TB, GL, 4, FB>()
+       : ns <= 6 ? mtile_kern<MT_TB, GL, 6, FB>()
+       : ns <= 8 ? mtile_kern<MT_TB, GL, 8, FB>()
+                 : mtile_kern<MT_TB, GL, 5, FB, 2>();  // (10: two copy-out parts of 5 x 64 chunks)
 }
 // fb: codewords longer than the tables (K = 11..12, GL = 2) through the canonical fallback
-static const void* mtile_kernel_for(int gl, int ns, bool fb = false) {
+static Kern mtile_kernel_for(int gl, int ns, bool fb = false) {
   if (fb) return mtile_ns<2, true>(ns);
   return gl >= 4 ? mtile_ns<4, false>(ns) : gl == 3 ? mtile_ns<3, false>(ns) : mtile_ns<2, false>(ns);
 }
 
 struct WsKernels {
-  const void* count;
-  const void* write;
+  Kern count;
+  Kern write;
 };
 template <int GL, bool FB = false>
-static const void* ws_write_ns(int ns) {
-  return ns <= 2 ? (const void*)gh_ws_write_kernel<WS_U, WS_TB, GL, 2, FB>
-         : ns <= 3 ? (const void*)gh_ws_write_kernel<WS_U, WS_TB, GL, 3, FB>
-         : ns <= 4 ? (const void*)gh_ws_write_kernel<WS_U, WS_TB, GL, 4, FB>
-         : ns <= 6 ? (const void*)gh_ws_write_kernel<WS_U, WS_TB, GL, 6, FB>
-                   : (const void*)gh_ws_write_kernel<WS_U, WS_TB, GL, 8, FB>;
+static Kern ws_write_ns(int ns) {
+  return ns <= 2 ? ws_write_kern<WS_U, WS_TB, GL, 2, FB>()
+         : ns <= 3 ? ws_write_kern<WS_U, WS_TB, GL, 3, FB>()
+         : ns <= 4 ? ws_write_kern<WS_U, WS_TB, GL, 4, FB>()
+         : ns <= 6 ? ws_write_kern<WS_U, WS_TB, GL, 6, FB>()
+                   : ws_write_kern<WS_U, WS_TB, GL, 8, FB>();
 }
 // Count kernel by its LUT width Kc, write kernel by K and NS (store instructions per
 // lane per piece: the typical piece's 16-byte chunks / 64).  fb: codes longer than the
 // tables or incomplete codes (canonical fallback, two lookups per window shift).
 static WsKernels ws_kernels(uint32_t Kc, uint32_t K, int ns, bool fb) {
-  if (fb) return {(const void*)gh_ws_count_kernel<WS_UC, WS_TBC, 2, true>, ws_write_ns<2, true>(ns)};
+  if (fb) return {ws_count_kern<WS_UC, WS_TBC, 2, true>(), ws_write_ns<2, true>(ns)};
   const int gc = lookups_per_shift(Kc), g = lookups_per_shift(K);
-  const void* cnt = gc >= 4 ? (const void*)gh_ws_count_kernel<WS_UC, WS_TBC, 4>
-                    : gc == 3 ? (const void*)gh_ws_count_kernel<WS_UC, WS_TBC, 3>
-                              : (const void*)gh_ws_count_kernel<WS_UC, WS_TBC, 2>;
-  const void* wr = g >= 4 ? ws_write_ns<4>(ns) : g == 3 ? ws_write_ns<3>(ns) : ws_write_ns<2>(ns);
+  const Kern cnt = gc >= 4 ? ws_count_kern<WS_UC, WS_TBC, 4, false>()
+                   : gc == 3 ? ws_count_kern<WS_UC, WS_TBC, 3, false>()
+                             : ws_count_kern<WS_UC, WS_TBC, 2, false>();
+  const Kern wr = g >= 4 ? ws_write_ns<4>(ns) : g == 3 ? ws_write_ns<3>(ns) : ws_write_ns<2>(ns);
   return {cnt, wr};
 }
+
+// Every name the pickers can return, one per line: the pickers enumerated over their
+// argument domains (shortest codeword and codewords per shift; lookups per shift, stores
+// per copy-out and fallback; table widths, stores per piece and fallback).  No device.
+static std::string all_kernel_shapes() {
+  std::vector<std::string> v;
+  auto add = [&](const char* n) {
+    if (std::find(v.begin(), v.end(), n) == v.end()) v.push_back(n);
+  };
+  for (uint32_t ml = 3; ml <= 12; ++ml)
+    for (uint32_t g = 2; g <= 4; ++g) add(tile_kernel_for(ml, g).name);
+  for (int fb = 0; fb <= 1; ++fb)
+    for (int gl = 2; gl <= 4; ++gl)
+      for (int ns = 4; ns <= 10; ++ns) add(mtile_kernel_for(gl, ns, fb != 0).name);
+  for (int pass = 0; pass < 2; ++pass)  // the count names, then the write names
+    for (int fb = 0; fb <= 1; ++fb)
+      for (uint32_t kc = 2; kc <= 14; ++kc)
+        for (uint32_t k = 2; k <= 12; ++k)
+          for (int ns = 2; ns <= 8; ++ns) {
+            const WsKernels w = ws_kernels(kc, k, ns, fb != 0);
+            add(pass ? w.write.name : w.count.name);
+          }
+  std::string s;
+  for (const std::string& n : v) s += n + "\n";
+  return s;
+}
+
+// The lane-major load of the tile kernel reads U segments past the shard end (word
+// 4 * (nseg - 1 + U), gh_tile.hip); gh_ctx_load / gh_ctx_load_device pad the payload with
+// 16 zero words, which covers U <= 4.
+static_assert(TILE_U <= 4 && TILE_U3 <= 4, "payload padding (16 words) covers at most 4 segments per lane");
 
 struct gh_ctx {
   int device = 0;
@@ -135,6 +200,7 @@ struct gh_ctx {
   uint32_t ntiles = 0;             // tiles (tile kernel) / wave blocks (wave split)
   size_t lds = 0;                  // dynamic LDS of the tile / write kernel
   size_t lut_bytes = 0;            // LDS bytes of its LUT
+  std::string shape;               // the picked kernel name(s) (gh_ctx_kernel_shape)
   uint32_t stage_bytes = 0;        // one staging buffer (tile) / one wave's (write kernel)
   // tile kernel (grouped codes)
   bool tile = false;
@@ -195,7 +261,17 @@ static void free_shard(gh_ctx* c) {
   c->mtile = false;
   c->mt_fb = false;
   c->ws = false;
+  c->shape.clear();
   c->loaded = false;
+}
+
+// GH_TILE_GRID=n (n >= 2; tests): fewer workgroups of a persistent kernel than fit the
+// device, so a small stream gives each decoding workgroup many tiles and rounds.  It only
+// lowers the grid.
+static uint32_t tile_grid_cap(uint32_t grid) {
+  if (const char* e = getenv("GH_TILE_GRID"))
+    if (grid > 2) return (uint32_t)std::clamp<long>(atol(e), 2, (long)grid);
+  return grid;
 }
 
 // ---- tile kernel setup -----------------------------------------------------------
@@ -226,13 +302,13 @@ static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
   per_seg = std::min<uint64_t>(per_seg, ((uint64_t)TILE_NS * 64 * 16 - 2 * STAGE_PAD - margin) / seg_wave);
   c->stage_bytes = (uint32_t)((STAGE_PAD + seg_wave * per_seg + margin + 15) & ~15ull);
   const std::vector<uint32_t> lt = grouped_lut(cn, K);
-  const void* kern = tile_kernel_for(c->tile_minl, c->tile_g);
+  const Kern kern = tile_kernel_for(c->tile_minl, c->tile_g);
   const char* envr = getenv("GH_LGR");
   const int lg = envr ? std::clamp(atoi(envr), 0, 14 - (int)K) : std::min(5, 14 - (int)K);
   int best = 0, best_lg = 0;
   for (int l2 = lg; l2 >= 0; --l2) {
     int pc = 0;
-    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern, TILE_TB, tile_lds_bytes(4ull << (K + l2), c->stage_bytes)));
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern.fn, TILE_TB, tile_lds_bytes(4ull << (K + l2), c->stage_bytes)));
     if (pc > best) {
       best = pc;
       best_lg = l2;
@@ -254,6 +330,7 @@ static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
   // LEAD_A * TILE_TB), the others decode; every workgroup must be resident at once
   // (the grid is sized from the occupancy; decodes on one device are chained, see DevChain)
   c->grid = (uint32_t)std::min<uint64_t>({(uint64_t)c->ntiles + 1, (uint64_t)best * c->num_cu, (uint64_t)LEAD_A * TILE_TB});
+  c->grid = tile_grid_cap(c->grid);
   c->idle_block = 0xFFFFFFFFu;
   if (const char* e = getenv("GH_TILE_IDLE"))  // experiment: block grid / 2 (the leader's CU partner) idles
     if (atoi(e) && c->grid == (uint32_t)best * c->num_cu && best == 2) {
@@ -265,6 +342,7 @@ static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
     GH_HIP(hipMalloc(&c->d_stamps, nb));
     GH_HIP(hipMemset(c->d_stamps, 0, nb));
   }
+  c->shape = kern.name;
   c->tile = true;
   return GH_OK;
 }
@@ -327,11 +405,11 @@ static int mtile_setup(gh_ctx* c, double avg_seg_bytes) {
   c->stage_bytes = (uint32_t)((STAGE_PAD + cap + 16 + 15) & ~15ull);  // + the write overrun
   c->mt_gl = lookups_per_shift(K);
   c->mt_fb = fb;
-  const void* kern = mtile_kernel_for(c->mt_gl, c->mt_ns, fb);
+  const Kern kern = mtile_kernel_for(c->mt_gl, c->mt_ns, fb);
   c->lut_bytes = lut_b;
   c->lds = mtile_lds_bytes(c->lut_bytes, c->stage_bytes);
   int pc = 0;
-  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern, MT_TB, c->lds));
+  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern.fn, MT_TB, c->lds));
   pc = std::min(pc, 2);  // (as tile_setup: the occupancy query can answer one too many)
   if (pc < 1) return GH_OK;
   std::vector<uint64_t> lt = multi_lut(cn, K);
@@ -368,8 +446,10 @@ static int mtile_setup(gh_ctx* c, double avg_seg_bytes) {
   c->tile_u = MT_U;
   c->ntiles = (uint32_t)ceil_div(c->nseg, (uint64_t)MT_U * MT_TB);
   c->grid = (uint32_t)std::min<uint64_t>({(uint64_t)c->ntiles + 1, (uint64_t)pc * c->num_cu, (uint64_t)LEAD_A * MT_TB});
+  c->grid = tile_grid_cap(c->grid);
   if (c->grid < 2) return GH_OK;
   c->idle_block = 0xFFFFFFFFu;
+  c->shape = kern.name;
   c->mtile = true;
   c->tile = true;
   return GH_OK;
@@ -490,8 +570,8 @@ static int ws_setup(gh_ctx* c, double avg_seg_bytes) {
   if (const char* en = getenv("GH_WS_NS")) c->ws_ns = std::clamp(atoi(en), 2, 8);
   const WsKernels k = ws_kernels(kc, K, c->ws_ns, fb);
   int pc_c = 0, pc_w = 0;
-  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_c, k.count, WS_TBC, c->lds_count));
-  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_w, k.write, WS_TB, c->lds));
+  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_c, k.count.fn, WS_TBC, c->lds_count));
+  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_w, k.write.fn, WS_TB, c->lds));
   if (pc_c < 1 || pc_w < 1) return fail(GH_E_HIP, "wave-split kernels do not fit on a CU");
   c->ws_nblocks = (uint32_t)ceil_div(c->nseg, (uint64_t)WS_SB);  // superblocks
   const uint64_t wg_blocks = ceil_div(c->ws_nblocks, (uint64_t)NW);  // workgroups that have a superblock
@@ -507,6 +587,7 @@ static int ws_setup(gh_ctx* c, double avg_seg_bytes) {
   GH_HIP(hipMalloc(&c->d_ws_junk, 16ull * 64 * c->ws_nranges));
   GH_HIP(hipMalloc(&c->d_rng_tot, 8ull * c->ws_nranges + 16));
   GH_HIP(hipMalloc(&c->d_rng_off, 8ull * c->ws_nranges + 16));
+  c->shape = std::string(k.count.name) + "+" + k.write.name;
   c->ws = true;
   return GH_OK;
 }
@@ -563,15 +644,31 @@ extern "C" int gh_ctx_create(int device, gh_ctx** out) {
   GH_HIP(hipMemset(c->d_misc, 0, 128));
   for (uint32_t ml : {3u, 4u, 5u})
     for (uint32_t gv : {2u, 3u, 4u})
-      (void)hipFuncSetAttribute(tile_kernel_for(ml, gv), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute(tile_kernel_for(ml, gv).fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   for (int gl : {2, 3, 4})
     for (int ns : {4, 6, 8, 10})
       for (bool fb : {false, true})
-        (void)hipFuncSetAttribute(mtile_kernel_for(gl, ns, fb), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(mtile_kernel_for(gl, ns, fb).fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipGetLastError();
   *out = c;
   return GH_OK;
 }
+
+// Copies s and its terminating NUL into buf[0..cap).
+static int copy_name(const std::string& s, char* buf, size_t cap) {
+  if (!buf) return fail(GH_E_ARG, "null argument");
+  if (s.size() + 1 > cap) return fail(GH_E_SMALL, "name buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return GH_OK;
+}
+
+extern "C" int gh_ctx_kernel_shape(gh_ctx* c, char* buf, size_t cap) {
+  if (!c) return fail(GH_E_ARG, "null ctx");
+  if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_kernel_shape before gh_ctx_load");
+  return copy_name(c->shape, buf, cap);
+}
+
+extern "C" int gh_kernel_shapes(char* buf, size_t cap) { return copy_name(all_kernel_shapes(), buf, cap); }
 
 extern "C" int gh_ctx_device(gh_ctx* c, int* device) {
   if (!c || !device) return fail(GH_E_ARG, "null argument");
@@ -883,9 +980,9 @@ extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
     ac[0] = &wc;
     aw[0] = &ww;
     const WsKernels wk = ws_kernels(c->ws_kc, c->ws_k, c->ws_ns, c->ws_fb);
-    GH_HIP(hipLaunchKernel(wk.count, dim3(c->ws_grid_c), dim3(WS_TBC), ac, c->lds_count, st));
+    GH_HIP(hipLaunchKernel(wk.count.fn, dim3(c->ws_grid_c), dim3(WS_TBC), ac, c->lds_count, st));
     GH_HIP(hipLaunchKernel((const void*)gh_ws_scan_kernel, dim3(1), dim3(WS_SCAN_TB), ac, 0, st));
-    GH_HIP(hipLaunchKernel(wk.write, dim3(c->grid), dim3(WS_TB), aw, c->lds, st));
+    GH_HIP(hipLaunchKernel(wk.write.fn, dim3(c->grid), dim3(WS_TB), aw, c->lds, st));
   } else {
     TileParams t{};
     t.payload = c->d_payload;
@@ -913,7 +1010,7 @@ extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
     t.stamps = c->d_stamps;
     t.tstamps = c->d_stamps ? (unsigned long long*)((uint8_t*)c->d_stamps + 32ull * c->grid * 2 * 128) : nullptr;
     t.idle_block = c->idle_block;
-    const void* kern = c->mtile ? mtile_kernel_for(c->mt_gl, c->mt_ns, c->mt_fb) : tile_kernel_for(c->tile_minl, c->tile_g);
+    const void* kern = (c->mtile ? mtile_kernel_for(c->mt_gl, c->mt_ns, c->mt_fb) : tile_kernel_for(c->tile_minl, c->tile_g)).fn;
     static thread_local void* ta[1];
     static thread_local TileParams tp;
     tp = t;

@@ -48,7 +48,7 @@ EXPORTED = (
     "gh_ectx_create", "gh_ectx_destroy", "gh_ectx_load", "gh_ectx_plan", "gh_ectx_encode",
     "gh_ectx_download", "gh_ctx_device", "gh_sync_gaps", "gh_ctx_load_raw",
     "gh_ctx_load_file", "gh_ctx_save_file", "gh_dev_alloc", "gh_dev_free", "gh_dev_copy",
-    "gh_raw_parse", "gh_bw_copy",
+    "gh_raw_parse", "gh_bw_copy", "gh_ctx_kernel_shape", "gh_kernel_shapes",
 )
 
 
@@ -153,6 +153,8 @@ def lib() -> ctypes.CDLL:
             "gh_ectx_encode": ([P, ctypes.POINTER(ctypes.c_float)], I),
             "gh_ectx_download": ([P, P, U64], I),
             "gh_ctx_device": ([P, ctypes.POINTER(I)], I),
+            "gh_ctx_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_sync_gaps": ([I, P, U32, P, U64, P, P, ctypes.POINTER(gh_sync_report)], I),
             "gh_ctx_load_raw": ([P, P, U32, U64, P, U64, U64, ctypes.POINTER(gh_sync_report)], I),
             "gh_ctx_load_file": ([P, ctypes.c_char_p, U64, U64, U64, ctypes.POINTER(gh_file_info)], I),
@@ -323,6 +325,13 @@ def plan_shards(g: int, nshards: int) -> list:
     return [int(x) for x in b]
 
 
+def kernel_shapes() -> list:
+    """Every kernel name a load can pick (gh_kernel_shapes); needs no device."""
+    buf = ctypes.create_string_buffer(1 << 14)
+    _check(lib().gh_kernel_shapes(buf, len(buf)))
+    return buf.value.decode().split()
+
+
 def device_count() -> int:
     return int(lib().gh_device_count())
 
@@ -398,6 +407,12 @@ class Decoder:
         r = gh_report()
         _check(lib().gh_ctx_report(self._h, ctypes.c_void_p(hip_stream or None), ctypes.byref(r)))
         return r
+
+    def kernel_shape(self) -> str:
+        """Name of the kernel instantiation(s) the last load picked (gh_ctx_kernel_shape)."""
+        buf = ctypes.create_string_buffer(256)
+        _check(lib().gh_ctx_kernel_shape(self._h, buf, len(buf)))
+        return buf.value.decode()
 
     def reset_timing(self) -> None:
         _check(lib().gh_ctx_reset_timing(self._h))

@@ -202,6 +202,16 @@ int gh_ctx_reset_timing(gh_ctx* ctx);
 /* HIP device ordinal the context is bound to. */
 int gh_ctx_device(gh_ctx* ctx, int* device);
 
+/* Name of the kernel template instantiation the last load picked for the shard, NUL-
+ * terminated into buf[0..cap): "tile<TB,U,G,OW,MINL>" (single-pass tile kernel),
+ * "mtile<TB,GL,NS,fb=F,np=P>" (two-pass tile kernel) or
+ * "ws_count<U,TB,GL,fb=F>+ws_write<U,TB,GL,NS,fb=F>" (wave split); empty for an empty
+ * shard.  GH_E_SMALL when cap is too small, GH_E_STATE before a load. */
+int gh_ctx_kernel_shape(gh_ctx* ctx, char* buf, size_t cap);
+/* Every kernel name a load can pick (the count and write kernels of the wave split
+ * separately), one per line.  Needs no device. */
+int gh_kernel_shapes(char* buf, size_t cap);
+
 /* ---- streaming file I/O ------------------------------ */
 /* Replaces the reference CLI's whole-file fread + synchronous copies
  * (decoder/src/huff.cpp:90-140, decoder.cu:759-768): the file's gap words and the
