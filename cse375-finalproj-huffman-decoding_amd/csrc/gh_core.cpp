@@ -255,6 +255,82 @@ extern "C" int gh_stream_parse(const void* file, size_t len, gh_stream* out) {
 }
 
 // ---------------------------------------------------------------------------
+// Seek index (sidecar image, gaphuff.h): parse and locate.  The image is built by
+// gh_ctx_build_index (gh_decode.hip).  Entries are read with memcpy: the image may sit
+// at any alignment.
+// ---------------------------------------------------------------------------
+constexpr size_t IDX_HEADER = 40;
+
+static uint64_t idx_entry(const gh_index* ix, uint64_t k) { return rd<uint64_t>((const uint8_t*)ix->offsets + 8 * k); }
+
+extern "C" uint64_t gh_index_bytes(uint64_t g, uint32_t log2_stride) {
+  if (log2_stride < GH_INDEX_MIN_LOG2 || log2_stride > GH_INDEX_MAX_LOG2) return 0;
+  const uint64_t stride = 1ull << log2_stride;
+  const uint64_t nblocks = g / stride + (g % stride != 0);  // < 2^56: the byte count fits
+  return IDX_HEADER + 8 * (nblocks + 1);
+}
+
+extern "C" int gh_index_parse(const void* file, size_t len, gh_index* out) {
+  if (!file || !out) return fail(GH_E_ARG, "null argument");
+  const uint8_t* p = (const uint8_t*)file;
+  if (len < IDX_HEADER) return fail(GH_E_FORMAT, "index shorter than its header");
+  if (rd<uint64_t>(p) != GH_INDEX_MAGIC) return fail(GH_E_FORMAT, "not a seek index (magic)");
+  gh_index ix{};
+  ix.log2_stride = rd<uint32_t>(p + 8);
+  if (rd<uint32_t>(p + 12) != 0) return fail(GH_E_FORMAT, "index: reserved field not zero");
+  ix.n = rd<uint64_t>(p + 16);
+  ix.g = rd<uint64_t>(p + 24);
+  ix.nentries = rd<uint64_t>(p + 32);
+  const uint64_t bytes = gh_index_bytes(ix.g, ix.log2_stride);
+  if (bytes == 0) return fail(GH_E_FORMAT, "index: stride outside 2^8 .. 2^20 segments");
+  if (ix.nentries != (bytes - IDX_HEADER) / 8) return fail(GH_E_FORMAT, "index: entry count does not match G and the stride");
+  if (len < bytes) return fail(GH_E_FORMAT, "index shorter than its entries");
+  ix.offsets = (const uint64_t*)(p + IDX_HEADER);
+  if (idx_entry(&ix, 0) != 0) return fail(GH_E_FORMAT, "index: first entry not 0");
+  if (idx_entry(&ix, ix.nentries - 1) != ix.n) return fail(GH_E_FORMAT, "index: last entry not N");
+  // a segment holds at most 143 codewords (its codewords lie in at most 128 + 15 bits)
+  const uint64_t max_step = 143ull << ix.log2_stride;
+  uint64_t prev = 0;
+  for (uint64_t k = 1; k < ix.nentries; ++k) {
+    const uint64_t v = idx_entry(&ix, k);
+    if (v < prev) return fail(GH_E_FORMAT, "index: entries decrease");
+    if (v - prev > max_step) return fail(GH_E_FORMAT, "index: more symbols in a block than its segments can hold");
+    prev = v;
+  }
+  *out = ix;
+  return GH_OK;
+}
+
+extern "C" int gh_index_locate(const gh_index* ix, uint64_t lo, uint64_t hi, uint64_t* seg_begin,
+                               uint64_t* seg_end, uint64_t* skip) {
+  if (!ix || !ix->offsets || !seg_begin || !seg_end || !skip) return fail(GH_E_ARG, "null argument");
+  if (ix->nentries == 0) return fail(GH_E_ARG, "index without entries");
+  if (lo > hi || hi > ix->n) return fail(GH_E_ARG, "byte range outside [0, N]");
+  *seg_begin = *seg_end = *skip = 0;
+  if (lo == hi) return GH_OK;
+  const uint64_t nblocks = ix->nentries - 1;
+  if (nblocks == 0) return fail(GH_E_ARG, "index of an empty stream");
+  // k: the last block whose first symbol is at or before lo (entry 0 is 0 <= lo)
+  uint64_t a = 0, b = nblocks;  // offsets[a] <= lo; b == nblocks or offsets[b] > lo
+  while (b - a > 1) {
+    const uint64_t mid = a + (b - a) / 2;
+    if (idx_entry(ix, mid) <= lo) a = mid; else b = mid;
+  }
+  const uint64_t k = a;
+  // m: the first entry at or past hi (entry nblocks is N >= hi; entry 0 is 0 < hi)
+  a = 0, b = nblocks;  // offsets[a] < hi <= offsets[b]
+  while (b - a > 1) {
+    const uint64_t mid = a + (b - a) / 2;
+    if (idx_entry(ix, mid) < hi) a = mid; else b = mid;
+  }
+  const uint64_t m = b;
+  *seg_begin = k << ix->log2_stride;
+  *seg_end = std::min<uint64_t>(m << ix->log2_stride, ix->g);
+  *skip = lo - idx_entry(ix, k);
+  return GH_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Encoder
 // ---------------------------------------------------------------------------
 extern "C" int gh_encode_plan_make(const uint8_t* in, uint64_t n, int threads,

@@ -40,6 +40,7 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 
 #include "gh_tile.hip"
 #include "gh_wsplit.hip"
+#include "gh_index.hip"
 #include "gh_mtile.hip"
 
 }  // namespace gh
@@ -189,7 +190,7 @@ struct gh_ctx {
   bool loaded = false;
   Canon canon;
   // the loaded shard
-  uint64_t nseg = 0, seg_begin = 0, seg_end = 0, n_total = 0;
+  uint64_t nseg = 0, seg_begin = 0, seg_end = 0, n_total = 0, g_total = 0;
   uint32_t gap_nib0 = 0, first_start = 0;
   uint32_t* d_payload = nullptr;
   uint32_t* d_gaps = nullptr;
@@ -741,6 +742,7 @@ static int load_common(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e, ui
   c->seg_begin = b;
   c->seg_end = e;
   c->n_total = s->n;
+  c->g_total = s->g;
   if (c->nseg > 0 && cn.nsyms == 0) return fail(GH_E_TABLE, "empty code");
   const uint64_t per_seg = cn.minlen ? (128 + cn.minlen - 1) / cn.minlen : 128;  // codewords per segment, at most
   if (out_cap == 0) out_cap = std::min<uint64_t>(s->n, c->nseg * per_seg);
@@ -1131,6 +1133,151 @@ extern "C" int gh_ctx_copy_output(gh_ctx* c, uint64_t off, void* dst, uint64_t n
   GH_HIP(hipSetDevice(c->device));
   if (c->done_rec) GH_HIP(hipStreamWaitEvent(st, c->done_ev, 0));  // after the last decode
   GH_HIP(hipMemcpyAsync(dst, c->d_out + off, nbytes, hipMemcpyDefault, st));
+  return GH_OK;
+}
+
+// ---- seek index (gh_index.hip) ------------------------------------------------------
+// The index kernels are not decode shapes: no load picks them, gh_kernel_shapes does not
+// list them.  By the count table's width and the fallback, as ws_kernels' count kernel.
+static const void* index_kernel_for(uint32_t kc, bool fb) {
+  if (fb) return (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 2, true>;
+  const int gl = lookups_per_shift(kc);
+  return gl >= 4 ? (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 4, false>
+       : gl == 3 ? (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 3, false>
+                 : (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 2, false>;
+}
+
+namespace {
+struct DevMem {  // device memory of one gh_ctx_build_index call
+  void* p = nullptr;
+  ~DevMem() { if (p) (void)hipFree(p); }
+};
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+}  // namespace
+
+extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, uint64_t out_len,
+                                  uint64_t* symbols, float* kernel_ms) {
+  if (!c || !out) return fail(GH_E_ARG, "null argument");
+  if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_build_index before gh_ctx_load");
+  const uint64_t bytes = gh_index_bytes(c->g_total, log2_stride);
+  if (bytes == 0) return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
+  if (c->seg_begin != 0 || c->seg_end != c->g_total)
+    return fail(GH_E_ARG, "gh_ctx_build_index: the load must cover segments [0, G)");
+  if (out_len < bytes) return fail(GH_E_SMALL, "index buffer smaller than gh_index_bytes");
+  const uint64_t nblocks = (bytes - 40) / 8 - 1;
+  std::vector<uint64_t> counts(nblocks, 0);
+  float ms = 0;
+  GH_HIP(hipSetDevice(c->device));
+  if (int rc = wait_decode(c)) return rc;
+  if (c->nseg > 0) {
+    const Canon& cn = c->canon;
+    // The context's decode mode may be a tile kernel, which keeps no count table on the
+    // device: the build makes its own table and fallback tables, and frees them.
+    const uint32_t kc = ws_count_bits(cn);
+    const bool fb = kraft16(cn) != 65536 || cn.maxlen > kc;
+    std::vector<uint32_t> lc;
+    count_lut(cn, kc, &lc);
+    uint32_t fbt[FB_WORDS];
+    fallback_tables(cn, fbt);
+    DevMem d_lut, d_fb, d_cnt, d_status;
+    GH_HIP(hipMalloc(&d_lut.p, 4ull << kc));
+    GH_HIP(hipMemcpy(d_lut.p, lc.data(), 4ull << kc, hipMemcpyHostToDevice));
+    GH_HIP(hipMalloc(&d_fb.p, sizeof(fbt)));
+    GH_HIP(hipMemcpy(d_fb.p, fbt, sizeof(fbt), hipMemcpyHostToDevice));
+    GH_HIP(hipMalloc(&d_cnt.p, 8 * nblocks));
+    GH_HIP(hipMemset(d_cnt.p, 0, 8 * nblocks));
+    GH_HIP(hipMalloc(&d_status.p, 16));
+    GH_HIP(hipMemset(d_status.p, 0, 16));
+    // the stream's last segment ends by the decode's rule (last_segment_end): its words
+    // and its start bit from the device copies, as gh_ctx_load_device reads them
+    uint32_t w5[5] = {};
+    GH_HIP(hipMemcpy(w5, c->d_payload + 4 * (c->nseg - 1), sizeof(w5), hipMemcpyDeviceToHost));  // (16 padding words follow)
+    uint32_t st = c->first_start;
+    if (c->nseg > 1) {
+      const uint64_t nib = c->gap_nib0 + c->nseg - 2;
+      uint32_t wv = 0;
+      GH_HIP(hipMemcpy(&wv, c->d_gaps + (nib >> 3), 4, hipMemcpyDeviceToHost));
+      st = (wv >> (4 * (nib & 7))) & 15u;
+    }
+    IdxParams ip{};
+    ip.w.payload = c->d_payload;
+    ip.w.gaps = c->d_gaps;
+    ip.w.lut = (const uint2*)d_lut.p;
+    ip.w.status = (unsigned int*)d_status.p;
+    ip.w.nseg = (uint32_t)c->nseg;
+    ip.w.gap_nib0 = c->gap_nib0;
+    ip.w.first_start = c->first_start;
+    ip.w.kbits = kc;
+    ip.w.lut_bytes = (uint32_t)(4u << kc);
+    ip.w.last_end = last_segment_end(cn, w5, st);
+    ip.w.fb = (const uint32_t*)d_fb.p;
+    ip.w.fb_lo = std::max<uint32_t>(cn.minlen, 1);
+    ip.w.fb_hi = std::max<uint32_t>(cn.maxlen, ip.w.fb_lo);
+    ip.w.chk_pay = 4 * c->nseg + 16;
+    ip.w.chk_gap = c->nseg / 8 + 4;
+    ip.counts = (unsigned long long*)d_cnt.p;
+    ip.nblocks = (uint32_t)nblocks;
+    ip.log2_stride = log2_stride;
+    const void* kern = index_kernel_for(kc, fb);
+    const size_t lds = std::max<size_t>(4ull << kc, 64) + (fb ? FB_BYTES : 0);
+    if (lds > 64 * 1024) GH_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int pc = 0;
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern, IDX_TB, lds));
+    if (pc < 1) return fail(GH_E_HIP, "the index kernel does not fit on a CU");
+    // every workgroup that has an index block, at most what the device holds at once
+    uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)pc * c->num_cu, ceil_div(nblocks, (uint64_t)(IDX_TB / 64)));
+    if (const char* eg = getenv("GH_INDEX_GRID"))  // tests: few workgroups, many index blocks per wave
+      grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
+    EventPair ev;
+    GH_HIP(hipEventCreate(&ev.a));
+    GH_HIP(hipEventCreate(&ev.b));
+    void* args[1] = {&ip};
+    {
+      // Joins the device's decode chain: a persistent tile kernel assumes its whole grid
+      // is resident, so the build starts after the device's last tile decode, and the
+      // chain stays locked until the build has finished (no tile decode of any context
+      // is launched while it runs).
+      DevChain& dc = dev_chain(c->device);
+      std::lock_guard<std::mutex> chain_lock(dc.mu);
+      if (dc.has) GH_HIP(hipStreamWaitEvent(c->stream, dc.last, 0));
+      GH_HIP(hipEventRecord(ev.a, c->stream));
+      GH_HIP(hipLaunchKernel(kern, dim3(grid), dim3(IDX_TB), args, lds, c->stream));
+      GH_HIP(hipGetLastError());
+      GH_HIP(hipEventRecord(ev.b, c->stream));
+      GH_HIP(hipStreamSynchronize(c->stream));
+    }
+    GH_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+    unsigned int status = 0;
+    GH_HIP(hipMemcpy(&status, d_status.p, 4, hipMemcpyDeviceToHost));
+    GH_HIP(hipMemcpy(counts.data(), d_cnt.p, 8 * nblocks, hipMemcpyDeviceToHost));
+    if (status & GH_ST_LAYOUT) return fail(GH_E_HIP, "index kernel: LDS layout assumption violated");
+    if (status & GH_ST_BADCODE) return fail(GH_E_CORRUPT, "invalid code in stream");
+  }
+  // exclusive scan of the block counts on the host; the last entry is N
+  uint8_t* o = (uint8_t*)out;
+  auto put64 = [&](size_t at, uint64_t v) { std::memcpy(o + at, &v, 8); };
+  uint64_t run = 0;
+  for (uint64_t k = 0; k < nblocks; ++k) {
+    if (run > c->n_total) return fail(GH_E_CORRUPT, "stream holds more than N symbols before its last segments");
+    put64(40 + 8 * k, run);
+    run += counts[k];
+  }
+  if (run < c->n_total) return fail(GH_E_CORRUPT, "stream holds fewer than N symbols");
+  put64(40 + 8 * nblocks, c->n_total);
+  put64(0, GH_INDEX_MAGIC);
+  const uint32_t hdr[2] = {log2_stride, 0u};
+  std::memcpy(o + 8, hdr, 8);
+  put64(16, c->n_total);
+  put64(24, c->g_total);
+  put64(32, nblocks + 1);
+  if (symbols) *symbols = run;
+  if (kernel_ms) *kernel_ms = ms;
   return GH_OK;
 }
 

@@ -49,6 +49,7 @@ EXPORTED = (
     "gh_ectx_download", "gh_ctx_device", "gh_sync_gaps", "gh_ctx_load_raw",
     "gh_ctx_load_file", "gh_ctx_save_file", "gh_dev_alloc", "gh_dev_free", "gh_dev_copy",
     "gh_raw_parse", "gh_bw_copy", "gh_ctx_kernel_shape", "gh_kernel_shapes",
+    "gh_index_bytes", "gh_index_parse", "gh_index_locate", "gh_ctx_build_index",
 )
 
 
@@ -98,6 +99,11 @@ class gh_file_info(ctypes.Structure):
 class gh_raw_stream(ctypes.Structure):
     _fields_ = [("syms", ctypes.POINTER(gh_sym)), ("nsyms", ctypes.c_uint32), ("n", ctypes.c_uint64),
                 ("w", ctypes.c_uint64), ("units", ctypes.c_void_p)]
+
+
+class gh_index(ctypes.Structure):
+    _fields_ = [("log2_stride", ctypes.c_uint32), ("n", ctypes.c_uint64), ("g", ctypes.c_uint64),
+                ("nentries", ctypes.c_uint64), ("offsets", ctypes.c_void_p)]
 
 
 class gh_sync_report(ctypes.Structure):
@@ -164,6 +170,11 @@ def lib() -> ctypes.CDLL:
             "gh_dev_free": ([P], I),
             "gh_dev_copy": ([P, P, U64], I),
             "gh_bw_copy": ([P, P, U64, P, I, ctypes.POINTER(ctypes.c_float)], I),
+            "gh_index_bytes": ([U64, U32], U64),
+            "gh_index_parse": ([P, ctypes.c_size_t, ctypes.POINTER(gh_index)], I),
+            "gh_index_locate": ([ctypes.POINTER(gh_index), U64, U64, ctypes.POINTER(U64), ctypes.POINTER(U64),
+                                 ctypes.POINTER(U64)], I),
+            "gh_ctx_build_index": ([P, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_float)], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -345,6 +356,7 @@ class Decoder:
         _check(lib().gh_ctx_create(device, ctypes.byref(self._h)))
         self.device = device
         self._stream: Optional[Stream] = None
+        self._file_g: Optional[int] = None  # G of the last load_file / load_raw
 
     def close(self) -> None:
         if self._h:
@@ -378,6 +390,7 @@ class Decoder:
                                       (1 << 64) - 1 if seg_end is None else seg_end, out_cap,
                                       ctypes.byref(info)))
         self._stream = None
+        self._file_g = int(info.g)
         return info
 
     def save_file(self, path: str, nbytes: int, file_offset: int = 0, offset: int = 0,
@@ -398,6 +411,7 @@ class Decoder:
         _check(lib().gh_ctx_load_raw(self._h, ctypes.byref(sy), len(symbols), n, _ptr(u), u.size, out_cap,
                                      ctypes.byref(r)))
         self._stream = None
+        self._file_g = int(r.g)
         return r
 
     def decode(self, hip_stream: int = 0, timed: bool = True) -> None:
@@ -413,6 +427,20 @@ class Decoder:
         buf = ctypes.create_string_buffer(256)
         _check(lib().gh_ctx_kernel_shape(self._h, buf, len(buf)))
         return buf.value.decode()
+
+    def build_index(self, log2_stride: int = 8):
+        """Seek index of the loaded stream (the load must cover all its segments), built on
+        the GPU: (sidecar image as np.uint8, codewords counted, kernel ms)."""
+        g = self._stream.g if self._stream is not None else (self._file_g or 0)
+        nbytes = int(lib().gh_index_bytes(g, log2_stride))
+        if nbytes == 0:
+            raise GapHuffError(-1, "index stride outside 2^8 .. 2^20 segments")
+        img = np.zeros(nbytes, dtype=np.uint8)
+        symbols = ctypes.c_uint64()
+        ms = ctypes.c_float()
+        _check(lib().gh_ctx_build_index(self._h, log2_stride, _ptr(img), img.size, ctypes.byref(symbols),
+                                        ctypes.byref(ms)))
+        return img, int(symbols.value), float(ms.value)
 
     def reset_timing(self) -> None:
         _check(lib().gh_ctx_reset_timing(self._h))
@@ -448,6 +476,77 @@ def decode(file_bytes, ngpus: int = 1, devices: Optional[Sequence[int]] = None,
     r = gh_report()
     _check(lib().gh_decode(ctypes.byref(s.c), _ptr(out), out.size, ctypes.byref(o), ctypes.byref(r)))
     return out[: s.n]
+
+
+# --------------------------------------------------------------------------- random access
+@dataclass
+class Index:
+    """A parsed seek index (keeps the image bytes alive)."""
+
+    raw: np.ndarray
+    c: gh_index
+
+    @property
+    def log2_stride(self) -> int:
+        return int(self.c.log2_stride)
+
+    @property
+    def n(self) -> int:
+        return int(self.c.n)
+
+    @property
+    def g(self) -> int:
+        return int(self.c.g)
+
+    @property
+    def offsets(self) -> np.ndarray:
+        """The nentries output offsets (a view of the image)."""
+        return self.raw[40: 40 + 8 * int(self.c.nentries)].view("<u8")
+
+    def locate(self, lo: int, hi: int):
+        """(seg_begin, seg_end, skip) for output bytes [lo, hi) (gh_index_locate)."""
+        b, e, skip = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().gh_index_locate(ctypes.byref(self.c), lo, hi, ctypes.byref(b), ctypes.byref(e),
+                                     ctypes.byref(skip)))
+        return int(b.value), int(e.value), int(skip.value)
+
+
+def parse_index(image) -> Index:
+    raw = _u8(image)
+    ix = gh_index()
+    _check(lib().gh_index_parse(_ptr(raw), raw.size, ctypes.byref(ix)))
+    return Index(raw, ix)
+
+
+def decode_range(src, index, lo: int, hi: int, device: int = 0) -> np.ndarray:
+    """Bytes [lo, hi) of the original data: loads and decodes only the segments the
+    index names for them.  ``src``: a :class:`Stream`, the file's bytes, or a path (then
+    only the header, the gap array and those segments' payload are read,
+    gh_ctx_load_file).  ``index``: an :class:`Index` or a sidecar image."""
+    ix = index if isinstance(index, Index) else parse_index(index)
+    b, e, skip = ix.locate(lo, hi)
+    cap = skip + (hi - lo)
+    with Decoder(device) as d:
+        if isinstance(src, (str, os.PathLike)):
+            # (segments past the file's G are refused by the load itself, with GH_E_ARG too)
+            info = d.load_file(os.fspath(src), b, e, cap)
+            n, g = int(info.n), int(info.g)
+        else:
+            s = src if isinstance(src, Stream) else parse(src)
+            n, g = s.n, s.g
+            if (n, g) == (ix.n, ix.g):
+                d.load(s, b, e, cap)
+        if (n, g) != (ix.n, ix.g):
+            raise GapHuffError(-1, f"the index is for N = {ix.n}, G = {ix.g}; the stream has N = {n}, G = {g}")
+        if hi == lo:
+            return np.zeros(0, dtype=np.uint8)
+        d.decode(timed=False)
+        rep = d.report()
+        if rep.status:
+            raise GapHuffError(-7, f"device status {rep.status}")
+        if rep.symbols < cap:  # never hand back undecoded (uninitialised) output bytes
+            raise GapHuffError(-7, f"segments [{b}, {e}) decoded to {rep.symbols} of {cap} symbols")
+        return d.download(hi - lo, offset=skip)
 
 
 def _syms(symbols: Sequence[tuple]):

@@ -1,9 +1,13 @@
 // bin/decoder <compressed.huff | raw container> <output> [--gpus N] [--shards S] [--reps R] [--json]
-//             [--verify FILE]
+//             [--verify FILE] [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]
 // --shards S (default: one per GPU) splits the gap segments into S shards, shard k on
 // device k mod N, each streaming its own payload range and writing at its offset.
 // A raw-stream container (bin/encoder --raw, GH_RAW_MAGIC) is decoded by the
 // self-synchronising path (gh_ctx_load_raw) on one GPU.
+// --write-index FILE (single-shard runs) builds the stream's seek index on the GPU after
+// the load, one entry per 2^K segments (--index-stride K, 8..20, default 8), and writes
+// the sidecar image.  --index FILE --range LO:HI decodes only the segments that hold
+// output bytes [LO, HI) and writes just those bytes to the output.
 //
 // Drop-in for the reference decoder CLI (Huffman_coding_Gap_arrays/decoder/src/
 // huff.cpp:22-142, used as `./bin/decoder in out` by run_huffman.sh:38), decoding on
@@ -59,18 +63,27 @@ static int die(const char* what, int rc) {
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr,
-                 "Usage: bin/decoder input output [--gpus N] [--shards S] [--reps R] [--json] [--verify FILE]\n");
+                 "Usage: bin/decoder input output [--gpus N] [--shards S] [--reps R] [--json] [--verify FILE]\n"
+                 "       [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]\n");
     return 2;
   }
   int ngpus = 1, reps = 1, nshards = 0;
   bool json = false;
   const char* verify = nullptr;
+  const char* write_index = nullptr;
+  const char* index_file = nullptr;
+  const char* range = nullptr;
+  int index_stride = GH_INDEX_MIN_LOG2;
   for (int i = 3; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) ngpus = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--shards") && i + 1 < argc) nshards = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--reps") && i + 1 < argc) reps = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--json")) json = true;
     else if (!std::strcmp(argv[i], "--verify") && i + 1 < argc) verify = argv[++i];
+    else if (!std::strcmp(argv[i], "--write-index") && i + 1 < argc) write_index = argv[++i];
+    else if (!std::strcmp(argv[i], "--index-stride") && i + 1 < argc) index_stride = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--index") && i + 1 < argc) index_file = argv[++i];
+    else if (!std::strcmp(argv[i], "--range") && i + 1 < argc) range = argv[++i];
     else {
       std::fprintf(stderr, "decoder: unknown option %s\n", argv[i]);
       return 2;
@@ -78,6 +91,34 @@ int main(int argc, char** argv) {
   }
   if (ngpus < 1) ngpus = 1;
   if (reps < 1) reps = 1;
+  // --index FILE --range LO:HI: the segments to load, from the sidecar alone
+  const bool ranged = index_file || range;
+  uint64_t lo = 0, hi = 0, rb = 0, re = 0, skip = 0;
+  gh_index ix{};
+  std::vector<uint8_t> ix_img;
+  if (ranged) {
+    char* end = nullptr;
+    if (!index_file || !range || write_index) {
+      std::fprintf(stderr, "decoder: --index FILE and --range LO:HI go together (and not with --write-index)\n");
+      return 2;
+    }
+    lo = std::strtoull(range, &end, 10);
+    if (end == range || *end != ':') { std::fprintf(stderr, "decoder: --range LO:HI\n"); return 2; }
+    const char* h = end + 1;
+    hi = std::strtoull(h, &end, 10);
+    if (end == h || *end) { std::fprintf(stderr, "decoder: --range LO:HI\n"); return 2; }
+    FILE* f = std::fopen(index_file, "rb");
+    if (!f) { std::fprintf(stderr, "decoder: Could not open index file %s\n", index_file); return 1; }
+    std::fseek(f, 0, SEEK_END);
+    ix_img.resize((size_t)std::max(std::ftell(f), 0L));
+    std::fseek(f, 0, SEEK_SET);
+    const bool okr = std::fread(ix_img.data(), 1, ix_img.size(), f) == ix_img.size();
+    std::fclose(f);
+    int r = okr ? gh_index_parse(ix_img.data(), ix_img.size(), &ix) : GH_E_FORMAT;
+    if (!r) r = gh_index_locate(&ix, lo, hi, &rb, &re, &skip);
+    if (r) return die("bad index / range", r);
+    ngpus = nshards = 1;
+  }
 
   // Header first (sizes for the shard plan); each shard then streams its own payload
   // range from the file (gh_ctx_load_file: pinned double-buffered read -> H2D).
@@ -94,6 +135,10 @@ int main(int argc, char** argv) {
     std::fclose(f);
   }
   if (is_raw) ngpus = nshards = 1;  // a raw stream's segment entries are found on one device
+  if (is_raw && ranged) {
+    std::fprintf(stderr, "decoder: --range needs a gap-array file\n");
+    return 2;
+  }
   const int ndev = gh_device_count();
   if (ndev < 1) return die("no HIP device", GH_E_NODEV);
   if (ngpus > ndev) ngpus = ndev;
@@ -128,6 +173,18 @@ int main(int argc, char** argv) {
     bounds[1] = info.g;
     std::printf("Raw stream: gap array built on the GPU in %.3f ms (%llu boundaries repaired)\n",
                 sr.kernel_ms, (unsigned long long)sr.mismatches);
+  } else if (ranged) {
+    if ((rc = gh_ctx_load_file(ctx[0], argv[1], rb, re, skip + (hi - lo), &info))) {
+      cleanup();
+      return die("bad compressed stream / upload", rc);
+    }
+    if (info.n != ix.n || info.g != ix.g) {
+      cleanup();
+      std::fprintf(stderr, "decoder: the index is for another stream (N or G differ)\n");
+      return 1;
+    }
+    bounds[0] = rb;
+    bounds[1] = re;
   } else if (nshards == 1) {
     if ((rc = gh_ctx_load_file(ctx[0], argv[1], 0, UINT64_MAX, 0, &info))) {
       cleanup();
@@ -157,6 +214,25 @@ int main(int argc, char** argv) {
   std::printf("Input file: %s\n", argv[1]);
   std::printf("Original size: %llu bytes\n", (unsigned long long)s.n);
   std::printf("Compressed size: %llu bytes\n", (unsigned long long)s.w);  // reference prints W
+  if (write_index) {
+    if (nshards != 1) {
+      cleanup();
+      std::fprintf(stderr, "decoder: --write-index needs a single-shard run\n");
+      return 2;
+    }
+    std::vector<uint8_t> img((size_t)gh_index_bytes(info.g, (uint32_t)index_stride));
+    float ims = 0;
+    if (img.empty()) { cleanup(); std::fprintf(stderr, "decoder: --index-stride 8..20\n"); return 2; }
+    if ((rc = gh_ctx_build_index(ctx[0], (uint32_t)index_stride, img.data(), img.size(), nullptr, &ims))) {
+      cleanup();
+      return die("index build", rc);
+    }
+    FILE* f = std::fopen(write_index, "wb");
+    bool okw = f && std::fwrite(img.data(), 1, img.size(), f) == img.size();
+    if (f) okw = std::fclose(f) == 0 && okw;
+    if (!okw) { cleanup(); std::fprintf(stderr, "decoder: cannot write %s\n", write_index); return 1; }
+    std::printf("Index: %zu bytes (one entry per %u segments), built in %.3f ms\n", img.size(), 1u << index_stride, ims);
+  }
   const double t1 = now_ms();
   for (int r = 0; r < reps; ++r)
     for (int k = 0; k < nshards; ++k)
@@ -180,7 +256,9 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "decoder: device reported status 0x%x (corrupted stream?)\n", status);
     return 1;
   }
-  if (total < s.n) {
+  // bytes to write: the whole stream, or the range's (at byte `skip` of the shard's output)
+  const uint64_t need = ranged ? skip + (hi - lo) : s.n;
+  if (total < need) {
     cleanup();
     std::fprintf(stderr, "decoder: stream decoded to %llu < N symbols\n", (unsigned long long)total);
     return 1;
@@ -195,7 +273,7 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "decoder: shard %d overflowed its output (corrupted stream?)\n", k);
       return 1;
     }
-    want[k] = off[k] < s.n ? std::min<uint64_t>(rep[k].symbols, s.n - off[k]) : 0;
+    want[k] = ranged ? hi - lo : off[k] < s.n ? std::min<uint64_t>(rep[k].symbols, s.n - off[k]) : 0;
     off[k + 1] = off[k] + rep[k].symbols;
   }
   {  // create / truncate the output once, then every shard writes its range concurrently
@@ -208,7 +286,7 @@ int main(int argc, char** argv) {
     std::fclose(f);
   }
   if ((rc = for_each_shard(nshards, [&](int k) {
-         return gh_ctx_save_file(ctx[k], argv[2], off[k], 0, want[k], 0, nullptr);
+         return gh_ctx_save_file(ctx[k], argv[2], off[k], ranged ? skip : 0, want[k], 0, nullptr);
        }))) {
     cleanup();
     return die("write output", rc);
@@ -237,7 +315,7 @@ int main(int argc, char** argv) {
         seen += a;
         if (a == 0) break;
       }
-      if (seen != s.n) ok = 0;
+      if (seen != (ranged ? hi - lo : s.n)) ok = 0;
     }
     if (v) std::fclose(v);
     if (o) std::fclose(o);

@@ -236,6 +236,49 @@ int gh_ctx_load_file(gh_ctx* ctx, const char* path, uint64_t seg_begin, uint64_t
 int gh_ctx_save_file(gh_ctx* ctx, const char* path, uint64_t file_offset, uint64_t byte_offset,
                      uint64_t nbytes, int truncate, double* ms);
 
+/* ---- random access: seek index and byte-range decode --------------------------- */
+/* A shard load decodes any segment range on its own; the seek index maps an output byte
+ * offset to the segment that holds it, so bytes [lo, hi) of the original data are read
+ * without decoding the rest.  No reference counterpart (the reference decodes whole
+ * streams only).  With stride = 1 << log2_stride segments (log2_stride in
+ * GH_INDEX_MIN_LOG2..GH_INDEX_MAX_LOG2) and nblocks = ceil(G / stride), the index holds
+ * nblocks + 1 entries: offsets[k], k < nblocks, is the number of codewords that start
+ * before payload bit 128 * stride * k (the output offset of segment k * stride's first
+ * symbol; offsets[0] = 0), and offsets[nblocks] = N.  Sidecar image, little-endian:
+ *   u64 GH_INDEX_MAGIC ("GHIDX1\0\0"), u32 log2_stride, u32 0, u64 N, u64 G,
+ *   u64 nentries, nentries x u64 offsets. */
+#define GH_INDEX_MAGIC 0x0000315844494847ull
+#define GH_INDEX_MIN_LOG2 8
+#define GH_INDEX_MAX_LOG2 20
+typedef struct gh_index {
+  uint32_t log2_stride;
+  uint64_t n, g, nentries;
+  const uint64_t* offsets;   /* view into the image (any alignment: read it with memcpy) */
+} gh_index;
+/* Size of the image for G segments; 0 on a stride outside the range. */
+uint64_t gh_index_bytes(uint64_t g, uint32_t log2_stride);
+/* Parse an image (views into `file`).  GH_E_FORMAT unless: the magic and the stride are
+ * right, nentries = ceil(G / stride) + 1, the image holds them, the first entry is 0
+ * and the last N, the entries never decrease, and no step exceeds 143 * stride (a
+ * segment holds at most 143 codewords). */
+int gh_index_parse(const void* file, size_t file_len, gh_index* out);
+/* Segments to load for output bytes [lo, hi): load [*seg_begin, *seg_end) with out_cap =
+ * *skip + (hi - lo); the bytes start at byte *skip of that shard's output.  seg_begin =
+ * k * stride for the last block k with offsets[k] <= lo, seg_end = min(m * stride, G)
+ * for the first entry m with offsets[m] >= hi; an empty segment range when lo == hi.
+ * GH_E_ARG when lo > hi or hi > N. */
+int gh_index_locate(const gh_index* ix, uint64_t lo, uint64_t hi, uint64_t* seg_begin,
+                    uint64_t* seg_end, uint64_t* skip);
+/* Index of the stream loaded in ctx (the load must cover segments [0, G)); writes the
+ * sidecar image (gh_index_bytes bytes) into out.  symbols (may be NULL): codewords
+ * counted over all segments, the last segment's padding included (= gh_report.symbols
+ * of a decode).  kernel_ms (may be NULL): HIP-event time of the kernel(s).  Synchronous.
+ * GH_E_STATE before a load, GH_E_ARG when the load does not cover [0, G) or the stride
+ * is bad, GH_E_SMALL when out_len is too small, GH_E_CORRUPT when the stream holds
+ * fewer than N codewords. */
+int gh_ctx_build_index(gh_ctx* ctx, uint32_t log2_stride, void* out, uint64_t out_len,
+                       uint64_t* symbols, float* kernel_ms);
+
 /* ---- self-synchronising decode of gap-less streams ---- */
 /* Replaces CUHD's decoder for raw Huffman streams without a gap array
  * (gpuhd/src/cuhd_gpu_decoder.cu:145-523, CUHDGPUDecoder::decode declared at
