@@ -330,6 +330,51 @@ extern "C" int gh_index_locate(const gh_index* ix, uint64_t lo, uint64_t hi, uin
   return GH_OK;
 }
 
+// Range gather plan (gh_ctx_gather): every range cut at the index entries it spans.  A
+// piece never reaches past its block's symbols (b <= offsets[k+1] - offsets[k] <= 143 *
+// stride < 2^32, gh_index_parse), and blocks without symbols are skipped (a == b).
+extern "C" int gh_gather_plan(const gh_index* ix, const gh_range* ranges, uint32_t nranges,
+                              gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces,
+                              uint64_t* out_bytes) {
+  if (npieces) *npieces = 0;
+  if (out_bytes) *out_bytes = 0;
+  if (!ix || !ix->offsets || !npieces || !out_bytes || (nranges && !ranges) || (cap && !pieces))
+    return fail(GH_E_ARG, "null argument");
+  if (ix->nentries == 0) return fail(GH_E_ARG, "index without entries");
+  const uint64_t nblocks = ix->nentries - 1;
+  if (nblocks > 0xFFFFFFFFull) return fail(GH_E_ARG, "index of more than 2^32 blocks");
+  uint64_t np = 0, dst = 0;
+  for (uint32_t i = 0; i < nranges; ++i) {
+    const uint64_t lo = ranges[i].lo, hi = ranges[i].hi;
+    if (lo > hi || hi > ix->n) {
+      *npieces = *out_bytes = 0;
+      return fail(GH_E_ARG, "byte range outside [0, N]");
+    }
+    if (lo == hi) continue;  // (then N > 0: nblocks >= 1)
+    // k: the last block whose first symbol is at or before lo (entry 0 is 0 <= lo)
+    uint64_t a = 0, b = nblocks;  // offsets[a] <= lo; b == nblocks or offsets[b] > lo
+    while (b - a > 1) {
+      const uint64_t mid = a + (b - a) / 2;
+      if (idx_entry(ix, mid) <= lo) a = mid; else b = mid;
+    }
+    uint64_t o0 = idx_entry(ix, a);
+    for (uint64_t k = a; k < nblocks && o0 < hi; ++k) {
+      const uint64_t o1 = idx_entry(ix, k + 1);
+      const uint64_t pa = std::max(lo, o0), pb = std::min(hi, o1);
+      if (pa < pb) {
+        if (np < cap) pieces[np] = gh_gather_piece{dst, (uint32_t)k, (uint32_t)(pa - o0), (uint32_t)(pb - o0), 0u};
+        ++np;
+        dst += pb - pa;
+      }
+      o0 = o1;
+    }
+  }
+  *npieces = np;
+  *out_bytes = dst;
+  if (np > cap) return fail(GH_E_SMALL, "piece buffer smaller than the plan");
+  return GH_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Encoder
 // ---------------------------------------------------------------------------

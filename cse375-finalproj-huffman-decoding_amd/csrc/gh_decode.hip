@@ -41,6 +41,7 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 #include "gh_tile.hip"
 #include "gh_wsplit.hip"
 #include "gh_index.hip"
+#include "gh_gather.hip"
 #include "gh_mtile.hip"
 
 }  // namespace gh
@@ -233,6 +234,24 @@ struct gh_ctx {
   uint4* d_ws_junk = nullptr;
   unsigned long long* d_rng_tot = nullptr;
   unsigned long long* d_rng_off = nullptr;
+  // range gather (gh_ctx_gather): the tables live from the first gather to the next load,
+  // the piece and output buffers for the life of the context (grown on demand)
+  bool ga_ready = false;
+  bool ga_fb = false;
+  uint32_t ga_kc = 0, ga_ks = 0;   // count / symbol table widths
+  uint32_t ga_last_end = 0;
+  uint32_t ga_wgs = 0;             // workgroups the device holds at once
+  size_t ga_lds = 0;
+  const void* ga_kern = nullptr;
+  uint32_t* d_ga_lut_c = nullptr;  // count table {b | end mask << 16}
+  uint32_t* d_ga_lut_s = nullptr;  // symbol table {len | symbol << 8}
+  uint32_t* d_ga_fb = nullptr;     // canonical fallback tables
+  gh_gather_piece* d_ga_pieces = nullptr;
+  uint64_t ga_pieces_cap = 0;
+  uint8_t* d_ga_out = nullptr;
+  uint64_t ga_out_cap = 0;
+  std::vector<gh_gather_piece> ga_pieces;
+  hipEvent_t ga_ev0 = nullptr, ga_ev1 = nullptr;
   // timing
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, pool;
   double acc_ms = 0;
@@ -243,8 +262,13 @@ static void free_shard(gh_ctx* c) {
   (void)hipSetDevice(c->device);
   for (void* p : {(void*)c->d_payload, (void*)c->d_gaps, (void*)c->d_out, (void*)c->d_gran, (void*)c->d_lut_t,
                   (void*)c->d_stamps, (void*)c->d_ws_lut_c, (void*)c->d_ws_lut_w, (void*)c->d_fb,
-                  (void*)c->d_seg_cnt, (void*)c->d_ws_junk, (void*)c->d_rng_tot, (void*)c->d_rng_off})
+                  (void*)c->d_seg_cnt, (void*)c->d_ws_junk, (void*)c->d_rng_tot, (void*)c->d_rng_off,
+                  (void*)c->d_ga_lut_c, (void*)c->d_ga_lut_s, (void*)c->d_ga_fb})
     (void)hipFree(p);
+  c->d_ga_lut_c = nullptr;
+  c->d_ga_lut_s = nullptr;
+  c->d_ga_fb = nullptr;
+  c->ga_ready = false;
   c->d_payload = nullptr;
   c->d_gaps = nullptr;
   c->d_out = nullptr;
@@ -715,6 +739,10 @@ extern "C" int gh_ctx_destroy(gh_ctx* c) {
   }
   free_shard(c);
   (void)hipFree(c->d_misc);
+  (void)hipFree(c->d_ga_pieces);
+  (void)hipFree(c->d_ga_out);
+  if (c->ga_ev0) (void)hipEventDestroy(c->ga_ev0);
+  if (c->ga_ev1) (void)hipEventDestroy(c->ga_ev1);
   for (auto& e : c->pending) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
@@ -1147,6 +1175,22 @@ static const void* index_kernel_for(uint32_t kc, bool fb) {
                  : (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 2, false>;
 }
 
+// End of the last loaded segment (nseg > 0) by the decode's rule (last_segment_end): its
+// words and its start bit from the device copies, as gh_ctx_load_device reads them.
+static int loaded_last_end(gh_ctx* c, uint32_t* out) {
+  uint32_t w5[5] = {};
+  GH_HIP(hipMemcpy(w5, c->d_payload + 4 * (c->nseg - 1), sizeof(w5), hipMemcpyDeviceToHost));  // (16 padding words follow)
+  uint32_t st = c->first_start;
+  if (c->nseg > 1) {
+    const uint64_t nib = c->gap_nib0 + c->nseg - 2;
+    uint32_t wv = 0;
+    GH_HIP(hipMemcpy(&wv, c->d_gaps + (nib >> 3), 4, hipMemcpyDeviceToHost));
+    st = (wv >> (4 * (nib & 7))) & 15u;
+  }
+  *out = last_segment_end(c->canon, w5, st);
+  return GH_OK;
+}
+
 namespace {
 struct DevMem {  // device memory of one gh_ctx_build_index call
   void* p = nullptr;
@@ -1194,17 +1238,8 @@ extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, ui
     GH_HIP(hipMemset(d_cnt.p, 0, 8 * nblocks));
     GH_HIP(hipMalloc(&d_status.p, 16));
     GH_HIP(hipMemset(d_status.p, 0, 16));
-    // the stream's last segment ends by the decode's rule (last_segment_end): its words
-    // and its start bit from the device copies, as gh_ctx_load_device reads them
-    uint32_t w5[5] = {};
-    GH_HIP(hipMemcpy(w5, c->d_payload + 4 * (c->nseg - 1), sizeof(w5), hipMemcpyDeviceToHost));  // (16 padding words follow)
-    uint32_t st = c->first_start;
-    if (c->nseg > 1) {
-      const uint64_t nib = c->gap_nib0 + c->nseg - 2;
-      uint32_t wv = 0;
-      GH_HIP(hipMemcpy(&wv, c->d_gaps + (nib >> 3), 4, hipMemcpyDeviceToHost));
-      st = (wv >> (4 * (nib & 7))) & 15u;
-    }
+    uint32_t last_end = 0;
+    if (int rc = loaded_last_end(c, &last_end)) return rc;
     IdxParams ip{};
     ip.w.payload = c->d_payload;
     ip.w.gaps = c->d_gaps;
@@ -1215,7 +1250,7 @@ extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, ui
     ip.w.first_start = c->first_start;
     ip.w.kbits = kc;
     ip.w.lut_bytes = (uint32_t)(4u << kc);
-    ip.w.last_end = last_segment_end(cn, w5, st);
+    ip.w.last_end = last_end;
     ip.w.fb = (const uint32_t*)d_fb.p;
     ip.w.fb_lo = std::max<uint32_t>(cn.minlen, 1);
     ip.w.fb_hi = std::max<uint32_t>(cn.maxlen, ip.w.fb_lo);
@@ -1277,6 +1312,149 @@ extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, ui
   put64(24, c->g_total);
   put64(32, nblocks + 1);
   if (symbols) *symbols = run;
+  if (kernel_ms) *kernel_ms = ms;
+  return GH_OK;
+}
+
+// ---- batched range gather (gh_gather.hip) -------------------------------------------
+// Not decode shapes either.  By the count table's width and the fallback, as
+// index_kernel_for.
+static const void* gather_kernel_for(uint32_t kc, bool fb) {
+  if (fb) return (const void*)gh_gather_kernel<GA_U, GA_TB, 2, true>;
+  const int gl = lookups_per_shift(kc);
+  return gl >= 4 ? (const void*)gh_gather_kernel<GA_U, GA_TB, 4, false>
+       : gl == 3 ? (const void*)gh_gather_kernel<GA_U, GA_TB, 3, false>
+                 : (const void*)gh_gather_kernel<GA_U, GA_TB, 2, false>;
+}
+
+// The gather's tables, built on the context's first gather after a load (free_shard drops
+// them): the count table of the index build (ws_count_bits), a single-symbol table of at
+// most 12 bits, the fallback tables and the end of the stream's last segment.
+static int gather_setup(gh_ctx* c) {
+  const Canon& cn = c->canon;
+  const uint32_t kc = ws_count_bits(cn);
+  const uint32_t ks = std::min<uint32_t>(std::max<uint32_t>(cn.maxlen, 2), 12);
+  const bool fb = kraft16(cn) != 65536 || cn.maxlen > std::min(kc, ks);
+  {
+    std::vector<uint32_t> lc;
+    count_lut(cn, kc, &lc);
+    const std::vector<uint32_t> ls = single_lut(cn, ks);
+    uint32_t fbt[FB_WORDS];
+    fallback_tables(cn, fbt);
+    GH_HIP(hipMalloc(&c->d_ga_lut_c, 4ull << kc));
+    GH_HIP(hipMemcpy(c->d_ga_lut_c, lc.data(), 4ull << kc, hipMemcpyHostToDevice));
+    GH_HIP(hipMalloc(&c->d_ga_lut_s, 4ull << ks));
+    GH_HIP(hipMemcpy(c->d_ga_lut_s, ls.data(), 4ull << ks, hipMemcpyHostToDevice));
+    GH_HIP(hipMalloc(&c->d_ga_fb, sizeof(fbt)));
+    GH_HIP(hipMemcpy(c->d_ga_fb, fbt, sizeof(fbt), hipMemcpyHostToDevice));
+  }
+  if (int rc = loaded_last_end(c, &c->ga_last_end)) return rc;
+  c->ga_kc = kc;
+  c->ga_ks = ks;
+  c->ga_fb = fb;
+  c->ga_kern = gather_kernel_for(kc, fb);
+  c->ga_lds = (4ull << kc) + (4ull << ks) + (fb ? FB_BYTES : 0);
+  if (c->ga_lds > 64 * 1024)
+    GH_HIP(hipFuncSetAttribute(c->ga_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->ga_lds));
+  int pc = 0;
+  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, c->ga_kern, GA_TB, c->ga_lds));
+  if (pc < 1) return fail(GH_E_HIP, "the gather kernel does not fit on a CU");
+  c->ga_wgs = (uint32_t)pc * (uint32_t)c->num_cu;
+  if (!c->ga_ev0) GH_HIP(hipEventCreate(&c->ga_ev0));
+  if (!c->ga_ev1) GH_HIP(hipEventCreate(&c->ga_ev1));
+  c->ga_ready = true;
+  return GH_OK;
+}
+
+extern "C" int gh_ctx_gather(gh_ctx* c, const gh_index* ix, const gh_range* ranges, uint32_t nranges,
+                             void* dst, uint64_t dst_len, void* hip_stream, float* kernel_ms) {
+  if (!c || !ix || !ix->offsets || (nranges && !ranges)) return fail(GH_E_ARG, "null argument");
+  if (kernel_ms) *kernel_ms = 0;
+  if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_gather before gh_ctx_load");
+  if (c->seg_begin != 0 || c->seg_end != c->g_total)
+    return fail(GH_E_ARG, "gh_ctx_gather: the load must cover segments [0, G)");
+  if (ix->n != c->n_total || ix->g != c->g_total) return fail(GH_E_ARG, "gh_ctx_gather: the index is another stream's (N, G)");
+  const uint64_t ibytes = gh_index_bytes(ix->g, ix->log2_stride);
+  if (ibytes == 0 || ix->nentries != (ibytes - 40) / 8) return fail(GH_E_ARG, "gh_ctx_gather: malformed index");
+  // plan into the context's piece vector (sized by a first pass)
+  uint64_t np = 0, total = 0;
+  int rc = gh_gather_plan(ix, ranges, nranges, c->ga_pieces.data(), c->ga_pieces.size(), &np, &total);
+  if (rc == GH_E_SMALL) {
+    c->ga_pieces.resize(np);
+    rc = gh_gather_plan(ix, ranges, nranges, c->ga_pieces.data(), c->ga_pieces.size(), &np, &total);
+  }
+  if (rc) return rc;
+  if (total > dst_len) return fail(GH_E_SMALL, "gather destination smaller than the ranges' bytes");
+  if (total == 0) return GH_OK;  // (no range, only empty ranges, or an empty stream)
+  if (!dst) return fail(GH_E_ARG, "null argument");
+  if (np >= (1ull << 31)) return fail(GH_E_ARG, "gh_ctx_gather: 2^31 or more pieces in one batch");
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  GH_HIP(hipSetDevice(c->device));
+  if (int rc2 = wait_decode(c)) return rc2;
+  if (!c->ga_ready)
+    if (int rc2 = gather_setup(c)) return rc2;
+  if (np > c->ga_pieces_cap) {
+    (void)hipFree(c->d_ga_pieces);
+    c->d_ga_pieces = nullptr;
+    c->ga_pieces_cap = 0;
+    GH_HIP(hipMalloc(&c->d_ga_pieces, np * sizeof(gh_gather_piece)));
+    c->ga_pieces_cap = np;
+  }
+  if (total > c->ga_out_cap) {
+    (void)hipFree(c->d_ga_out);
+    c->d_ga_out = nullptr;
+    c->ga_out_cap = 0;
+    GH_HIP(hipMalloc(&c->d_ga_out, total));
+    c->ga_out_cap = total;
+  }
+  GatherParams gp{};
+  gp.w.payload = c->d_payload;
+  gp.w.gaps = c->d_gaps;
+  gp.w.lut = (const uint2*)c->d_ga_lut_c;
+  gp.w.out = c->d_ga_out;
+  gp.w.status = c->d_misc + 16;  // (a word of its own: [1] is the decode's)
+  gp.w.nseg = (uint32_t)c->nseg;
+  gp.w.gap_nib0 = c->gap_nib0;
+  gp.w.first_start = c->first_start;
+  gp.w.kbits = c->ga_kc;
+  gp.w.lut_bytes = (uint32_t)(4u << c->ga_kc);
+  gp.w.last_end = c->ga_last_end;
+  gp.w.fb = c->d_ga_fb;
+  gp.w.fb_lo = std::max<uint32_t>(c->canon.minlen, 1);
+  gp.w.fb_hi = std::max<uint32_t>(c->canon.maxlen, gp.w.fb_lo);
+  gp.w.chk_pay = 4 * c->nseg + 16;
+  gp.w.chk_gap = c->nseg / 8 + 4;
+  gp.pieces = c->d_ga_pieces;
+  gp.sym_lut = c->d_ga_lut_s;
+  gp.npieces = (uint32_t)np;
+  gp.log2_stride = ix->log2_stride;
+  gp.sym_bits = c->ga_ks;
+  // every workgroup that has a piece, at most what the device holds at once
+  uint32_t grid = (uint32_t)std::min<uint64_t>(c->ga_wgs, ceil_div(np, (uint64_t)(GA_TB / 64)));
+  if (const char* eg = getenv("GH_GATHER_GRID"))  // tests: few workgroups, many pieces per wave
+    grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
+  void* args[1] = {&gp};
+  unsigned int status = 0;
+  float ms = 0;
+  {
+    // Joins the device's decode chain as gh_ctx_build_index does: the gather starts after
+    // the device's last tile decode, and the chain stays locked until it has finished.
+    DevChain& dc = dev_chain(c->device);
+    std::lock_guard<std::mutex> chain_lock(dc.mu);
+    if (dc.has) GH_HIP(hipStreamWaitEvent(st, dc.last, 0));
+    GH_HIP(hipMemsetAsync(c->d_misc + 16, 0, 4, st));
+    GH_HIP(hipMemcpyAsync(c->d_ga_pieces, c->ga_pieces.data(), np * sizeof(gh_gather_piece), hipMemcpyHostToDevice, st));
+    GH_HIP(hipEventRecord(c->ga_ev0, st));
+    GH_HIP(hipLaunchKernel(c->ga_kern, dim3(grid), dim3(GA_TB), args, c->ga_lds, st));
+    GH_HIP(hipGetLastError());
+    GH_HIP(hipEventRecord(c->ga_ev1, st));
+    GH_HIP(hipMemcpyAsync(dst, c->d_ga_out, total, hipMemcpyDefault, st));
+    GH_HIP(hipStreamSynchronize(st));
+  }
+  GH_HIP(hipEventElapsedTime(&ms, c->ga_ev0, c->ga_ev1));
+  GH_HIP(hipMemcpy(&status, c->d_misc + 16, 4, hipMemcpyDeviceToHost));
+  if (status & GH_ST_LAYOUT) return fail(GH_E_HIP, "gather kernel: LDS layout assumption violated");
+  if (status & GH_ST_BADCODE) return fail(GH_E_CORRUPT, "gather: invalid code in stream, or the index is another stream's");
   if (kernel_ms) *kernel_ms = ms;
   return GH_OK;
 }

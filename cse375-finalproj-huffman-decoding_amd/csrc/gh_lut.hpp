@@ -8,6 +8,7 @@
 //                                the Kc-bit window (bit e-1 of the mask per codeword
 //                                end e, b = their bits);
 //   wave split, write pass       u64 {up to four symbol bytes, b | n << 8};
+//   range gather, decode pass    u32 {len | sym << 8}, one codeword per lookup, any width;
 //   canonical fallback           FB_WORDS u32: running limit16[1..16], base16[1..16],
 //                                first[1..16], then the symbol bytes (file order) —
 //                                for codewords longer than a table and for patterns
@@ -95,6 +96,19 @@ inline std::vector<uint32_t> grouped_lut(const Canon& c, uint32_t K) {
     uint32_t fi = 0;
     const uint32_t l = canon_decode16(c, (i << (32 - K)) >> 16, &fi);
     t[i] = l | ((uint32_t)c.sym[fi] << 8) | (l << 23);
+  }
+  return t;
+}
+
+// Range-gather symbol LUT (gh_gather.hip) of any width K: entry i = {len | sym << 8} of
+// the codeword at the top of i, 0 when it is longer than K or outside the code (the
+// fallback decodes it; its result has the same layout).
+inline std::vector<uint32_t> single_lut(const Canon& c, uint32_t K) {
+  std::vector<uint32_t> t(std::max<uint32_t>(1u << K, 4), 0u);
+  for (uint32_t i = 0; i < (1u << K); ++i) {
+    uint32_t fi = 0;
+    const uint32_t l = canon_decode16(c, (i << (32 - K)) >> 16, &fi);
+    if (l != 0 && l <= K) t[i] = l | ((uint32_t)c.sym[fi] << 8);
   }
   return t;
 }

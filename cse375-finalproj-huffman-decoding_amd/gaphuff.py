@@ -50,6 +50,7 @@ EXPORTED = (
     "gh_ctx_load_file", "gh_ctx_save_file", "gh_dev_alloc", "gh_dev_free", "gh_dev_copy",
     "gh_raw_parse", "gh_bw_copy", "gh_ctx_kernel_shape", "gh_kernel_shapes",
     "gh_index_bytes", "gh_index_parse", "gh_index_locate", "gh_ctx_build_index",
+    "gh_gather_plan", "gh_ctx_gather",
 )
 
 
@@ -104,6 +105,15 @@ class gh_raw_stream(ctypes.Structure):
 class gh_index(ctypes.Structure):
     _fields_ = [("log2_stride", ctypes.c_uint32), ("n", ctypes.c_uint64), ("g", ctypes.c_uint64),
                 ("nentries", ctypes.c_uint64), ("offsets", ctypes.c_void_p)]
+
+
+class gh_range(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64)]
+
+
+class gh_gather_piece(ctypes.Structure):
+    _fields_ = [("dst", ctypes.c_uint64), ("block", ctypes.c_uint32), ("a", ctypes.c_uint32),
+                ("b", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
 class gh_sync_report(ctypes.Structure):
@@ -175,6 +185,8 @@ def lib() -> ctypes.CDLL:
             "gh_index_locate": ([ctypes.POINTER(gh_index), U64, U64, ctypes.POINTER(U64), ctypes.POINTER(U64),
                                  ctypes.POINTER(U64)], I),
             "gh_ctx_build_index": ([P, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_float)], I),
+            "gh_gather_plan": ([ctypes.POINTER(gh_index), P, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(U64)], I),
+            "gh_ctx_gather": ([P, ctypes.POINTER(gh_index), P, U32, P, U64, P, ctypes.POINTER(ctypes.c_float)], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -442,6 +454,24 @@ class Decoder:
                                         ctypes.byref(ms)))
         return img, int(symbols.value), float(ms.value)
 
+    def gather(self, index, ranges, dst_ptr: int = 0, dst_len: int = 0, hip_stream: int = 0):
+        """Bytes of the (lo, hi) ``ranges`` of the loaded stream (the load must cover all
+        its segments), concatenated in request order, in one launch (gh_ctx_gather):
+        (np.uint8 array, kernel ms).  With ``dst_ptr`` (a device or host address with room
+        for ``dst_len`` bytes) the bytes go there and the first item is their count."""
+        ix = index if isinstance(index, Index) else parse_index(index)
+        r = _ranges(ranges)
+        total = int((r[:, 1] - r[:, 0]).sum()) if r.size and (r[:, 1] >= r[:, 0]).all() else 0
+        ms = ctypes.c_float()
+        if dst_ptr:
+            out, dst, cap = None, ctypes.c_void_p(dst_ptr), dst_len
+        else:
+            out = np.empty(total, dtype=np.uint8)
+            dst, cap = _ptr(out), out.size
+        _check(lib().gh_ctx_gather(self._h, ctypes.byref(ix.c), _ptr(r), r.shape[0], dst, cap,
+                                   ctypes.c_void_p(hip_stream or None), ctypes.byref(ms)))
+        return (total if out is None else out), float(ms.value)
+
     def reset_timing(self) -> None:
         _check(lib().gh_ctx_reset_timing(self._h))
 
@@ -510,6 +540,32 @@ class Index:
                                      ctypes.byref(skip)))
         return int(b.value), int(e.value), int(skip.value)
 
+    def plan(self, ranges):
+        """The gather plan of the (lo, hi) ``ranges`` (gh_gather_plan): (pieces as a
+        structured array with fields dst, block, a, b, pad; the ranges' byte total)."""
+        r = _ranges(ranges)
+        np_, total = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib().gh_gather_plan(ctypes.byref(self.c), _ptr(r), r.shape[0], None, 0, ctypes.byref(np_),
+                                  ctypes.byref(total))
+        if rc not in (GH_OK, -9):
+            _check(rc)
+        pieces = np.zeros(int(np_.value), dtype=PIECE_DTYPE)
+        _check(lib().gh_gather_plan(ctypes.byref(self.c), _ptr(r), r.shape[0], _ptr(pieces), pieces.size,
+                                    ctypes.byref(np_), ctypes.byref(total)))
+        return pieces, int(total.value)
+
+
+# gh_gather_piece as a numpy record
+PIECE_DTYPE = np.dtype([("dst", "<u8"), ("block", "<u4"), ("a", "<u4"), ("b", "<u4"), ("pad", "<u4")])
+
+
+def _ranges(ranges) -> np.ndarray:
+    """(lo, hi) pairs as the C array of gh_range: a contiguous (n, 2) uint64 array."""
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+    if r.shape[0] >= 1 << 32:
+        raise GapHuffError(-1, "2^32 or more ranges in one batch")
+    return r
+
 
 def parse_index(image) -> Index:
     raw = _u8(image)
@@ -547,6 +603,22 @@ def decode_range(src, index, lo: int, hi: int, device: int = 0) -> np.ndarray:
         if rep.symbols < cap:  # never hand back undecoded (uninitialised) output bytes
             raise GapHuffError(-7, f"segments [{b}, {e}) decoded to {rep.symbols} of {cap} symbols")
         return d.download(hi - lo, offset=skip)
+
+
+def decode_ranges(src, index, ranges, device: int = 0) -> list:
+    """The bytes of each (lo, hi) range of the original data, as a list of arrays: the
+    whole stream is loaded once and every range decoded in one launch (Decoder.gather).
+    ``src`` and ``index`` as for :func:`decode_range`."""
+    ix = index if isinstance(index, Index) else parse_index(index)
+    r = _ranges(ranges)
+    with Decoder(device) as d:
+        if isinstance(src, (str, os.PathLike)):
+            d.load_file(os.fspath(src))
+        else:
+            d.load(src if isinstance(src, Stream) else parse(src))
+        out, _ = d.gather(ix, r)
+    ends = np.cumsum(r[:, 1] - r[:, 0]).astype(np.int64) if r.size else np.zeros(0, dtype=np.int64)
+    return [out[int(e - (h - l)): int(e)] for e, (l, h) in zip(ends, r)]
 
 
 def _syms(symbols: Sequence[tuple]):

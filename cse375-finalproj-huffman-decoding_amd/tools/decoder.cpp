@@ -1,5 +1,6 @@
 // bin/decoder <compressed.huff | raw container> <output> [--gpus N] [--shards S] [--reps R] [--json]
 //             [--verify FILE] [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]
+//             [--index FILE --ranges FILE]
 // --shards S (default: one per GPU) splits the gap segments into S shards, shard k on
 // device k mod N, each streaming its own payload range and writing at its offset.
 // A raw-stream container (bin/encoder --raw, GH_RAW_MAGIC) is decoded by the
@@ -8,6 +9,9 @@
 // the load, one entry per 2^K segments (--index-stride K, 8..20, default 8), and writes
 // the sidecar image.  --index FILE --range LO:HI decodes only the segments that hold
 // output bytes [LO, HI) and writes just those bytes to the output.
+// --index FILE --ranges FILE (a text file, one LO:HI per line) loads the whole stream once
+// and decodes every range in one launch (gh_ctx_gather); the output is their
+// concatenation in file order.
 //
 // Drop-in for the reference decoder CLI (Huffman_coding_Gap_arrays/decoder/src/
 // huff.cpp:22-142, used as `./bin/decoder in out` by run_huffman.sh:38), decoding on
@@ -60,11 +64,87 @@ static int die(const char* what, int rc) {
   return 1;
 }
 
+static bool read_file(const char* path, std::vector<uint8_t>& out) {
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return false;
+  std::fseek(f, 0, SEEK_END);
+  out.resize((size_t)std::max(std::ftell(f), 0L));
+  std::fseek(f, 0, SEEK_SET);
+  const bool ok = std::fread(out.data(), 1, out.size(), f) == out.size();
+  std::fclose(f);
+  return ok;
+}
+
+// --index FILE --ranges FILE: the whole stream loaded once, every range of the text file
+// (one LO:HI per line; blank lines skipped) decoded in one launch, the concatenation
+// written to `output`.
+static int gather_main(const char* input, const char* output, const char* index_file, const char* ranges_file) {
+  std::vector<uint8_t> ix_img, text;
+  gh_index ix{};
+  if (!read_file(index_file, ix_img)) { std::fprintf(stderr, "decoder: Could not open index file %s\n", index_file); return 1; }
+  int rc = gh_index_parse(ix_img.data(), ix_img.size(), &ix);
+  if (rc) return die("bad index", rc);
+  if (!read_file(ranges_file, text)) { std::fprintf(stderr, "decoder: Could not open ranges file %s\n", ranges_file); return 1; }
+  text.push_back(0);
+  std::vector<gh_range> ranges;
+  for (const char* p = (const char*)text.data(); *p;) {
+    while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') ++p;
+    if (!*p) break;
+    char* end = nullptr;
+    gh_range r{};
+    bool ok = *p >= '0' && *p <= '9';
+    if (ok) r.lo = std::strtoull(p, &end, 10);
+    ok = ok && *end == ':' && end[1] >= '0' && end[1] <= '9';
+    if (ok) {
+      p = end + 1;
+      r.hi = std::strtoull(p, &end, 10);
+      ok = *end == 0 || *end == ' ' || *end == '\t' || *end == '\r' || *end == '\n';
+    }
+    if (!ok || ranges.size() >= 0xFFFFFFFFull) {
+      std::fprintf(stderr, "decoder: %s: range %zu: expected LO:HI\n", ranges_file, ranges.size() + 1);
+      return 1;
+    }
+    ranges.push_back(r);
+    p = end;
+  }
+  uint64_t npieces = 0, total = 0;
+  rc = gh_gather_plan(&ix, ranges.data(), (uint32_t)ranges.size(), nullptr, 0, &npieces, &total);
+  if (rc && rc != GH_E_SMALL) return die("bad range", rc);
+  if (gh_device_count() < 1) return die("no HIP device", GH_E_NODEV);
+  gh_ctx* ctx = nullptr;
+  gh_file_info info{};
+  const double t0 = now_ms();
+  if ((rc = gh_ctx_create(0, &ctx))) return die("device init", rc);
+  if ((rc = gh_ctx_load_file(ctx, input, 0, UINT64_MAX, 0, &info))) { gh_ctx_destroy(ctx); return die("bad compressed stream / upload", rc); }
+  if (info.n != ix.n || info.g != ix.g) {
+    gh_ctx_destroy(ctx);
+    std::fprintf(stderr, "decoder: the index is for another stream (N or G differ)\n");
+    return 1;
+  }
+  std::vector<uint8_t> out((size_t)total);
+  float ms = 0;
+  const double t1 = now_ms();
+  rc = gh_ctx_gather(ctx, &ix, ranges.data(), (uint32_t)ranges.size(), out.data(), out.size(), nullptr, &ms);
+  const double t2 = now_ms();
+  gh_ctx_destroy(ctx);
+  if (rc) return die("gather", rc);
+  FILE* f = std::fopen(output, "wb");
+  bool okw = f && std::fwrite(out.data(), 1, out.size(), f) == out.size();
+  if (f) okw = std::fclose(f) == 0 && okw;
+  if (!okw) { std::fprintf(stderr, "decoder: cannot write %s\n", output); return 1; }
+  std::printf("Input file: %s\n", input);
+  std::printf("Original size: %llu bytes\n", (unsigned long long)info.n);
+  std::printf("Gather: %zu ranges, %llu pieces, %llu bytes; load %.3f ms, kernel %.3f ms, call %.3f ms\n", ranges.size(),
+              (unsigned long long)npieces, (unsigned long long)total, t1 - t0, ms, t2 - t1);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr,
                  "Usage: bin/decoder input output [--gpus N] [--shards S] [--reps R] [--json] [--verify FILE]\n"
-                 "       [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]\n");
+                 "       [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]\n"
+                 "       [--index FILE --ranges FILE]\n");
     return 2;
   }
   int ngpus = 1, reps = 1, nshards = 0;
@@ -73,6 +153,7 @@ int main(int argc, char** argv) {
   const char* write_index = nullptr;
   const char* index_file = nullptr;
   const char* range = nullptr;
+  const char* ranges_file = nullptr;
   int index_stride = GH_INDEX_MIN_LOG2;
   for (int i = 3; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) ngpus = std::atoi(argv[++i]);
@@ -84,6 +165,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--index-stride") && i + 1 < argc) index_stride = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--index") && i + 1 < argc) index_file = argv[++i];
     else if (!std::strcmp(argv[i], "--range") && i + 1 < argc) range = argv[++i];
+    else if (!std::strcmp(argv[i], "--ranges") && i + 1 < argc) ranges_file = argv[++i];
     else {
       std::fprintf(stderr, "decoder: unknown option %s\n", argv[i]);
       return 2;
@@ -91,6 +173,13 @@ int main(int argc, char** argv) {
   }
   if (ngpus < 1) ngpus = 1;
   if (reps < 1) reps = 1;
+  if (ranges_file) {
+    if (!index_file || range || write_index) {
+      std::fprintf(stderr, "decoder: --ranges FILE goes with --index FILE (and not with --range or --write-index)\n");
+      return 2;
+    }
+    return gather_main(argv[1], argv[2], index_file, ranges_file);
+  }
   // --index FILE --range LO:HI: the segments to load, from the sidecar alone
   const bool ranged = index_file || range;
   uint64_t lo = 0, hi = 0, rb = 0, re = 0, skip = 0;

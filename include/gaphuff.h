@@ -278,6 +278,34 @@ int gh_index_locate(const gh_index* ix, uint64_t lo, uint64_t hi, uint64_t* seg_
  * fewer than N codewords. */
 int gh_ctx_build_index(gh_ctx* ctx, uint32_t log2_stride, void* out, uint64_t out_len,
                        uint64_t* symbols, float* kernel_ms);
+/* Batched range gather: many byte ranges of a resident stream in one launch.  offsets[k]
+ * is the output position of index block k's first symbol, so a block decodes on its own;
+ * a batch is cut into pieces "decode index block k, keep the symbols at positions [a, b)
+ * of the block, store them at dst".  One wave owns a piece and walks the block's segments
+ * from its start, so gathers want a small stride: 2^8 .. 2^10 segments. */
+typedef struct gh_range { uint64_t lo, hi; } gh_range;            /* output bytes [lo, hi) */
+typedef struct gh_gather_piece {
+  uint64_t dst;      /* byte offset in the gathered output                          */
+  uint32_t block;    /* index block k: segments [k*stride, min((k+1)*stride, G))     */
+  uint32_t a, b;     /* keep symbols at positions [a, b) counted from offsets[k]     */
+  uint32_t pad;      /* 0 */
+} gh_gather_piece;
+/* Pieces for `nranges` ranges, in request order; range i's bytes start at
+ * sum_{j<i} (hi_j - lo_j) of the output.  Ranges may be empty, overlap, repeat and
+ * come in any order.  *npieces / *out_bytes are always written (so a first call with
+ * cap = 0 sizes the buffers; GH_E_SMALL then).  GH_E_ARG: lo > hi or hi > N.  No device. */
+int gh_gather_plan(const gh_index* ix, const gh_range* ranges, uint32_t nranges,
+                   gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces,
+                   uint64_t* out_bytes);
+/* Bytes of `nranges` ranges of the stream loaded in ctx (the load must cover [0, G)),
+ * concatenated in request order, into dst (device or host memory, dst_len >= their sum).
+ * Synchronous.  kernel_ms (may be NULL): HIP-event time of the gather kernel.  The tables
+ * are built on the context's first gather and kept until its next load.
+ * GH_E_STATE before a load; GH_E_ARG: load not covering [0, G), ix->n / ix->g differ
+ * from the stream's, a bad range; GH_E_SMALL: dst_len too small; GH_E_CORRUPT on a
+ * device status bit. */
+int gh_ctx_gather(gh_ctx* ctx, const gh_index* ix, const gh_range* ranges, uint32_t nranges,
+                  void* dst, uint64_t dst_len, void* hip_stream, float* kernel_ms);
 
 /* ---- self-synchronising decode of gap-less streams ---- */
 /* Replaces CUHD's decoder for raw Huffman streams without a gap array
