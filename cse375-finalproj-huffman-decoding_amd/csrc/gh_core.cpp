@@ -256,8 +256,9 @@ extern "C" int gh_stream_parse(const void* file, size_t len, gh_stream* out) {
 
 // ---------------------------------------------------------------------------
 // Seek index (sidecar image, gaphuff.h): parse and locate.  The image is built by
-// gh_ctx_build_index (gh_decode.hip).  Entries are read with memcpy: the image may sit
-// at any alignment.
+// gh_ctx_build_index (gh_decode.hip) from a loaded stream, and by the encoders:
+// gh_encode_index (below) and gh_ectx_index (gh_encode.hip).  Entries are read with
+// memcpy: the image may sit at any alignment.
 // ---------------------------------------------------------------------------
 constexpr size_t IDX_HEADER = 40;
 
@@ -527,6 +528,65 @@ extern "C" int gh_encode_write(const uint8_t* in, const gh_encode_plan* plan, in
   std::memcpy(out + off, gaps.data(), 4 * GW);
   off += 4 * GW;
   std::memcpy(out + off, words.data(), 4 * W);
+  return GH_OK;
+}
+
+// Header of a seek index image (gaphuff.h); returns its size in bytes.
+size_t gh::index_header(uint32_t log2_stride, uint64_t n, uint64_t g, uint64_t nentries, uint8_t* out) {
+  wr<uint64_t>(out, GH_INDEX_MAGIC);
+  wr<uint32_t>(out + 8, log2_stride);
+  wr<uint32_t>(out + 12, 0u);
+  wr<uint64_t>(out + 16, n);
+  wr<uint64_t>(out + 24, g);
+  wr<uint64_t>(out + 32, nentries);
+  return IDX_HEADER;
+}
+
+// The seek index of the stream gh_encode_write produces, from the input alone: the
+// encoder knows every codeword's first bit, so offsets[k] = the first i with start(i) >=
+// 128 * stride * k falls out of a walk over the code lengths.  Threaded as
+// gh_encode_write: per-thread bit totals, a scan, then thread t resolves the boundaries
+// inside its bit range [tbits[t], tbits[t + 1]); every boundary lies below the stream's
+// bit total (k * stride < G), so each has exactly one such thread.
+extern "C" int gh_encode_index(const uint8_t* in, const gh_encode_plan* plan, uint32_t log2_stride,
+                               int threads, void* out_v, uint64_t out_len) {
+  if (!plan || !out_v || (plan->n && !in)) return fail(GH_E_ARG, "null argument");
+  const uint64_t bytes = gh_index_bytes(plan->g, log2_stride);
+  if (bytes == 0) return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
+  if (out_len < bytes) return fail(GH_E_SMALL, "index buffer too small");
+  uint8_t* out = (uint8_t*)out_v;
+  const uint64_t n = plan->n;
+  const uint64_t S = (uint64_t)GH_SEGMENT_BITS << log2_stride;
+  const uint64_t nblocks = (bytes - IDX_HEADER) / 8 - 1;
+  const int nt = (int)std::min<uint64_t>(n_threads(threads), std::max<uint64_t>(1, n >> 20));
+  std::vector<uint64_t> tbits(nt + 1, 0);
+  parallel_for(nt, [&](int t) {
+    const uint64_t a = n * t / nt, b = n * (t + 1) / nt;
+    uint64_t s = 0;
+    for (uint64_t i = a; i < b; ++i) s += plan->len[in[i]];
+    tbits[t + 1] = s;
+  });
+  for (int t = 0; t < nt; ++t) tbits[t + 1] += tbits[t];
+  if (tbits[nt] != plan->bits || ceil_div(tbits[nt], GH_SEGMENT_BITS) != plan->g)
+    return fail(GH_E_ARG, "input does not match the plan");
+  uint8_t* ent = out + gh::index_header(log2_stride, n, plan->g, nblocks + 1, out);
+  parallel_for(nt, [&](int t) {
+    const uint64_t a = n * t / nt, b = n * (t + 1) / nt;
+    const uint64_t lo = tbits[t], hi = tbits[t + 1];
+    uint64_t k = ceil_div(lo, S);  // the first boundary at or past this thread's first bit
+    if (k >= nblocks || k * S >= hi) return;
+    uint64_t pos = lo;
+    for (uint64_t i = a; i < b; ++i) {
+      if (pos >= k * S) {  // (codewords are shorter than a stride: at most one boundary)
+        wr<uint64_t>(ent + 8 * k, i);
+        if (++k >= nblocks || k * S >= hi) return;
+      }
+      pos += plan->len[in[i]];
+    }
+    // boundaries inside the thread's last codeword: the next thread's first symbol
+    for (; k < nblocks && k * S < hi; ++k) wr<uint64_t>(ent + 8 * k, b);
+  });
+  wr<uint64_t>(ent + 8 * nblocks, n);
   return GH_OK;
 }
 

@@ -26,12 +26,16 @@
 //                        complete its last word.  Gap nibbles likewise in LDS; the two
 //                        edge gap words of a chunk (shared with its neighbours) are
 //                        atomicOr-ed into the zeroed gap array, the rest stored.
+//   gh_enc_index_kernel  (gh_ectx_index, after an encode) the seek index from the chunk
+//                        offsets: see the kernel.
 // Traffic: N (histogram, plan step) + 2N + C + gaps (encode) bytes.  A single pass
 // with a decoupled look-back (one 4 KiB chunk per workgroup) measured 2.85 ms on
 // cfg4, slower than these three kernels: its workgroups waited on their nearest
 // predecessors' aggregates.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -514,6 +518,78 @@ __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW
   }
 }
 
+// Seek index of the encoded stream (gaphuff.h, "random access"), from what the encode left
+// on the device: offsets[k] = the number of codewords that start before payload bit
+// B = S * k, S = 128 << log2_stride.  Chunk-centric, the write kernel's chunk geometry:
+// workgroup b takes chunks b, b + G, ...; chunk c covers bits [o0, o0 + chunk_bits[c]) and
+// owns the boundaries inside them.  A chunk that owns none is left before any input byte
+// is loaded (workgroup-uniform: at large strides almost every chunk).  Otherwise the
+// lanes' bits are block-scanned as in the write kernel, and the thread whose bits
+// [q0, q1) hold B counts its own symbols that start before B and stores the entry.  A
+// thread covers at most 256 bits and S >= 32768, so it owns at most one boundary; the
+// threads' ranges partition the stream's bits and every boundary lies below their total
+// (k * stride < G), so each entry has exactly one writer: no atomics, no zero-fill.
+struct EncIndexParams {
+  const uint8_t* in;
+  const uint32_t* lut;                 // 256 x {code << 8 | len}
+  const uint32_t* chunk_bits;          // code bits of each chunk
+  const uint32_t* chunk_loc;           // bit offset of each chunk within its scan block
+  const unsigned long long* blk_off;   // bit offset of each scan block
+  unsigned long long* offsets;         // nblocks entries
+  uint64_t n, nblocks;
+  uint32_t nchunks, log2_bits;         // S = 1 << log2_bits
+};
+
+__global__ __launch_bounds__(ETB) void gh_enc_index_kernel(const EncIndexParams p) {
+  __shared__ uint32_t s_lenr[256 * EBREP];
+  __shared__ uint32_t s_red[2][ETB / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  for (int i = tid; i < 256 * EBREP; i += ETB) s_lenr[i] = p.lut[i / EBREP] & 0xFFu;
+  const uint32_t* s_len = s_lenr + (lane & (EBREP - 1));  // entry b of this lane's copy: s_len[b * EBREP]
+  __syncthreads();
+  const uint32_t sh = p.log2_bits;
+  const unsigned long long smask = (1ull << sh) - 1ull;
+  uint32_t it = 0;  // chunks scanned so far (the wave sums are double-buffered)
+  for (uint32_t c = blockIdx.x; c < p.nchunks; c += gridDim.x) {
+    const unsigned long long o0 = p.blk_off[c / SCAN_BLK] + p.chunk_loc[c];
+    const unsigned long long end = o0 + p.chunk_bits[c];
+    if ((((o0 + smask) >> sh) << sh) >= end) continue;  // no boundary in [o0, end)
+    const uint64_t ib = (uint64_t)c * ECHUNK + (uint64_t)tid * EBPT;
+    // (in bounds: the input buffer is padded past n; bytes past n are masked by index)
+    const uint4 v = *(const uint4*)(p.in + ib);
+    uint32_t l[EBPT], bits = 0;
+    if (ib + EBPT <= p.n) {  // (divergent only in the last chunk)
+#pragma unroll
+      for (int k = 0; k < EBPT; ++k) l[k] = s_len[enc_byte(v, k) * EBREP];
+    } else {
+      const uint32_t rem = ib < p.n ? (uint32_t)(p.n - ib) : 0u;
+#pragma unroll
+      for (int k = 0; k < EBPT; ++k) l[k] = (uint32_t)k < rem ? s_len[enc_byte(v, k) * EBREP] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < EBPT; ++k) bits += l[k];
+    const uint32_t incl = enc_wave_scan(bits);
+    if (lane == 63) s_red[it & 1][wid] = incl;
+    __syncthreads();  // (one barrier per scanned chunk: the other buffer is the previous chunk's)
+    uint32_t before = 0;
+#pragma unroll
+    for (int q = 0; q < ETB / 64; ++q) before += q < wid ? s_red[it & 1][q] : 0u;
+    ++it;
+    const unsigned long long q0 = o0 + before + (incl - bits), q1 = q0 + bits;
+    const unsigned long long k = (q0 + smask) >> sh, B = k << sh;  // the first boundary at or past q0
+    if (B < q1 && k < p.nblocks) {
+      uint32_t pos = 0, cnt = 0;  // bits before each symbol, relative to q0
+      const uint32_t rel = (uint32_t)(B - q0);
+#pragma unroll
+      for (int j = 0; j < EBPT; ++j) {
+        cnt += pos < rel ? 1u : 0u;
+        pos += l[j];
+      }
+      p.offsets[k] = ib + cnt;
+    }
+  }
+}
+
 }  // namespace gh
 
 using namespace gh;
@@ -541,6 +617,10 @@ struct gh_ectx {
   uint32_t* d_junk = nullptr;              // write kernel padding stores: one dword per thread
   uint64_t junk_cap = 0;
   uint64_t words_cap = 0, gaps_cap = 0;
+  const uint32_t* d_loc = nullptr;             // the last encode's chunk offsets: views into d_chunk_off
+  const unsigned long long* d_blk = nullptr;
+  unsigned long long* d_index = nullptr;       // gh_ectx_index: the entries
+  uint64_t index_cap = 0;
   gh_encode_plan plan{};
   bool planned = false, encoded = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -575,7 +655,7 @@ extern "C" int gh_ectx_destroy(gh_ectx* e) {
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   for (void* p : {(void*)e->d_in, (void*)e->d_count, (void*)e->d_lut, (void*)e->d_chunk_bits,
-                  (void*)e->d_chunk_off, (void*)e->d_words, (void*)e->d_gaps, (void*)e->d_junk})
+                  (void*)e->d_chunk_off, (void*)e->d_words, (void*)e->d_gaps, (void*)e->d_junk, (void*)e->d_index})
     (void)hipFree(p);
   if (e->ev0) (void)hipEventDestroy(e->ev0);
   if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -702,6 +782,8 @@ extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
       GH_EHIP(hipMalloc(&e->d_junk, 4ull * gw * ETB));
       e->junk_cap = (uint64_t)gw * ETB;
     }
+    e->d_loc = loc;
+    e->d_blk = blk;
     EncParams p{e->d_in, e->d_lut, loc, blk, e->d_words, e->d_gaps, e->d_junk, e->n, (uint32_t)nchunks, ew, eg};
     void* args[] = {&p};
     GH_EHIP(hipLaunchKernel(wk, dim3(gw), dim3(ETB), args, dyn, e->stream));
@@ -726,5 +808,46 @@ extern "C" int gh_ectx_download(gh_ectx* e, void* out, uint64_t out_len) {
   if (GW) GH_EHIP(hipMemcpyAsync(o + hdr, e->d_gaps, 4 * GW, hipMemcpyDeviceToHost, e->stream));
   if (pl.w) GH_EHIP(hipMemcpyAsync(o + hdr + 4 * GW, e->d_words, 4 * pl.w, hipMemcpyDeviceToHost, e->stream));
   GH_EHIP(hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+// The index kernel reads the input, the code lengths, the chunk bits and the two-level
+// chunk offsets of the last encode; nothing of the encode's output.
+extern "C" int gh_ectx_index(gh_ectx* e, uint32_t log2_stride, void* out, uint64_t out_len, float* kernel_ms) {
+  if (!e || !out) return fail(GH_E_ARG, "null argument");
+  if (!e->encoded) return fail(GH_E_STATE, "gh_ectx_index before gh_ectx_encode");
+  const gh_encode_plan& pl = e->plan;
+  const uint64_t bytes = gh_index_bytes(pl.g, log2_stride);
+  if (bytes == 0) return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
+  if (out_len < bytes) return fail(GH_E_SMALL, "index buffer too small");
+  GH_EHIP(hipSetDevice(e->device));
+  uint8_t* o = (uint8_t*)out;
+  const uint64_t nblocks = (bytes - 40) / 8 - 1;
+  const uint64_t nchunks = ceil_div(e->n, ECHUNK);
+  if (nblocks > e->index_cap) {
+    (void)hipFree(e->d_index);
+    e->d_index = nullptr;
+    e->index_cap = 0;
+    GH_EHIP(hipMalloc(&e->d_index, 8 * nblocks));
+    e->index_cap = nblocks;
+  }
+  GH_EHIP(hipEventRecord(e->ev0, e->stream));
+  if (nblocks) {  // (then N > 0: the encode ran its kernels)
+    int pc = 0;
+    GH_EHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, (const void*)gh_enc_index_kernel, ETB, 0));
+    uint32_t grid = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pc, 1) * e->num_cu);
+    if (const char* eg = getenv("GH_ENC_INDEX_GRID"))  // tests: few workgroups, many chunks each
+      grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
+    const EncIndexParams p{e->d_in, e->d_lut, e->d_chunk_bits, e->d_loc, e->d_blk, e->d_index, e->n, nblocks,
+                           (uint32_t)nchunks, 7u + log2_stride};
+    hipLaunchKernelGGL(gh_enc_index_kernel, dim3(grid), dim3(ETB), 0, e->stream, p);
+    GH_EHIP(hipGetLastError());
+  }
+  GH_EHIP(hipEventRecord(e->ev1, e->stream));
+  if (nblocks) GH_EHIP(hipMemcpyAsync(o + 40, e->d_index, 8 * nblocks, hipMemcpyDeviceToHost, e->stream));
+  GH_EHIP(hipStreamSynchronize(e->stream));
+  if (kernel_ms) GH_EHIP(hipEventElapsedTime(kernel_ms, e->ev0, e->ev1));
+  index_header(log2_stride, pl.n, pl.g, nblocks + 1, o);
+  std::memcpy(o + 40 + 8 * nblocks, &pl.n, 8);
   return GH_OK;
 }

@@ -53,6 +53,8 @@ inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 int plan_from_counts(gh_encode_plan* plan, int force_version);
 // Writes the image header; returns its size.  out must hold file_bytes - payload.
 size_t encode_header(const gh_encode_plan* plan, uint8_t* out);
+// Writes a seek index image's header (40 bytes, any alignment); returns its size.
+size_t index_header(uint32_t log2_stride, uint64_t n, uint64_t g, uint64_t nentries, uint8_t* out);
 
 // Host memory <-> device memory through the device's pinned staging buffers
 // (gh_io.cpp): each 32 MiB chunk is copied to / from a pinned buffer by a few host

@@ -50,7 +50,7 @@ EXPORTED = (
     "gh_ctx_load_file", "gh_ctx_save_file", "gh_dev_alloc", "gh_dev_free", "gh_dev_copy",
     "gh_raw_parse", "gh_bw_copy", "gh_ctx_kernel_shape", "gh_kernel_shapes",
     "gh_index_bytes", "gh_index_parse", "gh_index_locate", "gh_ctx_build_index",
-    "gh_gather_plan", "gh_ctx_gather",
+    "gh_gather_plan", "gh_ctx_gather", "gh_encode_index", "gh_ectx_index",
 )
 
 
@@ -187,6 +187,8 @@ def lib() -> ctypes.CDLL:
             "gh_ctx_build_index": ([P, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_float)], I),
             "gh_gather_plan": ([ctypes.POINTER(gh_index), P, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(U64)], I),
             "gh_ctx_gather": ([P, ctypes.POINTER(gh_index), P, U32, P, U64, P, ctypes.POINTER(ctypes.c_float)], I),
+            "gh_encode_index": ([P, ctypes.POINTER(gh_encode_plan), U32, I, P, U64], I),
+            "gh_ectx_index": ([P, U32, P, U64, ctypes.POINTER(ctypes.c_float)], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -267,6 +269,19 @@ def encode(data, threads: int = 0, force_version: int = 0) -> np.ndarray:
     return out
 
 
+def encode_index(data, log2_stride: int = 8, threads: int = 0, force_version: int = 0) -> np.ndarray:
+    """Seek index (sidecar image, np.uint8) of the stream ``encode(data)`` produces, from
+    the data alone (gh_encode_index): no decode, no device."""
+    d = _u8(data)
+    plan = encode_plan(d, threads, force_version)
+    nbytes = int(lib().gh_index_bytes(plan.g, log2_stride))
+    if nbytes == 0:
+        raise GapHuffError(-1, "index stride outside 2^8 .. 2^20 segments")
+    img = np.zeros(nbytes, dtype=np.uint8)
+    _check(lib().gh_encode_index(_ptr(d), ctypes.byref(plan), log2_stride, threads, _ptr(img), img.size))
+    return img
+
+
 class Encoder:
     """One gh_ectx: the GPU encoder on one gfx950 device.
 
@@ -318,6 +333,18 @@ class Encoder:
         out = np.empty(self.plan.file_bytes, dtype=np.uint8)
         _check(lib().gh_ectx_download(self._h, _ptr(out), out.size))
         return out
+
+    def index(self, log2_stride: int = 8):
+        """Seek index of the encoded stream, built on the device from what the encode left
+        there (gh_ectx_index): (sidecar image as np.uint8, kernel ms)."""
+        g = self.plan.g if self.plan is not None else 0
+        nbytes = int(lib().gh_index_bytes(g, log2_stride))
+        if nbytes == 0:
+            raise GapHuffError(-1, "index stride outside 2^8 .. 2^20 segments")
+        img = np.zeros(nbytes, dtype=np.uint8)
+        ms = ctypes.c_float()
+        _check(lib().gh_ectx_index(self._h, log2_stride, _ptr(img), img.size, ctypes.byref(ms)))
+        return img, float(ms.value)
 
 
 def encode_gpu(data, device: int = 0, force_version: int = 0) -> np.ndarray:

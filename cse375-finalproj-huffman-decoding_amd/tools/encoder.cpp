@@ -1,11 +1,15 @@
 // bin/encoder <input> <compressed.huff> [--threads T] [--v2] [--gpu [DEVICE]] [--raw]
+//             [--write-index FILE [--index-stride K]]
 //
 // Drop-in for the reference encoder CLI (Huffman_coding_Gap_arrays/encoder/src/
 // huff.cpp:30-220): same positional arguments, same output format (v1 header when
 // the sizes fit the reference's 32-bit fields, the 64-bit v2 header otherwise), and
 // the same stdout lines (:176-181).  Encoding runs on the host through the gaphuff C
 // ABI, or with --gpu on a gfx950 device (gh_ectx_*, byte-identical output; the
-// reference's own encoder is a GPU one, encoder.cu:382-457).
+// reference's own encoder is a GPU one, encoder.cu:382-457).  --write-index also writes
+// the stream's seek index (gaphuff.h "random access"; K = log2 of the stride in segments,
+// default 8) from the encoder itself: gh_encode_index on the host, gh_ectx_index with
+// --gpu; the same index with --raw (G is the same).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -26,10 +30,14 @@ int main(int argc, char** argv) {
   }
   int threads = 0, force = 0, gpu = -1;
   bool raw = false;  // write the gap-less raw-stream container (GH_RAW_MAGIC) instead
+  const char* index_path = nullptr;
+  uint32_t index_k = 8;
   for (int i = 3; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--threads") && i + 1 < argc) threads = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--v2")) force = 2;
     else if (!std::strcmp(argv[i], "--raw")) raw = true;
+    else if (!std::strcmp(argv[i], "--write-index") && i + 1 < argc) index_path = argv[++i];
+    else if (!std::strcmp(argv[i], "--index-stride") && i + 1 < argc) index_k = (uint32_t)std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--gpu")) gpu = (i + 1 < argc && argv[i + 1][0] != '-') ? std::atoi(argv[++i]) : 0;
     else {
       std::fprintf(stderr, "encoder: unknown option %s\n", argv[i]);
@@ -52,7 +60,7 @@ int main(int argc, char** argv) {
   }
   std::fclose(f);
   gh_encode_plan* plan = new gh_encode_plan;
-  std::vector<uint8_t> out;
+  std::vector<uint8_t> out, index;
   double t0, t1, t2;
   int rc;
   if (gpu >= 0) {
@@ -68,6 +76,10 @@ int main(int argc, char** argv) {
     if (!rc) {
       out.resize(plan->file_bytes);
       rc = gh_ectx_download(e, out.data(), out.size());
+    }
+    if (!rc && index_path) {  // (a bad stride: size 0, and the library's refusal)
+      index.resize(std::max<uint64_t>(gh_index_bytes(plan->g, index_k), 1));
+      rc = gh_ectx_index(e, index_k, index.data(), index.size(), nullptr);
     }
     if (rc) {
       std::fprintf(stderr, "encoder: %s\n", gh_last_error());
@@ -89,6 +101,14 @@ int main(int argc, char** argv) {
       return 1;
     }
     t2 = now_ms();
+    if (index_path) {  // (a bad stride: size 0, and the library's refusal)
+      index.resize(std::max<uint64_t>(gh_index_bytes(plan->g, index_k), 1));
+      rc = gh_encode_index(in.data(), plan, index_k, threads, index.data(), index.size());
+      if (rc) {
+        std::fprintf(stderr, "encoder: %s\n", gh_last_error());
+        return 1;
+      }
+    }
   }
   if (raw) {  // same code and payload words, no gap array
     gh_stream st;
@@ -123,6 +143,19 @@ int main(int argc, char** argv) {
     return 1;
   }
   std::fclose(o);
+  if (index_path) {
+    FILE* x = std::fopen(index_path, "wb");
+    if (!x) {
+      std::fprintf(stderr, "Could not open index file\n");
+      return 1;
+    }
+    if (std::fwrite(index.data(), 1, index.size(), x) != index.size()) {
+      std::fclose(x);
+      std::fprintf(stderr, "write error\n");
+      return 1;
+    }
+    std::fclose(x);
+  }
   std::printf("Input file: %s\n", argv[1]);
   std::printf("Original size: %llu bytes\n", (unsigned long long)plan->n);
   std::printf("Compressed size: %llu bytes\n", (unsigned long long)(plan->w * 4));
@@ -130,6 +163,9 @@ int main(int argc, char** argv) {
   std::printf("Total encode time: %.3f ms\n", t2 - t0);
   std::printf("Throughput: %.2f MB/s\n",
               (double)plan->n / (1024.0 * 1024.0) / std::max(1e-9, (t2 - t0) / 1000.0));
+  if (index_path)
+    std::printf("Index: %llu entries, stride 2^%u, %llu bytes\n", (unsigned long long)((index.size() - 40) / 8),
+                index_k, (unsigned long long)index.size());
   delete plan;
   return 0;
 }

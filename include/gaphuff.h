@@ -278,6 +278,26 @@ int gh_index_locate(const gh_index* ix, uint64_t lo, uint64_t hi, uint64_t* seg_
  * fewer than N codewords. */
 int gh_ctx_build_index(gh_ctx* ctx, uint32_t log2_stride, void* out, uint64_t out_len,
                        uint64_t* symbols, float* kernel_ms);
+/* The same image from the encoders, which know every codeword's first bit before they
+ * write a word: no decode, no decode tables, no gh_ctx.  offsets[k] is the number of i
+ * with start(i) < 128 * stride * k, start(i) the exclusive prefix sum of
+ * plan->len[in[i]].
+ * Host: the sidecar image (gh_index_bytes(plan->g, log2_stride) bytes) of the stream that
+ * gh_encode_write(in, plan, ...) produces, into out.  Threaded like gh_encode_write; the
+ * image does not depend on `threads`.  No device.  GH_E_ARG: null pointers, a stride
+ * outside the range, an input whose bit total differs from plan->bits; GH_E_SMALL:
+ * out_len too small. */
+int gh_encode_index(const uint8_t* in, const gh_encode_plan* plan, uint32_t log2_stride,
+                    int threads, void* out, uint64_t out_len);
+/* GPU: the sidecar image of the stream the context's last gh_ectx_encode produced, from
+ * what that encode left on the device (input, code lengths, chunk bit offsets): one
+ * kernel that reads only the input chunks holding an index boundary, then one copy of the
+ * entries to out.  May be called repeatedly, with different strides, after one encode;
+ * the encoded image (gh_ectx_download) is untouched.  Synchronous, on the context's
+ * stream.  kernel_ms (may be NULL): HIP-event time of the index kernel alone.
+ * GH_E_STATE before gh_ectx_encode or after a later gh_ectx_load / gh_ectx_plan;
+ * GH_E_ARG: null pointers, a stride outside the range; GH_E_SMALL: out_len too small. */
+int gh_ectx_index(gh_ectx* ctx, uint32_t log2_stride, void* out, uint64_t out_len, float* kernel_ms);
 /* Batched range gather: many byte ranges of a resident stream in one launch.  offsets[k]
  * is the output position of index block k's first symbol, so a block decodes on its own;
  * a batch is cut into pieces "decode index block k, keep the symbols at positions [a, b)
