@@ -468,32 +468,75 @@ size_t gh::encode_header(const gh_encode_plan* plan, uint8_t* out) {
   return off;
 }
 
-extern "C" int gh_encode_write(const uint8_t* in, const gh_encode_plan* plan, int threads,
-                               void* out_v, uint64_t out_len) {
-  if (!plan || !out_v || (plan->n && !in)) return fail(GH_E_ARG, "null argument");
-  if (out_len < plan->file_bytes) return fail(GH_E_SMALL, "output buffer too small");
-  uint8_t* out = (uint8_t*)out_v;
-  const uint64_t n = plan->n, W = plan->w, G = plan->g;
-  const uint64_t GW = ceil_div(G, GH_GAPS_PER_WORD);
-  size_t off = gh::encode_header(plan, out);
-  std::vector<uint32_t> gaps(GW + 1, 0), words(W + 1, 0);
+extern "C" int gh_encode_plan_from_counts(const uint64_t counts[256], int force_version, gh_encode_plan* plan) {
+  if (!counts || !plan) return fail(GH_E_ARG, "null argument");
+  std::memset(plan, 0, sizeof(*plan));
+  for (int v = 0; v < 256; ++v) {
+    plan->count[v] = counts[v];
+    plan->n += counts[v];
+  }
+  return gh::plan_from_counts(plan, force_version);
+}
+
+extern "C" uint64_t gh_encode_bound(uint64_t n) {
+  // 16 bits per byte: W = ceil(n / 2) words, G = ceil(n / 8) segments; v2 header, 256 symbols
+  const uint64_t w = ceil_div(n, 2), g = ceil_div(n, 8);
+  return 16 + 2ull * GH_MAX_SYMBOLS + 24 + 4 * ceil_div(g, GH_GAPS_PER_WORD) + 4 * w;
+}
+
+extern "C" int gh_slice_extent(uint64_t base_bit, uint64_t bits, gh_slice* out) {
+  if (!out) return fail(GH_E_ARG, "null argument");
+  if (base_bit + bits < base_bit) return fail(GH_E_ARG, "slice end overflows 64 bits");
+  out->base_bit = base_bit;
+  out->bits = bits;
+  out->word0 = base_bit >> 5;
+  out->gapw0 = base_bit >> 10;
+  out->nwords = bits ? ((base_bit + bits - 1) >> 5) + 1 - out->word0 : 0;
+  out->ngapw = bits ? ((base_bit + bits - 1) >> 10) + 1 - out->gapw0 : 0;
+  return GH_OK;
+}
+
+// The host encoder's body: bytes in[0..n) as the slice at base_bit (gaphuff.h, "sliced
+// encode"); the whole stream is the slice at bit 0.  Threaded: per-thread bit totals, an
+// exclusive scan, then every thread packs its own bits; the words and gap words that two
+// threads (or two slices) share are ORed.  words / gaps are indexed from the slice's
+// word0 / gapw0; `zeroed`: the caller has cleared them.
+static int encode_slice_body(const uint8_t* in, uint64_t n, const gh_encode_plan* plan, uint64_t base_bit,
+                             int threads, uint32_t* words, uint64_t words_cap, uint32_t* gaps, uint64_t gaps_cap,
+                             bool zeroed, gh_slice* out) {
   const int nt = (int)std::min<uint64_t>(n_threads(threads), std::max<uint64_t>(1, n >> 20));
   // per-thread bit totals -> exclusive bit offsets
   std::vector<uint64_t> tbits(nt + 1, 0);
+  std::atomic<bool> absent{false};
   parallel_for(nt, [&](int t) {
     const uint64_t a = n * t / nt, b = n * (t + 1) / nt;
     uint64_t s = 0;
-    for (uint64_t i = a; i < b; ++i) s += plan->len[in[i]];
+    bool zero = false;
+    for (uint64_t i = a; i < b; ++i) {
+      const uint32_t l = plan->len[in[i]];
+      zero |= l == 0;
+      s += l;
+    }
     tbits[t + 1] = s;
+    if (zero) absent = true;
   });
+  if (absent) return fail(GH_E_TABLE, "a byte of the input has no code in the plan");
   for (int t = 0; t < nt; ++t) tbits[t + 1] += tbits[t];
-  if (tbits[nt] != plan->bits) return fail(GH_E_ARG, "input does not match the plan");
+  if (gh_slice_extent(base_bit, tbits[nt], out) || base_bit + tbits[nt] > plan->bits)
+    return fail(GH_E_ARG, "slice ends past the plan's bit total");
+  if (words_cap < out->nwords || gaps_cap < out->ngapw) return fail(GH_E_SMALL, "slice buffer too small");
+  if (!zeroed) {
+    if (out->nwords) std::memset(words, 0, 4 * out->nwords);
+    if (out->ngapw) std::memset(gaps, 0, 4 * out->ngapw);
+  }
+  const uint64_t word0 = out->word0, gapw0 = out->gapw0;
   parallel_for(nt, [&](int t) {
     const uint64_t a = n * t / nt, b = n * (t + 1) / nt;
-    uint64_t pos = tbits[t];
+    if (a == b) return;  // (an empty slice owns no word)
+    uint64_t pos = base_bit + tbits[t];
     uint64_t acc = 0;
     int nb = (int)(pos & 31);  // placeholder zero bits already in the first word
-    uint64_t widx = pos >> 5;
+    uint64_t widx = (pos >> 5) - word0;
     const uint64_t first_word = widx;
     auto emit = [&](uint32_t v) {
       if (widx == first_word) {
@@ -510,7 +553,7 @@ extern "C" int gh_encode_write(const uint8_t* in, const gh_encode_plan* plan, in
       if ((end >> 7) != (pos >> 7)) {  // codeword crosses a 128-bit boundary
         const uint32_t gv = (uint32_t)(end & 15);
         const uint64_t j = pos >> 7;
-        if (gv) __atomic_fetch_or(&gaps[j >> 3], gv << (4 * (j & 7)), __ATOMIC_RELAXED);
+        if (gv) __atomic_fetch_or(&gaps[(j >> 3) - gapw0], gv << (4 * (j & 7)), __ATOMIC_RELAXED);
       }
       acc = (acc << l) | plan->code[sym];
       nb += (int)l;
@@ -525,9 +568,68 @@ extern "C" int gh_encode_write(const uint8_t* in, const gh_encode_plan* plan, in
       __atomic_fetch_or(&words[widx], (uint32_t)(acc << (32 - nb)), __ATOMIC_RELAXED);
     }
   });
+  return GH_OK;
+}
+
+extern "C" int gh_encode_slice(const uint8_t* in, uint64_t n, const gh_encode_plan* plan, uint64_t base_bit,
+                               int threads, uint32_t* words, uint64_t words_cap, uint32_t* gapw,
+                               uint64_t gaps_cap, gh_slice* out) {
+  if (!plan || !out || (n && !in) || (words_cap && !words) || (gaps_cap && !gapw))
+    return fail(GH_E_ARG, "null argument");
+  return encode_slice_body(in, n, plan, base_bit, threads, words, words_cap, gapw, gaps_cap, false, out);
+}
+
+extern "C" int gh_encode_write(const uint8_t* in, const gh_encode_plan* plan, int threads,
+                               void* out_v, uint64_t out_len) {
+  if (!plan || !out_v || (plan->n && !in)) return fail(GH_E_ARG, "null argument");
+  if (out_len < plan->file_bytes) return fail(GH_E_SMALL, "output buffer too small");
+  uint8_t* out = (uint8_t*)out_v;
+  const uint64_t W = plan->w;
+  const uint64_t GW = ceil_div(plan->g, GH_GAPS_PER_WORD);
+  size_t off = gh::encode_header(plan, out);
+  // the whole stream is the slice at bit 0
+  std::vector<uint32_t> gaps(GW + 1, 0), words(W + 1, 0);
+  gh_slice sl;
+  const int rc = encode_slice_body(in, plan->n, plan, 0, threads, words.data(), W, gaps.data(), GW, true, &sl);
+  if (rc || sl.bits != plan->bits) return fail(GH_E_ARG, "input does not match the plan");
   std::memcpy(out + off, gaps.data(), 4 * GW);
   off += 4 * GW;
   std::memcpy(out + off, words.data(), 4 * W);
+  return GH_OK;
+}
+
+// Bytes of the image before the gap words.
+static uint64_t image_header_bytes(const gh_encode_plan* plan) {
+  return (plan->version == 2 ? 16 : 8) + 2ull * plan->nsyms + (plan->version == 2 ? 24 : 12);
+}
+
+extern "C" int gh_encode_image_init(const gh_encode_plan* plan, void* image, uint64_t image_len) {
+  if (!plan || !image) return fail(GH_E_ARG, "null argument");
+  const uint64_t hdr = image_header_bytes(plan), body = 4 * ceil_div(plan->g, GH_GAPS_PER_WORD) + 4 * plan->w;
+  if (plan->nsyms > GH_MAX_SYMBOLS || plan->file_bytes != hdr + body) return fail(GH_E_ARG, "inconsistent plan");
+  if (image_len < plan->file_bytes) return fail(GH_E_SMALL, "image buffer too small");
+  uint8_t* o = (uint8_t*)image;
+  const size_t off = gh::encode_header(plan, o);
+  std::memset(o + off, 0, body);
+  return GH_OK;
+}
+
+// Bytewise OR: the image's word area has no alignment, and OR does not care about the
+// byte order inside a word.
+extern "C" int gh_slice_merge(void* image, uint64_t image_len, const gh_encode_plan* plan, const gh_slice* s,
+                              const uint32_t* words, const uint32_t* gapw) {
+  if (!image || !plan || !s || (s->nwords && !words) || (s->ngapw && !gapw)) return fail(GH_E_ARG, "null argument");
+  const uint64_t GW = ceil_div(plan->g, GH_GAPS_PER_WORD), hdr = image_header_bytes(plan);
+  if (plan->file_bytes != hdr + 4 * GW + 4 * plan->w) return fail(GH_E_ARG, "inconsistent plan");
+  if (s->word0 > plan->w || s->nwords > plan->w - s->word0 || s->gapw0 > GW || s->ngapw > GW - s->gapw0)
+    return fail(GH_E_ARG, "slice extents outside the stream");
+  if (image_len < plan->file_bytes) return fail(GH_E_SMALL, "image buffer too small");
+  uint8_t* g = (uint8_t*)image + hdr + 4 * s->gapw0;
+  uint8_t* w = (uint8_t*)image + hdr + 4 * GW + 4 * s->word0;
+  const uint8_t* sg = (const uint8_t*)gapw;
+  const uint8_t* sw = (const uint8_t*)words;
+  for (uint64_t i = 0; i < 4 * s->ngapw; ++i) g[i] |= sg[i];
+  for (uint64_t i = 0; i < 4 * s->nwords; ++i) w[i] |= sw[i];
   return GH_OK;
 }
 

@@ -28,6 +28,9 @@
 //                        atomicOr-ed into the zeroed gap array, the rest stored.
 //   gh_enc_index_kernel  (gh_ectx_index, after an encode) the seek index from the chunk
 //                        offsets: see the kernel.
+// Sliced encode (gh_ectx_encode_slice): the same kernels on an input that is one slice of
+// a longer stream; the block scan starts at the slice's first stream bit and the write
+// kernel's SLICE variant indexes its outputs from the slice's origin.
 // Traffic: N (histogram, plan step) + 2N + C + gaps (encode) bytes.  A single pass
 // with a decoupled look-back (one 4 KiB chunk per workgroup) measured 2.85 ms on
 // cfg4, slower than these three kernels: its workgroups waited on their nearest
@@ -37,6 +40,9 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "gaphuff.h"
@@ -256,10 +262,13 @@ __global__ __launch_bounds__(SCAN_TB) void gh_enc_scan_kernel(const uint32_t* ch
     if (i0 + k < nchunks) chunk_loc[i0 + k] = b0 + v[k];
   if (tid == 0) blk_tot[blockIdx.x] = tot;
 }
-__global__ __launch_bounds__(SCAN_TB) void gh_enc_blkscan_kernel(unsigned long long* blk, uint32_t nblk) {
+// carry0: the stream bit the input starts at (a slice's base_bit; 0 for a whole stream), so
+// every chunk offset is a stream bit position.
+__global__ __launch_bounds__(SCAN_TB) void gh_enc_blkscan_kernel(unsigned long long* blk, uint32_t nblk,
+                                                                 unsigned long long carry0) {
   __shared__ unsigned long long s[SCAN_TB];
   const int tid = threadIdx.x;
-  unsigned long long carry = 0;
+  unsigned long long carry = carry0;
   for (uint32_t base = 0; base < nblk; base += SCAN_TB) {
     const uint32_t i = base + (uint32_t)tid;
     const unsigned long long x = i < nblk ? blk[i] : 0ull;
@@ -288,6 +297,7 @@ struct EncParams {
   uint64_t n;
   uint32_t nchunks;
   uint32_t ewords, egapw;  // LDS image words (payload, gaps): (1024 + ECHUNK x maxlen + 64) / 32 + 2, (1024 + ECHUNK x maxlen) / 1024 + 2
+  unsigned long long org;  // slice variant: the stream bit of words[0] and gaps[0], base_bit & ~1023
 };
 
 // Write-kernel LUT replicas (lane l reads copy l mod ELREP): 16 copies collide at most
@@ -324,7 +334,13 @@ __device__ __forceinline__ uint32_t enc_pair(uint32_t a, uint32_t c, uint32_t& l
 // stores share one in-order counter (vmcnt), and with a fixed count of stores younger
 // than the prefetch the next chunk waits for its loads with vmcnt(N) instead of also
 // waiting for this chunk's stores.
-template <int NSW>
+// SLICE: the input is a slice of a longer stream (gaphuff.h, "sliced encode").  The block
+// scan starts at the slice's base_bit, so o0, B, qs, the boundaries and the gap nibbles
+// are the stream's own; what differs is the origin of the outputs (p.org, the gap word
+// holding base_bit: B never lies before it) and the slice's first word: chunk 0 also
+// owns the word holding base_bit, whose leading bits (the previous slice's) stay zero in
+// the image.  The last word needs nothing: the completion lanes are masked by p.n.
+template <int NSW, bool SLICE>
 __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW>()))) void gh_enc_write_kernel(
     const EncParams p) {
   constexpr int ELREP = enc_lrep<NSW>();
@@ -470,14 +486,15 @@ __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW
     __syncthreads();
     // payload words whose first bit lies in [o0, o0 + cbits): local [w0, w1); the
     // image is zeroed as it is read (up to the completion word)
-    const uint32_t w0 = (qs + 31u) >> 5, w1 = (qend + 31u) >> 5;
-    uint32_t* wout = p.words + (B >> 5);
+    const uint32_t w0 = (SLICE && c == 0) ? qs >> 5 : (qs + 31u) >> 5, w1 = (qend + 31u) >> 5;
+    const unsigned long long org = SLICE ? p.org : 0ull;  // (B >= org: both multiples of 1024)
+    uint32_t* wout = p.words + ((B - org) >> 5);
     uint32_t* junk = p.junk + (size_t)blockIdx.x * ETB + tid;
     // (GH_ENC_OOB) buffer stores from the chunk's base (B is workgroup-uniform), the
     // padding ones out of range: dropped, no memory traffic
     const unsigned long long Bu = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(B >> 32)) << 32) |
                                   (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)B);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(p.words + (Bu >> 5), 0, 0x7FFFFFF0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(p.words + ((Bu - org) >> 5), 0, 0x7FFFFFF0, 0x00020000);
 #pragma unroll
     for (int j = 0; j < NSW; ++j) {
       const uint32_t i = (uint32_t)tid + (uint32_t)(ETB * j);
@@ -500,7 +517,7 @@ __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW
     // gap words of this chunk's segments: local [0, g1]; the first and the last may
     // hold nibbles of the neighbouring chunks
     const uint32_t g1 = cbits ? (qend - 1u) >> 10 : 0u;
-    uint32_t* gout = p.gaps + (B >> 10);
+    uint32_t* gout = p.gaps + ((B - org) >> 10);
     static_assert(EGAPW <= ETB, "one gap word per thread");
     {
       const uint32_t i = (uint32_t)tid;
@@ -508,7 +525,7 @@ __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW
       if (i <= g1) s_g[i] = 0;
       const bool in = cbits && i <= g1, edge = i == 0 || i == g1;
       if (GH_ENC_OOB) {  // interior: a plain store (always issued)
-        const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(p.gaps + (Bu >> 10), 0, 0x7FFFFFF0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(p.gaps + ((Bu - org) >> 10), 0, 0x7FFFFFF0, 0x00020000);
         __builtin_amdgcn_raw_buffer_store_b32(x, rg, (in && !edge) ? (int)(4u * i) : 0x7FFFFFF0, 0, 0);
       } else {
         *((in && !edge) ? gout + i : junk) = x;
@@ -623,6 +640,10 @@ struct gh_ectx {
   uint64_t index_cap = 0;
   gh_encode_plan plan{};
   bool planned = false, encoded = false;
+  uint64_t counts[256] = {};                   // histogram of the loaded input, when `counted`
+  bool counted = false;
+  bool sliced = false;                         // the last encode was a slice encode: `slice`
+  gh_slice slice{};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -679,13 +700,12 @@ extern "C" int gh_ectx_load(gh_ectx* e, const uint8_t* in, uint64_t n) {
   if (n) GH_EHIP(hipMemcpyAsync(e->d_in, in, n, hipMemcpyHostToDevice, e->stream));
   GH_EHIP(hipStreamSynchronize(e->stream));
   e->n = n;
-  e->planned = e->encoded = false;
+  e->planned = e->encoded = e->counted = e->sliced = false;
   return GH_OK;
 }
 
-extern "C" int gh_ectx_plan(gh_ectx* e, int force_version, gh_encode_plan* plan) {
-  if (!e) return fail(GH_E_ARG, "null ctx");
-  GH_EHIP(hipSetDevice(e->device));
+// Byte histogram of the loaded input into e->counts (synchronous).
+static int ectx_hist(gh_ectx* e) {
   GH_EHIP(hipMemsetAsync(e->d_count, 0, 256 * 8, e->stream));
   const uint64_t nchunks = ceil_div(e->n, ECHUNK);
   if (nchunks) {
@@ -693,30 +713,64 @@ extern "C" int gh_ectx_plan(gh_ectx* e, int force_version, gh_encode_plan* plan)
     hipLaunchKernelGGL(gh_enc_hist_kernel, dim3(grid), dim3(ETB), 0, e->stream, e->d_in, e->n, e->d_count);
     GH_EHIP(hipGetLastError());
   }
+  GH_EHIP(hipMemcpyAsync(e->counts, e->d_count, 256 * 8, hipMemcpyDeviceToHost, e->stream));
+  GH_EHIP(hipStreamSynchronize(e->stream));
+  e->counted = true;
+  return GH_OK;
+}
+
+extern "C" int gh_ectx_plan(gh_ectx* e, int force_version, gh_encode_plan* plan) {
+  if (!e) return fail(GH_E_ARG, "null ctx");
+  GH_EHIP(hipSetDevice(e->device));
+  e->planned = e->encoded = e->sliced = false;
+  int rc = ectx_hist(e);
+  if (rc) return rc;
   gh_encode_plan& pl = e->plan;
   std::memset(&pl, 0, sizeof(pl));
   pl.n = e->n;
-  GH_EHIP(hipMemcpyAsync(pl.count, e->d_count, 256 * 8, hipMemcpyDeviceToHost, e->stream));
-  GH_EHIP(hipStreamSynchronize(e->stream));
-  const int rc = plan_from_counts(&pl, force_version);
+  std::memcpy(pl.count, e->counts, sizeof(pl.count));
+  rc = plan_from_counts(&pl, force_version);
   if (rc) return rc;
   e->planned = true;
-  e->encoded = false;
   if (plan) *plan = pl;
   return GH_OK;
 }
 
-extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
-  if (!e) return fail(GH_E_ARG, "null ctx");
-  if (!e->planned) return fail(GH_E_STATE, "gh_ectx_encode before gh_ectx_plan");
+extern "C" int gh_ectx_counts(gh_ectx* e, uint64_t counts[256]) {
+  if (!e || !counts) return fail(GH_E_ARG, "null argument");
   GH_EHIP(hipSetDevice(e->device));
-  const gh_encode_plan& pl = e->plan;
+  e->planned = e->encoded = e->sliced = false;
+  const int rc = ectx_hist(e);
+  if (rc) return rc;
+  std::memcpy(counts, e->counts, sizeof(e->counts));
+  return GH_OK;
+}
+
+template <bool SLICE>
+static const void* enc_write_kernel(int need) {
+  return need <= 1   ? (const void*)gh_enc_write_kernel<1, SLICE>
+         : need <= 2 ? (const void*)gh_enc_write_kernel<2, SLICE>
+         : need <= 3 ? (const void*)gh_enc_write_kernel<3, SLICE>
+         : need <= 4 ? (const void*)gh_enc_write_kernel<4, SLICE>
+         : need <= 5 ? (const void*)gh_enc_write_kernel<5, SLICE>
+         : need <= 6 ? (const void*)gh_enc_write_kernel<6, SLICE>
+                     : (const void*)gh_enc_write_kernel<9, SLICE>;
+}
+
+// The device encode of the loaded input under pl, as code bits [base_bit, base_bit + bits)
+// of pl's stream: the whole stream (slice = false, base_bit 0, bits = pl.bits) or a slice
+// of it.  d_words[0] / d_gaps[0] are the payload / gap word holding stream bit
+// org = base_bit & ~1023 (a whole stream: words 0).
+static int ectx_encode_run(gh_ectx* e, const gh_encode_plan& pl, bool slice, uint64_t base_bit, uint64_t bits,
+                           float* kernel_ms) {
   for (int v = 0; v < 256; ++v)
     if (pl.len[v] > GH_MAX_CODE_LEN) return fail(GH_E_TABLE, "code longer than 16 bits");
   uint32_t lut[256];
   for (int v = 0; v < 256; ++v) lut[v] = (pl.code[v] << 8) | pl.len[v];
   const uint64_t nchunks = ceil_div(e->n, ECHUNK);
-  const uint64_t GW = ceil_div(pl.g, GH_GAPS_PER_WORD);
+  const uint64_t org = base_bit & ~1023ull, end = base_bit + bits;
+  const uint64_t NW = ceil_div(end, 32) - (org >> 5);    // a whole stream: pl.w
+  const uint64_t GW = ceil_div(end, 1024) - (org >> 10);  // a whole stream: ceil(pl.g / 8)
   if (nchunks + 1 > e->chunk_cap) {
     (void)hipFree(e->d_chunk_bits);
     (void)hipFree(e->d_chunk_off);
@@ -727,12 +781,12 @@ extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
     GH_EHIP(hipMalloc(&e->d_chunk_off, 4 * (nchunks + 1) + 8 * (nchunks / SCAN_BLK + 2) + 64));
     e->chunk_cap = nchunks + 1;
   }
-  if (pl.w + 4 > e->words_cap) {
+  if (NW + 4 > e->words_cap) {
     (void)hipFree(e->d_words);
     e->d_words = nullptr;
     e->words_cap = 0;
-    GH_EHIP(hipMalloc(&e->d_words, 4 * (pl.w + 4)));
-    e->words_cap = pl.w + 4;
+    GH_EHIP(hipMalloc(&e->d_words, 4 * (NW + 4)));
+    e->words_cap = NW + 4;
   }
   if (GW + 4 > e->gaps_cap) {
     (void)hipFree(e->d_gaps);
@@ -747,15 +801,9 @@ extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
   GH_EHIP(hipMemsetAsync(e->d_gaps, 0, 4 * (GW + 4), e->stream));
   if (nchunks) {
     // payload words per chunk ~ 4096 * W / n: NSW = store instructions per thread
-    const double wpc = (double)ECHUNK * (double)pl.w / (double)std::max<uint64_t>(e->n, 1) + 2.0;
+    const double wpc = (double)ECHUNK * (double)ceil_div(bits, 32) / (double)std::max<uint64_t>(e->n, 1) + 2.0;
     const int need = (int)std::ceil(wpc * 1.05 / ETB);
-    const void* wk = need <= 1   ? (const void*)gh_enc_write_kernel<1>
-                     : need <= 2 ? (const void*)gh_enc_write_kernel<2>
-                     : need <= 3 ? (const void*)gh_enc_write_kernel<3>
-                     : need <= 4 ? (const void*)gh_enc_write_kernel<4>
-                     : need <= 5 ? (const void*)gh_enc_write_kernel<5>
-                     : need <= 6 ? (const void*)gh_enc_write_kernel<6>
-                                 : (const void*)gh_enc_write_kernel<9>;
+    const void* wk = slice ? enc_write_kernel<true>(need) : enc_write_kernel<false>(need);
     // the LDS image holds a chunk at the code's longest codeword
     uint32_t maxlen = 1;
     for (int v = 0; v < 256; ++v) maxlen = std::max<uint32_t>(maxlen, pl.len[v]);
@@ -773,7 +821,8 @@ extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
     unsigned long long* blk = e->d_chunk_off + (nchunks + 2) / 2 + 1;  // after the local offsets
     hipLaunchKernelGGL(gh_enc_scan_kernel, dim3(nblk), dim3(SCAN_TB), 0, e->stream, e->d_chunk_bits,
                        (uint32_t)nchunks, loc, blk);
-    hipLaunchKernelGGL(gh_enc_blkscan_kernel, dim3(1), dim3(SCAN_TB), 0, e->stream, blk, nblk);
+    hipLaunchKernelGGL(gh_enc_blkscan_kernel, dim3(1), dim3(SCAN_TB), 0, e->stream, blk, nblk,
+                       (unsigned long long)base_bit);
     const uint32_t gw = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pw, 1) * e->num_cu);
     if ((uint64_t)gw * ETB > e->junk_cap) {
       (void)hipFree(e->d_junk);
@@ -784,7 +833,8 @@ extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
     }
     e->d_loc = loc;
     e->d_blk = blk;
-    EncParams p{e->d_in, e->d_lut, loc, blk, e->d_words, e->d_gaps, e->d_junk, e->n, (uint32_t)nchunks, ew, eg};
+    EncParams p{e->d_in, e->d_lut, loc, blk, e->d_words, e->d_gaps, e->d_junk, e->n, (uint32_t)nchunks, ew, eg,
+                org};
     void* args[] = {&p};
     GH_EHIP(hipLaunchKernel(wk, dim3(gw), dim3(ETB), args, dyn, e->stream));
     GH_EHIP(hipGetLastError());
@@ -792,7 +842,58 @@ extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
   GH_EHIP(hipEventRecord(e->ev1, e->stream));
   GH_EHIP(hipStreamSynchronize(e->stream));
   if (kernel_ms) GH_EHIP(hipEventElapsedTime(kernel_ms, e->ev0, e->ev1));
+  return GH_OK;
+}
+
+extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
+  if (!e) return fail(GH_E_ARG, "null ctx");
+  if (!e->planned) return fail(GH_E_STATE, "gh_ectx_encode before gh_ectx_plan");
+  GH_EHIP(hipSetDevice(e->device));
+  e->encoded = e->sliced = false;
+  const int rc = ectx_encode_run(e, e->plan, false, 0, e->plan.bits, kernel_ms);
+  if (rc) return rc;
   e->encoded = true;
+  return GH_OK;
+}
+
+extern "C" int gh_ectx_encode_slice(gh_ectx* e, const gh_encode_plan* sp, uint64_t base_bit, gh_slice* out,
+                                    float* kernel_ms) {
+  if (!e || !sp) return fail(GH_E_ARG, "null argument");
+  GH_EHIP(hipSetDevice(e->device));
+  e->encoded = e->sliced = false;  // (the buffers of an earlier encode are reused)
+  if (!e->counted) {
+    const int rc = ectx_hist(e);
+    if (rc) return rc;
+  }
+  uint64_t bits = 0;
+  for (int v = 0; v < 256; ++v) {
+    if (e->counts[v] && sp->len[v] == 0) return fail(GH_E_TABLE, "a byte of the input has no code in the plan");
+    bits += e->counts[v] * sp->len[v];
+  }
+  gh_slice sl;
+  if (gh_slice_extent(base_bit, bits, &sl) || base_bit + bits > sp->bits)
+    return fail(GH_E_ARG, "slice ends past the plan's bit total");
+  const int rc = ectx_encode_run(e, *sp, true, base_bit, bits, kernel_ms);
+  if (rc) return rc;
+  e->slice = sl;
+  e->sliced = true;
+  if (out) *out = sl;
+  return GH_OK;
+}
+
+extern "C" int gh_ectx_download_slice(gh_ectx* e, uint32_t* words, uint64_t words_cap, uint32_t* gapw,
+                                      uint64_t gaps_cap) {
+  if (!e) return fail(GH_E_ARG, "null ctx");
+  if (!e->sliced) return fail(GH_E_STATE, "gh_ectx_download_slice: the last encode was not a slice encode");
+  const gh_slice& sl = e->slice;
+  if (words_cap < sl.nwords || gaps_cap < sl.ngapw) return fail(GH_E_SMALL, "slice buffer too small");
+  if ((sl.nwords && !words) || (sl.ngapw && !gapw)) return fail(GH_E_ARG, "null argument");
+  GH_EHIP(hipSetDevice(e->device));
+  // the device buffers start at the gap word holding base_bit: up to 31 words before word0
+  const uint64_t lead = sl.word0 - ((sl.base_bit & ~1023ull) >> 5);
+  if (sl.ngapw) GH_EHIP(hipMemcpyAsync(gapw, e->d_gaps, 4 * sl.ngapw, hipMemcpyDeviceToHost, e->stream));
+  if (sl.nwords) GH_EHIP(hipMemcpyAsync(words, e->d_words + lead, 4 * sl.nwords, hipMemcpyDeviceToHost, e->stream));
+  GH_EHIP(hipStreamSynchronize(e->stream));
   return GH_OK;
 }
 
@@ -850,4 +951,105 @@ extern "C" int gh_ectx_index(gh_ectx* e, uint32_t log2_stride, void* out, uint64
   index_header(log2_stride, pl.n, pl.g, nblocks + 1, o);
   std::memcpy(o + 40 + 8 * nblocks, &pl.n, 8);
   return GH_OK;
+}
+
+// One-shot sliced encode (gaphuff.h).  Slice i: bytes [n i / K, n (i + 1) / K) on device
+// devs[i % ng], in a gh_ectx of its own; a host thread per distinct device takes that
+// device's slices in turn.  Two passes with the stream-wide plan between them: the first
+// loads the slices and takes their histograms, the second encodes every slice at its
+// scanned bit offset and downloads it.  The merge runs on the calling thread, in slice
+// order (neighbouring slices share their edge words).
+extern "C" int gh_encode_sharded(const uint8_t* in, uint64_t n, const gh_opts* o, uint32_t nslices,
+                                 int force_version, void* out, uint64_t out_len, gh_encode_plan* plan_out,
+                                 float* kernel_ms) {
+  if ((n && !in) || !out || nslices == 0) return fail(GH_E_ARG, "null argument or no slices");
+  const int ng = (o && o->ngpus > 1) ? o->ngpus : 1;
+  const uint32_t K = nslices;
+  std::vector<int> dev(K);
+  for (uint32_t i = 0; i < K; ++i) dev[i] = (o && o->devices) ? o->devices[i % ng] : (ng > 1 ? (int)(i % ng) : 0);
+  std::vector<int> devs(dev);  // the distinct devices: one host thread each
+  std::sort(devs.begin(), devs.end());
+  devs.erase(std::unique(devs.begin(), devs.end()), devs.end());
+  const int nd = (int)devs.size();
+  std::vector<gh_ectx*> ctx(K, nullptr);
+  auto cleanup = [&]() {
+    for (auto*& c : ctx) {
+      gh_ectx_destroy(c);
+      c = nullptr;
+    }
+  };
+  // f(i) for every slice i, the slices of one device in turn on that device's thread
+  auto per_device = [&](auto f) {
+    std::vector<int> rc(nd, GH_OK);
+    std::vector<std::string> msg(nd);
+    auto run = [&](int d) {
+      for (uint32_t i = 0; i < K && !rc[d]; ++i)
+        if (dev[i] == devs[d] && (rc[d] = f(i))) msg[d] = gh_last_error();
+    };
+    if (nd == 1) {
+      run(0);
+    } else {
+      std::vector<std::thread> th;
+      for (int d = 0; d < nd; ++d) th.emplace_back(run, d);
+      for (auto& t : th) t.join();
+    }
+    for (int d = 0; d < nd; ++d)
+      if (rc[d]) {
+        set_error(msg[d]);
+        return rc[d];
+      }
+    return (int)GH_OK;
+  };
+  auto cut = [&](uint32_t i) { return (uint64_t)((unsigned __int128)n * i / K); };
+  std::vector<uint64_t> counts((size_t)K * 256, 0);
+  int rc = per_device([&](uint32_t i) {
+    int r = gh_ectx_create(dev[i], &ctx[i]);
+    if (!r) r = gh_ectx_load(ctx[i], in + cut(i), cut(i + 1) - cut(i));
+    if (!r) r = gh_ectx_counts(ctx[i], &counts[(size_t)i * 256]);
+    return r;
+  });
+  gh_encode_plan* plan = new gh_encode_plan;
+  std::vector<uint64_t> base(K + 1, 0);
+  if (!rc) {
+    uint64_t sum[256] = {};
+    for (uint32_t i = 0; i < K; ++i)
+      for (int v = 0; v < 256; ++v) sum[v] += counts[(size_t)i * 256 + v];
+    rc = gh_encode_plan_from_counts(sum, force_version, plan);
+  }
+  if (!rc) {
+    if (plan_out) *plan_out = *plan;
+    if (out_len < plan->file_bytes) rc = fail(GH_E_SMALL, "output buffer too small");
+  }
+  std::vector<gh_slice> sl(K);
+  std::vector<std::vector<uint32_t>> words(K), gapw(K);
+  std::vector<float> ms(K, 0.f);
+  if (!rc) {
+    for (uint32_t i = 0; i < K; ++i) {  // the slices' bit totals, scanned
+      uint64_t b = 0;
+      for (int v = 0; v < 256; ++v) b += counts[(size_t)i * 256 + v] * plan->len[v];
+      base[i + 1] = base[i] + b;
+    }
+    rc = per_device([&](uint32_t i) {
+      int r = gh_ectx_encode_slice(ctx[i], plan, base[i], &sl[i], &ms[i]);
+      if (!r) {
+        words[i].resize(sl[i].nwords);
+        gapw[i].resize(sl[i].ngapw);
+        r = gh_ectx_download_slice(ctx[i], words[i].data(), words[i].size(), gapw[i].data(), gapw[i].size());
+      }
+      gh_ectx_destroy(ctx[i]);  // (this device's memory goes back before its next slice)
+      ctx[i] = nullptr;
+      return r;
+    });
+  }
+  cleanup();
+  if (!rc) rc = gh_encode_image_init(plan, out, out_len);
+  for (uint32_t i = 0; i < K && !rc; ++i) rc = gh_slice_merge(out, out_len, plan, &sl[i], words[i].data(), gapw[i].data());
+  if (!rc && kernel_ms) {
+    std::map<int, float> per_dev;
+    for (uint32_t i = 0; i < K; ++i) per_dev[dev[i]] += ms[i];
+    *kernel_ms = 0.f;
+    for (auto& d : per_dev) *kernel_ms = std::max(*kernel_ms, d.second);
+  }
+  delete plan;
+  return rc;
 }

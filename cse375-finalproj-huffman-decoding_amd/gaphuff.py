@@ -51,6 +51,9 @@ EXPORTED = (
     "gh_raw_parse", "gh_bw_copy", "gh_ctx_kernel_shape", "gh_kernel_shapes",
     "gh_index_bytes", "gh_index_parse", "gh_index_locate", "gh_ctx_build_index",
     "gh_gather_plan", "gh_ctx_gather", "gh_encode_index", "gh_ectx_index",
+    "gh_encode_plan_from_counts", "gh_encode_bound", "gh_slice_extent", "gh_encode_slice",
+    "gh_encode_image_init", "gh_slice_merge", "gh_ectx_counts", "gh_ectx_encode_slice",
+    "gh_ectx_download_slice", "gh_encode_sharded",
 )
 
 
@@ -79,6 +82,11 @@ class gh_encode_plan(ctypes.Structure):
         ("version", ctypes.c_uint32), ("syms", gh_sym * 256), ("code", ctypes.c_uint32 * 256),
         ("len", ctypes.c_uint8 * 256), ("count", ctypes.c_uint64 * 256),
     ]
+
+
+class gh_slice(ctypes.Structure):
+    _fields_ = [("base_bit", ctypes.c_uint64), ("bits", ctypes.c_uint64), ("word0", ctypes.c_uint64),
+                ("nwords", ctypes.c_uint64), ("gapw0", ctypes.c_uint64), ("ngapw", ctypes.c_uint64)]
 
 
 class gh_report(ctypes.Structure):
@@ -189,6 +197,19 @@ def lib() -> ctypes.CDLL:
             "gh_ctx_gather": ([P, ctypes.POINTER(gh_index), P, U32, P, U64, P, ctypes.POINTER(ctypes.c_float)], I),
             "gh_encode_index": ([P, ctypes.POINTER(gh_encode_plan), U32, I, P, U64], I),
             "gh_ectx_index": ([P, U32, P, U64, ctypes.POINTER(ctypes.c_float)], I),
+            "gh_encode_plan_from_counts": ([P, I, ctypes.POINTER(gh_encode_plan)], I),
+            "gh_encode_bound": ([U64], U64),
+            "gh_slice_extent": ([U64, U64, ctypes.POINTER(gh_slice)], I),
+            "gh_encode_slice": ([P, U64, ctypes.POINTER(gh_encode_plan), U64, I, P, U64, P, U64,
+                                 ctypes.POINTER(gh_slice)], I),
+            "gh_encode_image_init": ([ctypes.POINTER(gh_encode_plan), P, U64], I),
+            "gh_slice_merge": ([P, U64, ctypes.POINTER(gh_encode_plan), ctypes.POINTER(gh_slice), P, P], I),
+            "gh_ectx_counts": ([P, P], I),
+            "gh_ectx_encode_slice": ([P, ctypes.POINTER(gh_encode_plan), U64, ctypes.POINTER(gh_slice),
+                                      ctypes.POINTER(ctypes.c_float)], I),
+            "gh_ectx_download_slice": ([P, P, U64, P, U64], I),
+            "gh_encode_sharded": ([P, U64, ctypes.POINTER(gh_opts), U32, I, P, U64, ctypes.POINTER(gh_encode_plan),
+                                   ctypes.POINTER(ctypes.c_float)], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -282,6 +303,54 @@ def encode_index(data, log2_stride: int = 8, threads: int = 0, force_version: in
     return img
 
 
+# ---- sliced encode (include/gaphuff.h, "sliced encode") ----
+def plan_from_counts(counts, force_version: int = 0) -> gh_encode_plan:
+    """The stream-wide plan from a 256-entry histogram (e.g. the sum of the slices')."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    if c.size != 256:
+        raise GapHuffError(-1, "a histogram has 256 counts")
+    plan = gh_encode_plan()
+    _check(lib().gh_encode_plan_from_counts(_ptr(c), force_version, ctypes.byref(plan)))
+    return plan
+
+
+def slice_extent(base_bit: int, bits: int) -> gh_slice:
+    s = gh_slice()
+    _check(lib().gh_slice_extent(base_bit, bits, ctypes.byref(s)))
+    return s
+
+
+def encode_slice(data, plan: gh_encode_plan, base_bit: int, threads: int = 0):
+    """Host encoder of one slice of the stream planned by ``plan``: ``data`` as the code
+    bits from ``base_bit`` on.  Returns (gh_slice, words, gapw): the slice-local payload
+    and gap words (np.uint32), indexed from slice.word0 / slice.gapw0."""
+    d = _u8(data)
+    s = gh_slice()
+    rc = lib().gh_encode_slice(_ptr(d), d.size, ctypes.byref(plan), base_bit, threads, None, 0, None, 0,
+                               ctypes.byref(s))
+    if rc not in (GH_OK, -9):
+        _check(rc)
+    words = np.zeros(int(s.nwords), dtype=np.uint32)
+    gapw = np.zeros(int(s.ngapw), dtype=np.uint32)
+    _check(lib().gh_encode_slice(_ptr(d), d.size, ctypes.byref(plan), base_bit, threads, _ptr(words), words.size,
+                                 _ptr(gapw), gapw.size, ctypes.byref(s)))
+    return s, words, gapw
+
+
+def merge_slices(plan: gh_encode_plan, parts) -> np.ndarray:
+    """The compressed.huff image (np.uint8) of the (gh_slice, words, gapw) ``parts``, in
+    any order (gh_encode_image_init + gh_slice_merge, one after the other)."""
+    img = np.empty(plan.file_bytes, dtype=np.uint8)
+    _check(lib().gh_encode_image_init(ctypes.byref(plan), _ptr(img), img.size))
+    for s, words, gapw in parts:
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        g = np.ascontiguousarray(gapw, dtype=np.uint32)
+        if w.size < s.nwords or g.size < s.ngapw:
+            raise GapHuffError(-1, "slice buffers shorter than the slice's extents")
+        _check(lib().gh_slice_merge(_ptr(img), img.size, ctypes.byref(plan), ctypes.byref(s), _ptr(w), _ptr(g)))
+    return img
+
+
 class Encoder:
     """One gh_ectx: the GPU encoder on one gfx950 device.
 
@@ -293,6 +362,7 @@ class Encoder:
         self._h = ctypes.c_void_p()
         _check(lib().gh_ectx_create(device, ctypes.byref(self._h)))
         self.plan: Optional[gh_encode_plan] = None
+        self._slice: Optional[gh_slice] = None  # extents of the last slice encode
 
     def close(self) -> None:
         if self._h:
@@ -334,6 +404,30 @@ class Encoder:
         _check(lib().gh_ectx_download(self._h, _ptr(out), out.size))
         return out
 
+    def counts(self) -> np.ndarray:
+        """GPU histogram of the loaded input (256 x np.uint64); makes no plan."""
+        c = np.zeros(256, dtype=np.uint64)
+        _check(lib().gh_ectx_counts(self._h, _ptr(c)))
+        self.plan = None
+        return c
+
+    def encode_slice(self, plan: gh_encode_plan, base_bit: int):
+        """Encode the loaded input as the slice at ``base_bit`` of the stream planned by
+        ``plan`` (gh_ectx_encode_slice): (gh_slice, kernel ms)."""
+        s = gh_slice()
+        ms = ctypes.c_float()
+        _check(lib().gh_ectx_encode_slice(self._h, ctypes.byref(plan), base_bit, ctypes.byref(s), ctypes.byref(ms)))
+        self._slice = s
+        return s, float(ms.value)
+
+    def download_slice(self):
+        """(words, gapw) of the last slice encode, laid out as :func:`encode_slice`'s."""
+        s = self._slice or gh_slice()
+        words = np.zeros(int(s.nwords), dtype=np.uint32)
+        gapw = np.zeros(int(s.ngapw), dtype=np.uint32)
+        _check(lib().gh_ectx_download_slice(self._h, _ptr(words), words.size, _ptr(gapw), gapw.size))
+        return words, gapw
+
     def index(self, log2_stride: int = 8):
         """Seek index of the encoded stream, built on the device from what the encode left
         there (gh_ectx_index): (sidecar image as np.uint8, kernel ms)."""
@@ -354,6 +448,28 @@ def encode_gpu(data, device: int = 0, force_version: int = 0) -> np.ndarray:
         e.make_plan(force_version)
         e.encode()
         return e.download()
+
+
+def encode_sharded(data, nslices: int, devices: Optional[Sequence[int]] = None, force_version: int = 0,
+                   return_ms: bool = False):
+    """Compress bytes on the GPU(s) slice by slice (gh_encode_sharded): ``nslices`` even
+    cuts, slice i on ``devices[i % len(devices)]`` (default: device 0).  The image equals
+    ``encode(data)``; with ``return_ms`` also the encode kernels' time (the slowest
+    device's sum)."""
+    d = _u8(data)
+    o = gh_opts()
+    o.ngpus, o.reps = 1, 1
+    if devices is not None:
+        arr = (ctypes.c_int * len(devices))(*devices)
+        o.devices = ctypes.cast(arr, ctypes.POINTER(ctypes.c_int))
+        o.ngpus = len(devices)
+    out = np.empty(int(lib().gh_encode_bound(d.size)), dtype=np.uint8)
+    plan = gh_encode_plan()
+    ms = ctypes.c_float()
+    _check(lib().gh_encode_sharded(_ptr(d), d.size, ctypes.byref(o), nslices, force_version, _ptr(out), out.size,
+                                   ctypes.byref(plan), ctypes.byref(ms)))
+    img = out[: plan.file_bytes]
+    return (img, float(ms.value)) if return_ms else img
 
 
 def package_merge(sorted_counts: Sequence[int]) -> list:

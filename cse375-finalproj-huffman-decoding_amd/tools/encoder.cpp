@@ -1,5 +1,5 @@
 // bin/encoder <input> <compressed.huff> [--threads T] [--v2] [--gpu [DEVICE]] [--raw]
-//             [--write-index FILE [--index-stride K]]
+//             [--write-index FILE [--index-stride K]] [--slices K [--devices a,b,c]]
 //
 // Drop-in for the reference encoder CLI (Huffman_coding_Gap_arrays/encoder/src/
 // huff.cpp:30-220): same positional arguments, same output format (v1 header when
@@ -9,7 +9,9 @@
 // reference's own encoder is a GPU one, encoder.cu:382-457).  --write-index also writes
 // the stream's seek index (gaphuff.h "random access"; K = log2 of the stride in segments,
 // default 8) from the encoder itself: gh_encode_index on the host, gh_ectx_index with
-// --gpu; the same index with --raw (G is the same).
+// --gpu; the same index with --raw (G is the same).  --gpu --slices K encodes the input
+// in K slices (gh_encode_sharded), slice i on the i-th of --devices (round robin; default:
+// the --gpu device); the same file, and the index then from gh_encode_index.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -31,13 +33,26 @@ int main(int argc, char** argv) {
   int threads = 0, force = 0, gpu = -1;
   bool raw = false;  // write the gap-less raw-stream container (GH_RAW_MAGIC) instead
   const char* index_path = nullptr;
-  uint32_t index_k = 8;
+  uint32_t index_k = 8, slices = 0;
+  std::vector<int> devices;
   for (int i = 3; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--threads") && i + 1 < argc) threads = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--v2")) force = 2;
     else if (!std::strcmp(argv[i], "--raw")) raw = true;
     else if (!std::strcmp(argv[i], "--write-index") && i + 1 < argc) index_path = argv[++i];
     else if (!std::strcmp(argv[i], "--index-stride") && i + 1 < argc) index_k = (uint32_t)std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--slices") && i + 1 < argc) slices = (uint32_t)std::max(std::atoi(argv[++i]), 0);
+    else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
+      for (const char* s = argv[++i]; *s;) {
+        char* end = nullptr;
+        devices.push_back((int)std::strtol(s, &end, 10));
+        if (end == s) {
+          std::fprintf(stderr, "encoder: bad --devices list\n");
+          return 2;
+        }
+        s = *end == ',' ? end + 1 : end;
+      }
+    }
     else if (!std::strcmp(argv[i], "--gpu")) gpu = (i + 1 < argc && argv[i + 1][0] != '-') ? std::atoi(argv[++i]) : 0;
     else {
       std::fprintf(stderr, "encoder: unknown option %s\n", argv[i]);
@@ -63,7 +78,29 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> out, index;
   double t0, t1, t2;
   int rc;
-  if (gpu >= 0) {
+  if (slices && gpu < 0) {
+    std::fprintf(stderr, "encoder: --slices needs --gpu\n");
+    return 2;
+  }
+  if (gpu >= 0 && slices) {
+    if (devices.empty()) devices.push_back(gpu);
+    const gh_opts opts{(int)devices.size(), devices.data(), 1};
+    float ms = 0.f;
+    out.resize(gh_encode_bound(in.size()));
+    t0 = now_ms();
+    rc = gh_encode_sharded(in.data(), in.size(), &opts, slices, force, out.data(), out.size(), plan, &ms);
+    t2 = now_ms();
+    t1 = t2 - ms;
+    if (!rc) out.resize(plan->file_bytes);
+    if (!rc && index_path) {  // the index of a sliced stream: from the host encoder
+      index.resize(std::max<uint64_t>(gh_index_bytes(plan->g, index_k), 1));
+      rc = gh_encode_index(in.data(), plan, index_k, threads, index.data(), index.size());
+    }
+    if (rc) {
+      std::fprintf(stderr, "encoder: %s\n", gh_last_error());
+      return 1;
+    }
+  } else if (gpu >= 0) {
     gh_ectx* e = nullptr;
     float ms = 0.f;
     rc = gh_ectx_create(gpu, &e);

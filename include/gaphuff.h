@@ -106,6 +106,55 @@ int gh_encode_plan_make(const uint8_t* in, uint64_t n, int threads, int force_ve
 /* Write the compressed image (plan->file_bytes bytes) into `out`. */
 int gh_encode_write(const uint8_t* in, const gh_encode_plan* plan, int threads,
                     void* out, uint64_t out_len);
+/* The plan from a histogram alone (plan->n = the sum of the counts): the same plan as
+ * gh_encode_plan_make on any data with that histogram.  Counts may be sums over the
+ * slices of a stream that no single caller holds. */
+int gh_encode_plan_from_counts(const uint64_t counts[256], int force_version, gh_encode_plan* plan);
+/* Largest file_bytes any input of n bytes can have (16-bit codes, 256 symbols, a v2
+ * header): a buffer to allocate before the plan exists. */
+uint64_t gh_encode_bound(uint64_t n);
+
+/* ---- sliced encode: a stream built slice by slice ---------------------------- */
+/* A codeword's bits depend only on its first bit, and a gap nibble only on the codeword
+ * that crosses a 128-bit boundary, so a contiguous run of input bytes (a slice) is
+ * encoded on its own once the stream-wide plan and the slice's first bit are known.
+ * Under the stream's plan a slice holds code bits [base_bit, base_bit + bits), base_bit
+ * being the bit total of everything before it.  Its output is slice-local: the payload
+ * words [word0, word0 + nwords) and the gap words [gapw0, gapw0 + ngapw) it touches,
+ * with every bit that belongs to a neighbour zero.  ORing all slices' outputs into an
+ * image prepared by gh_encode_image_init gives exactly gh_encode_write's bytes for the
+ * whole input.  No reference counterpart (the reference encodes whole inputs only). */
+typedef struct gh_slice {
+  uint64_t base_bit, bits;   /* code bits [base_bit, base_bit + bits)                   */
+  uint64_t word0, nwords;    /* payload words: base_bit >> 5 up to
+                                ceil((base_bit + bits) / 32); nwords = 0 when bits = 0  */
+  uint64_t gapw0, ngapw;     /* gap words: base_bit >> 10 up to the word of bit
+                                base_bit + bits - 1, inclusive; ngapw = 0 when bits = 0 */
+} gh_slice;
+/* The extents of bits [base_bit, base_bit + bits).  GH_E_ARG: null out, or the sum
+ * overflows 64 bits. */
+int gh_slice_extent(uint64_t base_bit, uint64_t bits, gh_slice* out);
+/* Host encoder of one slice: the n bytes at `in` as the slice at base_bit of the stream
+ * planned by stream_plan.  Writes out->nwords words and out->ngapw gap words, indexed
+ * from out->word0 and out->gapw0 (words[0] is payload word word0).  The buffers do not
+ * depend on `threads`.  GH_E_TABLE: a byte of the slice has length 0 in the plan;
+ * GH_E_ARG: null pointers, base_bit + bits > plan->bits; GH_E_SMALL: words_cap <
+ * nwords or gaps_cap < ngapw (counted in u32) -- *out is filled all the same, so a first
+ * call with caps of 0 sizes the buffers (words and gapw may then be NULL). */
+int gh_encode_slice(const uint8_t* in, uint64_t n, const gh_encode_plan* stream_plan, uint64_t base_bit,
+                    int threads, uint32_t* words, uint64_t words_cap, uint32_t* gapw, uint64_t gaps_cap,
+                    gh_slice* out);
+/* Header of the stream into image[0 .. ), gap and payload words zeroed: the image every
+ * slice is merged into.  GH_E_SMALL when image_len < plan->file_bytes. */
+int gh_encode_image_init(const gh_encode_plan* plan, void* image, uint64_t image_len);
+/* OR one slice's words and gap words into the image (any alignment; the word area starts
+ * 8 + 2 S + 12 bytes into a v1 file).  Slices may be merged in any order, but merges
+ * into one image must not run concurrently: neighbouring slices share their edge words.
+ * GH_E_ARG: null pointers, extents outside the plan's W words / ceil(G / 8) gap words;
+ * GH_E_SMALL: image_len < plan->file_bytes. */
+int gh_slice_merge(void* image, uint64_t image_len, const gh_encode_plan* plan, const gh_slice* slice,
+                   const uint32_t* words, const uint32_t* gapw);
+
 /* Code lengths only: boundary package-merge over `nsyms` counts sorted ascending
  * (stable), restating encoder/src/package_merge.cpp:107-166; lengths written in
  * the same (ascending-count) order. */
@@ -135,6 +184,25 @@ int gh_ectx_plan(gh_ectx* ctx, int force_version, gh_encode_plan* plan);
 int gh_ectx_encode(gh_ectx* ctx, float* kernel_ms);
 /* Header + gap words + payload words into out (plan->file_bytes bytes). */
 int gh_ectx_download(gh_ectx* ctx, void* out, uint64_t out_len);
+/* Sliced encode on the device (see "sliced encode" above): the loaded input is one slice
+ * of a longer stream.
+ * gh_ectx_counts: the GPU histogram of the loaded input, as gh_ectx_plan runs it; no plan
+ * is made, and a following gh_ectx_encode needs a fresh gh_ectx_plan.  The counts of all
+ * slices, summed, go to gh_encode_plan_from_counts. */
+int gh_ectx_counts(gh_ectx* ctx, uint64_t counts[256]);
+/* Encode the loaded input as the slice at base_bit of the stream planned by stream_plan.
+ * The slice's bit total comes from its own histogram (taken here when gh_ectx_counts has
+ * not run since the load).  *out (may be NULL): the extents.  kernel_ms as in
+ * gh_ectx_encode.  Errors as gh_encode_slice's: GH_E_TABLE, GH_E_ARG. */
+int gh_ectx_encode_slice(gh_ectx* ctx, const gh_encode_plan* stream_plan, uint64_t base_bit, gh_slice* out,
+                         float* kernel_ms);
+/* The slice's words and gap words to host memory, laid out as gh_encode_slice lays them
+ * out.  GH_E_STATE unless the context's last encode was a slice encode; GH_E_SMALL: a cap
+ * (in u32) is too small.  After a slice encode gh_ectx_download and gh_ectx_index return
+ * GH_E_STATE: the context holds no whole image, and the seek index of a sliced stream is
+ * gh_encode_index's. */
+int gh_ectx_download_slice(gh_ectx* ctx, uint32_t* words, uint64_t words_cap, uint32_t* gapw,
+                           uint64_t gaps_cap);
 
 /* ---- GPU decoder -------------------------------------------------------------- */
 typedef struct gh_ctx gh_ctx;
@@ -387,6 +455,19 @@ typedef struct gh_opts {
 } gh_opts;
 int gh_decode(const gh_stream* s, uint8_t* out, uint64_t out_len, const gh_opts* opts,
               gh_report* rep);
+
+/* One-shot sliced encode of host memory: the input is cut evenly into nslices byte ranges,
+ * slice i goes to device opts->devices[i % ngpus] (or i % ngpus; ngpus <= 1: device
+ * `devices ? devices[0] : 0`; a device may repeat, as in gh_decode), one host thread per
+ * device and one gh_ectx per slice: load and gh_ectx_counts, then the plan from the summed
+ * counts, then gh_ectx_encode_slice at the scanned bit offsets, and the slices merged in
+ * order into out.  The image is byte-identical to gh_encode_write's.  *plan (may be NULL)
+ * is filled before out_len is checked (GH_E_SMALL when out_len < plan->file_bytes;
+ * gh_encode_bound(n) always suffices).  kernel_ms (may be NULL): per device the sum of its
+ * slices' encode times, the maximum over devices (gh_decode's convention). */
+int gh_encode_sharded(const uint8_t* in, uint64_t n, const gh_opts* opts, uint32_t nslices,
+                      int force_version, void* out, uint64_t out_len, gh_encode_plan* plan,
+                      float* kernel_ms);
 
 /* Evenly split G segments into `nshards` contiguous ranges: bounds[0..nshards]. */
 int gh_plan_shards(uint64_t g, uint32_t nshards, uint64_t* bounds);
