@@ -11,17 +11,11 @@
 #include <algorithm>
 #include <string>
 
+#include "gh_hip.hpp"
 #include "gh_internal.hpp"
 
 namespace gh {
 namespace {
-
-#define GH_HIP(expr)                                                              \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(GH_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
 
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 constexpr int BW_TB = 512;
@@ -58,20 +52,17 @@ extern "C" int gh_bw_copy(void* dst, const void* src, uint64_t bytes, void* hip_
   const uint64_t nb = std::max<uint64_t>(1, (n16 + BW_CHUNK16 - 1) / BW_CHUNK16);
   if (nb > 0x7fffffffull) return fail(GH_E_ARG, "gh_bw_copy: size too large");
   const uint32_t grid = (uint32_t)nb;
-  hipEvent_t e0, e1;
-  GH_HIP(hipEventCreate(&e0));
-  GH_HIP(hipEventCreate(&e1));
+  EventPair ev;
+  if (int rc = ev.create()) return rc;
   hipLaunchKernelGGL(gh_bw_copy_kernel, dim3(grid), dim3(BW_TB), 0, st, (v4u*)dst, (const v4u*)src, n16);
-  GH_HIP(hipEventRecord(e0, st));
+  GH_HIP(hipEventRecord(ev.a, st));
   for (int r = 0; r < reps; ++r)
     hipLaunchKernelGGL(gh_bw_copy_kernel, dim3(grid), dim3(BW_TB), 0, st, (v4u*)dst, (const v4u*)src, n16);
-  GH_HIP(hipEventRecord(e1, st));
+  GH_HIP(hipEventRecord(ev.b, st));
   GH_HIP(hipGetLastError());
-  GH_HIP(hipEventSynchronize(e1));
+  GH_HIP(hipEventSynchronize(ev.b));
   float ms = 0;
-  GH_HIP(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  if (int rc = ev.elapsed(&ms)) return rc;
   if (ms_avg) *ms_avg = ms / reps;
   return GH_OK;
 }

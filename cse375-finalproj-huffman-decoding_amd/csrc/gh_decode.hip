@@ -25,12 +25,15 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "gh_device.hpp"
+#include "gh_hip.hpp"
 #include "gh_internal.hpp"
 #include "gh_lut.hpp"
 
@@ -47,13 +50,6 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 }  // namespace gh
 
 using namespace gh;
-
-#define GH_HIP(expr)                                                              \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(GH_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
 
 // Tile kernel shapes: codes of >= 4-bit codewords (at most 32 per segment) run three
 // segments per lane with 8 output words each; codes with 3-bit codewords (at most 43
@@ -137,17 +133,24 @@ static Kern ws_write_ns(int ns) {
          : ns <= 6 ? ws_write_kern<WS_U, WS_TB, GL, 6, FB>()
                    : ws_write_kern<WS_U, WS_TB, GL, 8, FB>();
 }
+// The <GL, FB> member of a kernel family keyed by a table's width: GL lookups of `bits`
+// bits per window shift, or the canonical fallback with two.  kern(gl, fb) receives the
+// two as integral constants and returns the instantiation.
+template <class F>
+static auto kernel_by_width(uint32_t bits, bool fb, F kern) {
+  using std::integral_constant;
+  if (fb) return kern(integral_constant<int, 2>{}, std::true_type{});
+  const int gl = lookups_per_shift(bits);
+  return gl >= 4 ? kern(integral_constant<int, 4>{}, std::false_type{})
+       : gl == 3 ? kern(integral_constant<int, 3>{}, std::false_type{})
+                 : kern(integral_constant<int, 2>{}, std::false_type{});
+}
 // Count kernel by its LUT width Kc, write kernel by K and NS (store instructions per
 // lane per piece: the typical piece's 16-byte chunks / 64).  fb: codes longer than the
 // tables or incomplete codes (canonical fallback, two lookups per window shift).
 static WsKernels ws_kernels(uint32_t Kc, uint32_t K, int ns, bool fb) {
-  if (fb) return {ws_count_kern<WS_UC, WS_TBC, 2, true>(), ws_write_ns<2, true>(ns)};
-  const int gc = lookups_per_shift(Kc), g = lookups_per_shift(K);
-  const Kern cnt = gc >= 4 ? ws_count_kern<WS_UC, WS_TBC, 4, false>()
-                   : gc == 3 ? ws_count_kern<WS_UC, WS_TBC, 3, false>()
-                             : ws_count_kern<WS_UC, WS_TBC, 2, false>();
-  const Kern wr = g >= 4 ? ws_write_ns<4>(ns) : g == 3 ? ws_write_ns<3>(ns) : ws_write_ns<2>(ns);
-  return {cnt, wr};
+  return {kernel_by_width(Kc, fb, [](auto gl, auto f) { return ws_count_kern<WS_UC, WS_TBC, decltype(gl)::value, decltype(f)::value>(); }),
+          kernel_by_width(K, fb, [ns](auto gl, auto f) { return ws_write_ns<decltype(gl)::value, decltype(f)::value>(ns); })};
 }
 
 // Every name the pickers can return, one per line: the pickers enumerated over their
@@ -181,114 +184,125 @@ static std::string all_kernel_shapes() {
 // 16 zero words, which covers U <= 4.
 static_assert(TILE_U <= 4 && TILE_U3 <= 4, "payload padding (16 words) covers at most 4 segments per lane");
 
-struct gh_ctx {
-  int device = 0;
-  int num_cu = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;  // recorded after every decode, on the stream it ran on
-  bool done_rec = false;
-  hipEvent_t done_ev = nullptr;    // marks the last decode: `done`, or the timed decode's end event
-  bool loaded = false;
-  Canon canon;
-  // the loaded shard
+// ---- the context, by parts ---------------------------------------------------------
+// Each part owns its device memory (DevBuf): resetting a part frees it.
+
+// The loaded shard: segments [seg_begin, seg_end) of a stream of g_total.
+struct Shard {
   uint64_t nseg = 0, seg_begin = 0, seg_end = 0, n_total = 0, g_total = 0;
-  uint32_t gap_nib0 = 0, first_start = 0;
-  uint32_t* d_payload = nullptr;
-  uint32_t* d_gaps = nullptr;
-  uint8_t* d_out = nullptr;
+  uint32_t gap_nib0 = 0, first_start = 0;  // nibble of local segment 0's end in `gaps`; its start bit
+  uint32_t last_end = 0;  // wave split: end bit of the stream's last segment when the shard holds it
+  DevBuf payload;         // words [4 b, 4 e + 1) of the stream + zero padding (16 words in all)
+  DevBuf gaps;            // gap words from word b / 8
+  DevBuf out;
   uint64_t out_cap = 0;
-  unsigned int* d_misc = nullptr;  // [1] status, [2..3] symbol total, [4..11] tile poll counters
-  uint32_t grid = 0;               // workgroups of the tile kernel / the write kernel
-  uint32_t ntiles = 0;             // tiles (tile kernel) / wave blocks (wave split)
-  size_t lds = 0;                  // dynamic LDS of the tile / write kernel
-  size_t lut_bytes = 0;            // LDS bytes of its LUT
-  std::string shape;               // the picked kernel name(s) (gh_ctx_kernel_shape)
-  uint32_t stage_bytes = 0;        // one staging buffer (tile) / one wave's (write kernel)
-  // tile kernel (grouped codes)
-  bool tile = false;
-  uint32_t tile_k = 0, tile_g = 0, lgr = 0;  // LUT width, codewords per window shift, log2 LUT copies
-  uint32_t tile_minl = 4, tile_u = TILE_U;     // kernel shape (tile_kernel_for), segments per lane
-  uint32_t idle_block = 0xFFFFFFFFu;           // GH_TILE_IDLE experiments: a block that exits at once
-  bool mtile = false;              // the two-pass tile kernel (gh_mtile.hip; c->tile is set too)
-  bool mt_fb = false;              // ... with the canonical fallback (codewords longer than its tables)
-  uint32_t mt_kc = 0;              // its count table's width
-  int mt_gl = 2, mt_ns = 4;        // its lookups per window shift, stores per copy-out
-  uint32_t* d_lut_t = nullptr;
-  uint4* d_stamps = nullptr;       // GH_TILE_STAMPS builds only
-  unsigned long long* d_gran = nullptr;  // granules, within-round prefixes, round starts
-  uint64_t gran_words = 0;
+};
+
+enum class Mode { NONE, TILE, MTILE, WSPLIT };  // (NONE: nothing loaded, or an empty shard)
+
+// Tile kernel (grouped codes) and two-pass tile kernel (gh_mtile.hip).
+struct TilePlan {
+  uint32_t ntiles = 0;
+  uint32_t kbits = 0;      // LUT width (two-pass: its write table's)
+  uint32_t kbits_c = 0;    // two-pass: its count table's width
+  uint32_t lut_lgr = 0;    // tile: log2 copies of the LUT in LDS
+  uint32_t clut_lgr = 0;   // two-pass: log2 copies of the count table in LDS
+  uint32_t lut_bytes = 0;  // LDS bytes of the tables (tile: the LUT's copies; two-pass: write + count + fallback)
+  uint32_t stage_bytes = 0;  // one staging buffer (tile) / one wave's region (two-pass)
+  uint32_t idle_block = 0xFFFFFFFFu;  // GH_TILE_IDLE experiments: a block that exits at once
   uint32_t epoch = 0;
-  // wave split (every other code)
-  bool ws = false;
-  bool ws_fb = false;              // with the canonical fallback
-  uint32_t ws_k = 0, ws_kc = 0;    // write / count LUT widths
-  uint32_t ws_lgc = 0;             // log2 count-LUT copies in LDS
-  uint32_t ws_nblocks = 0, ws_nranges = 0, ws_grid_c = 0;
-  int ws_ns = 4;
-  size_t lds_count = 0;            // dynamic LDS of the count kernel
-  uint32_t ws_last_end = 0;        // end bit of the stream's last segment when the shard holds it
-  uint32_t* d_ws_lut_c = nullptr;  // count LUT {b | end mask << 16}
-  uint64_t* d_ws_lut_w = nullptr;  // write LUT {symbols, b | n << 8}
-  uint32_t* d_fb = nullptr;        // canonical fallback tables
-  uint8_t* d_seg_cnt = nullptr;
-  uint4* d_ws_junk = nullptr;
-  unsigned long long* d_rng_tot = nullptr;
-  unsigned long long* d_rng_off = nullptr;
-  // range gather (gh_ctx_gather): the tables live from the first gather to the next load,
-  // the piece and output buffers for the life of the context (grown on demand)
-  bool ga_ready = false;
-  bool ga_fb = false;
-  uint32_t ga_kc = 0, ga_ks = 0;   // count / symbol table widths
-  uint32_t ga_last_end = 0;
-  uint32_t ga_wgs = 0;             // workgroups the device holds at once
-  size_t ga_lds = 0;
-  const void* ga_kern = nullptr;
-  uint32_t* d_ga_lut_c = nullptr;  // count table {b | end mask << 16}
-  uint32_t* d_ga_lut_s = nullptr;  // symbol table {len | symbol << 8}
-  uint32_t* d_ga_fb = nullptr;     // canonical fallback tables
-  gh_gather_piece* d_ga_pieces = nullptr;
-  uint64_t ga_pieces_cap = 0;
-  uint8_t* d_ga_out = nullptr;
-  uint64_t ga_out_cap = 0;
-  std::vector<gh_gather_piece> ga_pieces;
-  hipEvent_t ga_ev0 = nullptr, ga_ev1 = nullptr;
-  // timing
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, pool;
+  uint64_t gran_words = 0;
+  DevBuf lut;     // the tables as they lie in LDS (one copy each)
+  DevBuf gran;    // granules, within-round prefixes, round starts
+  DevBuf stamps;  // GH_TILE_STAMPS builds only
+};
+
+// Wave split (every other code): count, scan and write kernels.
+struct WsPlan {
+  Kern count{};            // (the write kernel is Plan::kern)
+  uint32_t grid_c = 0;     // workgroups of the count kernel
+  size_t lds_count = 0;    // its dynamic LDS
+  uint32_t k = 0, kc = 0;  // write / count LUT widths
+  uint32_t lgc = 0;        // log2 count-LUT copies in LDS
+  uint32_t lut_bytes = 0;  // LDS bytes of the write LUT
+  uint32_t stage_bytes = 0;  // one wave's staging in the write kernel
+  uint32_t nblocks = 0, nranges = 0;  // superblocks; ranges (one per wave of the write grid)
+  DevBuf lut_c;    // count LUT {b | end mask << 16}
+  DevBuf lut_w;    // write LUT {symbols, b | n << 8}
+  DevBuf fb;       // canonical fallback tables
+  DevBuf seg_cnt, junk, rng_tot, rng_off;
+};
+
+// How the loaded shard is decoded: picked once by the load, launched as stored.
+struct Plan {
+  Mode mode = Mode::NONE;
+  Kern kern{};             // the tile / two-pass tile / wave-split write kernel
+  uint32_t grid = 0, block = 0;
+  size_t lds = 0;          // its dynamic LDS
+  std::string shape;       // the picked kernel name(s) (gh_ctx_kernel_shape)
+  TilePlan tile;           // mode TILE or MTILE
+  WsPlan ws;               // mode WSPLIT
+  bool tiled() const { return mode == Mode::TILE || mode == Mode::MTILE; }
+};
+
+// Range gather (gh_ctx_gather): the tables live from the first gather to the next load,
+// the piece and output buffers for the life of the context (grown on demand).
+struct GatherTables {
+  bool ready = false;
+  uint32_t kc = 0, ks = 0;  // count / symbol table widths
+  uint32_t last_end = 0;
+  uint32_t wgs = 0;         // workgroups the device holds at once
+  size_t lds = 0;
+  const void* kern = nullptr;
+  DevBuf lut_c;  // count table {b | end mask << 16}
+  DevBuf lut_s;  // symbol table {len | symbol << 8}
+  DevBuf fb;     // canonical fallback tables
+};
+struct Gather {
+  GatherTables tab;
+  DevBuf d_pieces, d_out;
+  std::vector<gh_gather_piece> pieces;
+  EventPair ev;
+};
+
+struct Timing {
+  std::vector<EventPair> pending, pool;  // timed decodes not yet reported; idle pairs
   double acc_ms = 0;
   uint32_t nlaunch = 0;
 };
 
+struct gh_ctx {
+  int device = 0;
+  int num_cu = 0;
+  Stream stream;
+  Event done;  // recorded after every untimed decode, on the stream it ran on
+  bool done_rec = false;
+  hipEvent_t done_ev = nullptr;  // marks the last decode: `done`, or the timed decode's end event
+  bool loaded = false;
+  Canon canon;
+  DevBuf misc;  // u32 [1] status, [2..3] symbol total, [4..11] tile poll counters, [16] gather status
+  Shard shard;
+  Plan plan;
+  Gather gather;
+  Timing timing;
+  ~gh_ctx();
+  unsigned int* misc_at(int i) const { return misc.get<unsigned int>() + i; }
+};
+
 static void free_shard(gh_ctx* c) {
   (void)hipSetDevice(c->device);
-  for (void* p : {(void*)c->d_payload, (void*)c->d_gaps, (void*)c->d_out, (void*)c->d_gran, (void*)c->d_lut_t,
-                  (void*)c->d_stamps, (void*)c->d_ws_lut_c, (void*)c->d_ws_lut_w, (void*)c->d_fb,
-                  (void*)c->d_seg_cnt, (void*)c->d_ws_junk, (void*)c->d_rng_tot, (void*)c->d_rng_off,
-                  (void*)c->d_ga_lut_c, (void*)c->d_ga_lut_s, (void*)c->d_ga_fb})
-    (void)hipFree(p);
-  c->d_ga_lut_c = nullptr;
-  c->d_ga_lut_s = nullptr;
-  c->d_ga_fb = nullptr;
-  c->ga_ready = false;
-  c->d_payload = nullptr;
-  c->d_gaps = nullptr;
-  c->d_out = nullptr;
-  c->d_gran = nullptr;
-  c->d_lut_t = nullptr;
-  c->d_stamps = nullptr;
-  c->d_ws_lut_c = nullptr;
-  c->d_ws_lut_w = nullptr;
-  c->d_fb = nullptr;
-  c->d_seg_cnt = nullptr;
-  c->d_ws_junk = nullptr;
-  c->d_rng_tot = nullptr;
-  c->d_rng_off = nullptr;
-  c->tile = false;
-  c->mtile = false;
-  c->mt_fb = false;
-  c->ws = false;
-  c->shape.clear();
+  c->shard = Shard{};
+  c->plan = Plan{};
+  c->gather.tab = GatherTables{};
   c->loaded = false;
 }
+
+// Raises a kernel's dynamic LDS limit where a launch needs more than the 64 KiB default.
+static int allow_lds(const void* fn, size_t lds) {
+  if (lds > 64 * 1024) GH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return GH_OK;
+}
+
 
 // GH_TILE_GRID=n (n >= 2; tests): fewer workgroups of a persistent kernel than fit the
 // device, so a small stream gives each decoding workgroup many tiles and rounds.  It only
@@ -299,18 +313,32 @@ static uint32_t tile_grid_cap(uint32_t grid) {
   return grid;
 }
 
+// The part of a tile plan that both tile kernels share, once the kernel and its tables are
+// known: the grid (workgroup 0 leads the rounds, up to LEAD_A aggregates per thread: D =
+// grid - 1 <= LEAD_A * block, the others decode; every workgroup must be resident at once:
+// `resident` is what the device holds, and decodes on one device are chained, see
+// DevChain) and the per-tile aggregates and prefixes.  Leaves p.grid < 2 when the shard is
+// too small for the kernel (the wave split then takes the code).
+static int tile_grid_and_granules(Plan& p, uint64_t resident) {
+  p.grid = (uint32_t)std::min<uint64_t>({(uint64_t)p.tile.ntiles + 1, resident, (uint64_t)LEAD_A * p.block});
+  p.grid = tile_grid_cap(p.grid);
+  if (p.grid < 2) return GH_OK;
+  p.tile.gran_words = 2ull * p.tile.ntiles + 2;
+  return p.tile.gran.alloc(8ull * p.tile.gran_words, true);
+}
+
 // ---- tile kernel setup -----------------------------------------------------------
 // LUT width K (>= maxlen), replicated 2^lgr times in LDS: the largest replication that
-// keeps the best occupancy.  Returns GH_OK with c->tile false when the kernel does not
-// fit a CU (the wave split then takes the code).
+// keeps the best occupancy.  Returns GH_OK with the plan's mode left NONE when the kernel
+// does not fit a CU (the wave split then takes the code).
 static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
   const Canon& cn = c->canon;
+  Plan p;
+  TilePlan& t = p.tile;
   const uint32_t maxsyms = (128 + cn.minlen - 1) / cn.minlen;  // <= 43 (minlen >= 3)
-  c->tile_k = K;
-  c->tile_g = std::min<uint32_t>(4, 32 / cn.maxlen);
-  c->tile_minl = cn.minlen >= 5 && GH_TILE_OW7 ? 5 : cn.minlen >= 4 ? 4 : 3;
-  c->tile_u = tile_u_for(cn.minlen);
-  c->ntiles = (uint32_t)ceil_div(c->nseg, (uint64_t)c->tile_u * TILE_TB);
+  t.kbits = K;
+  const uint32_t tile_u = tile_u_for(cn.minlen);
+  t.ntiles = (uint32_t)ceil_div(c->shard.nseg, (uint64_t)tile_u * TILE_TB);
   // Staging is sized for the typical piece, not the worst case (128 / minlen bytes per
   // segment): TILE_SCAP = 20 bytes per segment for grouped codes (r = 0.1: 16.5), the
   // stream's mean + 12 % for minlen-3 codes (r = 0.5: 21.5 -> 25), so that two
@@ -323,17 +351,20 @@ static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
       maxsyms, cn.minlen >= 4 ? (uint64_t)TILE_SCAP : (uint64_t)std::ceil(std::max(avg_seg_bytes, 1.0) * scapf + 1));
   if (const char* e = getenv("GH_TILE_SCAP")) per_seg = std::min<uint64_t>(maxsyms, (uint64_t)std::max(1, atoi(e)));
   const uint64_t margin = 4ull * (cn.minlen >= 4 ? 8 : 11) + 4;  // garbage past a piece's end (4 OW + 4, OW <= 8 / 11)
-  const uint64_t seg_wave = 64ull * c->tile_u;
+  const uint64_t seg_wave = 64ull * tile_u;
   per_seg = std::min<uint64_t>(per_seg, ((uint64_t)TILE_NS * 64 * 16 - 2 * STAGE_PAD - margin) / seg_wave);
-  c->stage_bytes = (uint32_t)((STAGE_PAD + seg_wave * per_seg + margin + 15) & ~15ull);
+  t.stage_bytes = (uint32_t)((STAGE_PAD + seg_wave * per_seg + margin + 15) & ~15ull);
   const std::vector<uint32_t> lt = grouped_lut(cn, K);
-  const Kern kern = tile_kernel_for(c->tile_minl, c->tile_g);
+  // by the shortest codeword (>= 5 with 7 output words, >= 4, 3) and the codewords per window shift
+  p.kern = tile_kernel_for(cn.minlen, std::min<uint32_t>(4, 32 / cn.maxlen));
+  p.block = TILE_TB;
+  if (int rc = allow_lds(p.kern.fn, 160 * 1024)) return rc;
   const char* envr = getenv("GH_LGR");
   const int lg = envr ? std::clamp(atoi(envr), 0, 14 - (int)K) : std::min(5, 14 - (int)K);
   int best = 0, best_lg = 0;
   for (int l2 = lg; l2 >= 0; --l2) {
     int pc = 0;
-    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern.fn, TILE_TB, tile_lds_bytes(4ull << (K + l2), c->stage_bytes)));
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, p.kern.fn, TILE_TB, tile_lds_bytes(4ull << (K + l2), t.stage_bytes)));
     if (pc > best) {
       best = pc;
       best_lg = l2;
@@ -346,29 +377,20 @@ static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
   // (its bounded polls then report GH_ST_TIMEOUT), so never plan more than two.
   best = std::min(best, 2);
   if (best < 1) return GH_OK;
-  GH_HIP(hipMalloc(&c->d_lut_t, 4ull << K));
-  GH_HIP(hipMemcpy(c->d_lut_t, lt.data(), 4ull << K, hipMemcpyHostToDevice));
-  c->lgr = (uint32_t)best_lg;
-  c->lut_bytes = 4ull << (K + best_lg);
-  c->lds = tile_lds_bytes(c->lut_bytes, c->stage_bytes);
-  // workgroup 0 leads the rounds (up to LEAD_A aggregates per thread: D = grid - 1 <=
-  // LEAD_A * TILE_TB), the others decode; every workgroup must be resident at once
-  // (the grid is sized from the occupancy; decodes on one device are chained, see DevChain)
-  c->grid = (uint32_t)std::min<uint64_t>({(uint64_t)c->ntiles + 1, (uint64_t)best * c->num_cu, (uint64_t)LEAD_A * TILE_TB});
-  c->grid = tile_grid_cap(c->grid);
-  c->idle_block = 0xFFFFFFFFu;
+  t.lut_lgr = (uint32_t)best_lg;
+  t.lut_bytes = (uint32_t)(4ull << (K + best_lg));
+  p.lds = tile_lds_bytes(t.lut_bytes, t.stage_bytes);
+  if (int rc = tile_grid_and_granules(p, (uint64_t)best * c->num_cu)) return rc;
+  if (p.grid < 2) return GH_OK;
   if (const char* e = getenv("GH_TILE_IDLE"))  // experiment: block grid / 2 (the leader's CU partner) idles
-    if (atoi(e) && c->grid == (uint32_t)best * c->num_cu && best == 2) {
-      c->idle_block = c->grid / 2;
-    }
-  if (c->grid < 2) return GH_OK;  // (the wave split then takes the code)
-  if (GH_TILE_STAMPS) {
-    const size_t nb = 32ull * c->grid * 2 * 128 + 8ull * (3ull * c->ntiles + 64 + 4 * 1024 + 4ull * c->grid);
-    GH_HIP(hipMalloc(&c->d_stamps, nb));
-    GH_HIP(hipMemset(c->d_stamps, 0, nb));
-  }
-  c->shape = kern.name;
-  c->tile = true;
+    if (atoi(e) && p.grid == (uint32_t)best * c->num_cu && best == 2) t.idle_block = p.grid / 2;
+  if (int rc = t.lut.upload(lt.data(), 4ull << K)) return rc;
+  if (GH_TILE_STAMPS)
+    if (int rc = t.stamps.alloc(32ull * p.grid * 2 * 128 + 8ull * (3ull * t.ntiles + 64 + 4 * 1024 + 4ull * p.grid), true))
+      return rc;
+  p.shape = p.kern.name;
+  p.mode = Mode::TILE;
+  c->plan = std::move(p);
   return GH_OK;
 }
 
@@ -377,11 +399,13 @@ static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
 // by the single-pass tile kernel.  One LUT of width K (the wave split's write width; 11
 // with a 1-bit codeword) with the codewords' start masks; one staging region per wave, sized for the stream's mean
 // bytes per segment + 12 % and at least one chain's worst case (64 x 128 / minlen bytes: a larger
-// piece is written and copied out chain by chain).  Returns GH_OK with c->tile false when
-// it does not fit a CU.
+// piece is written and copied out chain by chain).  Returns GH_OK with the plan's mode
+// left NONE when it does not fit a CU.
 static uint32_t ws_write_bits(const Canon& cn);
 static int mtile_setup(gh_ctx* c, double avg_seg_bytes) {
   const Canon& cn = c->canon;
+  Plan p;
+  TilePlan& t = p.tile;
   // codes with a 1-bit codeword: segments of up to 128 codewords, a chain's worst case
   // 8 KB, so 11-bit tables (24 KB with the count table) leave 16 regions of 8.5 KB
   const bool one = cn.minlen == 1;
@@ -413,7 +437,6 @@ static int mtile_setup(gh_ctx* c, double avg_seg_bytes) {
   if (const char* e = getenv("GH_MT_CLGR")) clgr = (uint32_t)std::clamp(atoi(e), 0, 3);
   if (!GH_MT_CLUT || one) clgr = 0;
   clgr = std::min<uint32_t>(clgr, Kc + clgr > 14 ? 14 - Kc : clgr);
-  c->mt_kc = Kc;
   const uint64_t lut_b = (GH_MT_CLUT ? (8ull << K) + (4ull << (Kc + clgr)) : 8ull << K)  // write table (+ count table)
                          + (fb ? (uint64_t)FB_BYTES : 0);                         // (+ fallback tables)
   const uint64_t lds_free = 160ull * 1024 - lut_b - mtile_lds_bytes(0, 0);
@@ -426,57 +449,42 @@ static int mtile_setup(gh_ctx* c, double avg_seg_bytes) {
   }
   const uint64_t cap = std::max<uint64_t>(64ull * MT_U * per_seg, 64ull * maxsyms);  // piece bytes staged at once
   if (STAGE_PAD + cap + 16 > region_max) return GH_OK;
-  c->mt_ns = cap + 16 <= 4096 ? 4 : cap + 16 <= 6144 ? 6 : cap + 16 <= 8192 ? 8 : 10;  // the copy-out's chunks cover a piece
-  c->stage_bytes = (uint32_t)((STAGE_PAD + cap + 16 + 15) & ~15ull);  // + the write overrun
-  c->mt_gl = lookups_per_shift(K);
-  c->mt_fb = fb;
-  const Kern kern = mtile_kernel_for(c->mt_gl, c->mt_ns, fb);
-  c->lut_bytes = lut_b;
-  c->lds = mtile_lds_bytes(c->lut_bytes, c->stage_bytes);
+  const int ns = cap + 16 <= 4096 ? 4 : cap + 16 <= 6144 ? 6 : cap + 16 <= 8192 ? 8 : 10;  // the copy-out's chunks cover a piece
+  t.stage_bytes = (uint32_t)((STAGE_PAD + cap + 16 + 15) & ~15ull);  // + the write overrun
+  p.kern = mtile_kernel_for(lookups_per_shift(K), ns, fb);
+  p.block = MT_TB;
+  t.lut_bytes = (uint32_t)lut_b;
+  p.lds = mtile_lds_bytes(t.lut_bytes, t.stage_bytes);
+  if (int rc = allow_lds(p.kern.fn, 160 * 1024)) return rc;
   int pc = 0;
-  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern.fn, MT_TB, c->lds));
+  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, p.kern.fn, MT_TB, p.lds));
   pc = std::min(pc, 2);  // (as tile_setup: the occupancy query can answer one too many)
   if (pc < 1) return GH_OK;
-  std::vector<uint64_t> lt = multi_lut(cn, K);
-  if (GH_MT_CLUT) {  // the count table (u32 {b | start mask << 16}, every codeword of the window)
-    std::vector<uint32_t> lc(1u << Kc);
-    for (uint32_t i = 0; i < (1u << Kc); ++i) {
-      uint32_t n = 0, m = 0;
-      const uint32_t b = window_codewords(cn, i, Kc, 32, &n, nullptr, &m);
-      lc[i] = b | ((n ? (1u | (m << 1)) & ((1u << b) - 1u) : 0u) << 16);
-    }
-    if (clgr) {  // replicated: dword i = entry i >> clgr
-      std::vector<uint32_t> lr(1u << (Kc + clgr));
-      for (uint32_t i = 0; i < lr.size(); ++i) lr[i] = lc[i >> clgr];
-      lc.swap(lr);
-    }
-    std::vector<uint64_t> both(lut_b / 8);
-    const uint64_t cb = 4ull << (Kc + clgr);
-    const bool cfirst = cb > (8ull << K);  // the larger table first (gh_mtile.hip)
-    std::memcpy((uint8_t*)both.data() + (cfirst ? 0 : 8ull << K), lc.data(), cb);
-    std::memcpy((uint8_t*)both.data() + (cfirst ? cb : 0), lt.data(), 8ull << K);
-    lt.swap(both);
+  t.kbits = K;
+  t.kbits_c = Kc;
+  t.clut_lgr = clgr;
+  t.ntiles = (uint32_t)ceil_div(c->shard.nseg, (uint64_t)MT_U * MT_TB);
+  if (int rc = tile_grid_and_granules(p, (uint64_t)pc * c->num_cu)) return rc;
+  if (p.grid < 2) return GH_OK;
+  // the tables as they lie in LDS: the write and count tables, the larger first
+  // (gh_mtile.hip), then the canonical tables (the kernel reads the last FB_BYTES)
+  std::vector<uint64_t> img(lut_b / 8, 0);
+  const std::vector<uint64_t> lt = multi_lut(cn, K);
+  const uint64_t wb = 8ull << K, cb = GH_MT_CLUT ? 4ull << (Kc + clgr) : 0;
+  std::memcpy((uint8_t*)img.data() + (cb > wb ? cb : 0), lt.data(), wb);
+  if (GH_MT_CLUT) {
+    const std::vector<uint32_t> lc = start_count_lut(cn, Kc, clgr);
+    std::memcpy((uint8_t*)img.data() + (cb > wb ? 0 : wb), lc.data(), cb);
   }
-  if (fb) {  // the canonical tables after the LUTs (the kernel reads the last FB_BYTES)
+  if (fb) {
     uint32_t fbt[FB_WORDS];
     fallback_tables(cn, fbt);
-    const size_t at = lut_b - FB_BYTES;
-    lt.resize(lut_b / 8, 0);
-    std::memcpy((uint8_t*)lt.data() + at, fbt, sizeof(fbt));
+    std::memcpy((uint8_t*)img.data() + lut_b - FB_BYTES, fbt, sizeof(fbt));
   }
-  GH_HIP(hipMalloc(&c->d_lut_t, lut_b));
-  GH_HIP(hipMemcpy(c->d_lut_t, lt.data(), lut_b, hipMemcpyHostToDevice));
-  c->tile_k = K;
-  c->lgr = clgr;  // (the two-pass kernel: the count table's copies)
-  c->tile_u = MT_U;
-  c->ntiles = (uint32_t)ceil_div(c->nseg, (uint64_t)MT_U * MT_TB);
-  c->grid = (uint32_t)std::min<uint64_t>({(uint64_t)c->ntiles + 1, (uint64_t)pc * c->num_cu, (uint64_t)LEAD_A * MT_TB});
-  c->grid = tile_grid_cap(c->grid);
-  if (c->grid < 2) return GH_OK;
-  c->idle_block = 0xFFFFFFFFu;
-  c->shape = kern.name;
-  c->mtile = true;
-  c->tile = true;
+  if (int rc = t.lut.upload(img.data(), lut_b)) return rc;
+  p.shape = p.kern.name;
+  p.mode = Mode::MTILE;
+  c->plan = std::move(p);
   return GH_OK;
 }
 
@@ -534,30 +542,32 @@ static int ws_ns_for(double avg_seg_bytes) {
   return ns <= 2 ? 2 : ns <= 3 ? 3 : ns <= 4 ? 4 : ns <= 6 ? 6 : 8;
 }
 
+// A count table of width kc and the canonical fallback tables, built and uploaded: for the
+// wave split's count pass, the index build and the gather.
+static int upload_count_tables(const Canon& cn, uint32_t kc, DevBuf& lut_c, DevBuf& fb) {
+  std::vector<uint32_t> lc;
+  count_lut(cn, kc, &lc);
+  uint32_t fbt[FB_WORDS];
+  fallback_tables(cn, fbt);
+  if (int rc = lut_c.upload(lc.data(), 4ull << kc)) return rc;
+  return fb.upload(fbt, sizeof(fbt));
+}
+
 static int ws_setup(gh_ctx* c, double avg_seg_bytes) {
   const Canon& cn = c->canon;
+  const uint64_t nseg = c->shard.nseg;
+  Plan p;
+  WsPlan& w = p.ws;
   const uint32_t K = ws_write_bits(cn), kc = ws_count_bits(cn);
   // canonical fallback: codewords longer than a table, or patterns outside an incomplete
   // code (a LUT entry with no codeword)
   const bool fb = kraft16(cn) != 65536 || cn.maxlen > std::min(K, kc);
-  c->ws_fb = fb;
-  c->ws_k = K;
-  c->ws_kc = kc;
-  {
-    const std::vector<uint64_t> lw = write_lut(cn, K);
-    std::vector<uint32_t> lc;
-    count_lut(cn, kc, &lc);
-    GH_HIP(hipMalloc(&c->d_ws_lut_w, 8ull << K));
-    GH_HIP(hipMemcpy(c->d_ws_lut_w, lw.data(), 8ull << K, hipMemcpyHostToDevice));
-    GH_HIP(hipMalloc(&c->d_ws_lut_c, 4ull << kc));
-    GH_HIP(hipMemcpy(c->d_ws_lut_c, lc.data(), 4ull << kc, hipMemcpyHostToDevice));
-    uint32_t fbt[FB_WORDS];
-    fallback_tables(cn, fbt);
-    GH_HIP(hipMalloc(&c->d_fb, sizeof(fbt)));
-    GH_HIP(hipMemcpy(c->d_fb, fbt, sizeof(fbt), hipMemcpyHostToDevice));
-  }
-  c->lut_bytes = 8ull << K;  // >= 32 bytes: whole 16-byte chunks
-  const size_t lb = c->lut_bytes + (fb ? (size_t)FB_BYTES : 0);  // write kernel: LUT + fallback tables
+  w.k = K;
+  w.kc = kc;
+  if (int rc = w.lut_w.upload(write_lut(cn, K).data(), 8ull << K)) return rc;
+  if (int rc = upload_count_tables(cn, kc, w.lut_c, w.fb)) return rc;
+  w.lut_bytes = 8u << K;  // >= 32 bytes: whole 16-byte chunks
+  const size_t lb = w.lut_bytes + (fb ? (size_t)FB_BYTES : 0);  // write kernel: LUT + fallback tables
   constexpr int NW = WS_TB / 64;
   // codewords per segment: wholly inside [start, E), E - start <= 143
   const uint32_t maxsyms = std::min<uint32_t>(143 / std::max<uint32_t>(cn.minlen, 1) + 1, 255);
@@ -579,41 +589,45 @@ static int ws_setup(gh_ctx* c, double avg_seg_bytes) {
   }
   if (const char* es = getenv("GH_WS_STAGE"))  // tests: force a small staging (per-chain blocks)
     stage = std::max<size_t>((size_t)atoll(es), (chain_worst + 15) & ~15ull) & ~15ull;
-  c->stage_bytes = (uint32_t)stage;
-  c->lds = lb + NW * stage;
+  w.stage_bytes = (uint32_t)stage;
+  p.lds = lb + NW * stage;
   // count LUT copies (lane l reads copy l mod 2^lgc: fewer bank conflicts on the skewed
   // lookups), up to 32 KB in LDS; GH_WS_LGC overrides (tests, experiments)
-  c->ws_lgc = 0;
   if (!fb) {
     uint32_t lgc = 0;
     while (lgc < 5 && (4ull << (kc + lgc + 1)) <= (uint64_t)WS_CLUT_MAX && 30u - kc - (lgc + 1) >= 16u) ++lgc;
     if (const char* e = getenv("GH_WS_LGC")) lgc = (uint32_t)std::clamp(atoi(e), 0, std::max(0, 14 - (int)kc));
-    c->ws_lgc = lgc;
+    w.lgc = lgc;
   }
-  c->lds_count = std::max<size_t>(4ull << (kc + c->ws_lgc), 64) + (fb ? FB_BYTES : 0);
-  c->ws_ns = ws_ns_for(avg_seg_bytes);
-  if (const char* en = getenv("GH_WS_NS")) c->ws_ns = std::clamp(atoi(en), 2, 8);
-  const WsKernels k = ws_kernels(kc, K, c->ws_ns, fb);
+  w.lds_count = std::max<size_t>(4ull << (kc + w.lgc), 64) + (fb ? FB_BYTES : 0);
+  int ns = ws_ns_for(avg_seg_bytes);
+  if (const char* en = getenv("GH_WS_NS")) ns = std::clamp(atoi(en), 2, 8);
+  const WsKernels k = ws_kernels(kc, K, ns, fb);
+  w.count = k.count;
+  p.kern = k.write;
+  p.block = WS_TB;
+  if (int rc = allow_lds(w.count.fn, w.lds_count)) return rc;
+  if (int rc = allow_lds(p.kern.fn, p.lds)) return rc;
   int pc_c = 0, pc_w = 0;
-  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_c, k.count.fn, WS_TBC, c->lds_count));
-  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_w, k.write.fn, WS_TB, c->lds));
+  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_c, w.count.fn, WS_TBC, w.lds_count));
+  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_w, p.kern.fn, WS_TB, p.lds));
   if (pc_c < 1 || pc_w < 1) return fail(GH_E_HIP, "wave-split kernels do not fit on a CU");
-  c->ws_nblocks = (uint32_t)ceil_div(c->nseg, (uint64_t)WS_SB);  // superblocks
-  const uint64_t wg_blocks = ceil_div(c->ws_nblocks, (uint64_t)NW);  // workgroups that have a superblock
-  c->grid = (uint32_t)std::min<uint64_t>((uint64_t)pc_w * c->num_cu, wg_blocks);
-  c->ws_grid_c = (uint32_t)std::min<uint64_t>((uint64_t)pc_c * c->num_cu, ceil_div(c->ws_nblocks, (uint64_t)(WS_TBC / 64)));
+  w.nblocks = (uint32_t)ceil_div(nseg, (uint64_t)WS_SB);  // superblocks
+  const uint64_t wg_blocks = ceil_div(w.nblocks, (uint64_t)NW);  // workgroups that have a superblock
+  p.grid = (uint32_t)std::min<uint64_t>((uint64_t)pc_w * c->num_cu, wg_blocks);
+  w.grid_c = (uint32_t)std::min<uint64_t>((uint64_t)pc_c * c->num_cu, ceil_div(w.nblocks, (uint64_t)(WS_TBC / 64)));
   if (const char* eg = getenv("GH_WS_GRID")) {  // tests: few workgroups, many blocks per wave
-    c->grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)c->grid);
-    c->ws_grid_c = (uint32_t)std::clamp<long>(atol(eg), 1, (long)c->ws_grid_c);
+    p.grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)p.grid);
+    w.grid_c = (uint32_t)std::clamp<long>(atol(eg), 1, (long)w.grid_c);
   }
-  c->ws_nranges = c->grid * (uint32_t)NW;  // one contiguous range per wave of the write grid
-  c->ntiles = c->ws_nblocks;
-  GH_HIP(hipMalloc(&c->d_seg_cnt, c->nseg + WS_CNT_PAD + 16));
-  GH_HIP(hipMalloc(&c->d_ws_junk, 16ull * 64 * c->ws_nranges));
-  GH_HIP(hipMalloc(&c->d_rng_tot, 8ull * c->ws_nranges + 16));
-  GH_HIP(hipMalloc(&c->d_rng_off, 8ull * c->ws_nranges + 16));
-  c->shape = std::string(k.count.name) + "+" + k.write.name;
-  c->ws = true;
+  w.nranges = p.grid * (uint32_t)NW;  // one contiguous range per wave of the write grid
+  if (int rc = w.seg_cnt.alloc(nseg + WS_CNT_PAD + 16)) return rc;
+  if (int rc = w.junk.alloc(16ull * 64 * w.nranges)) return rc;
+  if (int rc = w.rng_tot.alloc(8ull * w.nranges + 16)) return rc;
+  if (int rc = w.rng_off.alloc(8ull * w.nranges + 16)) return rc;
+  p.shape = std::string(w.count.name) + "+" + p.kern.name;
+  p.mode = Mode::WSPLIT;
+  c->plan = std::move(p);
   return GH_OK;
 }
 
@@ -634,11 +648,10 @@ static uint32_t last_segment_end(const Canon& cn, const uint32_t* w5, uint32_t s
   return std::max<uint32_t>(pos, 128);
 }
 
-// Start bit of global segment i (i >= 1) from the host gap words.
-static uint32_t seg_start_host(const gh_stream* s, uint64_t i) {
-  const uint64_t nib = i - 1;
+// Gap nibble `nib` of gap words in host memory (any alignment): 8 per u32, lowest first.
+static uint32_t gap_nibble(const void* words, uint64_t nib) {
   uint32_t wv;
-  std::memcpy(&wv, (const uint8_t*)s->gap_words + 4 * (nib >> 3), 4);
+  std::memcpy(&wv, (const uint8_t*)words + 4 * (nib >> 3), 4);
   return (wv >> (4 * (nib & 7))) & 15u;
 }
 
@@ -659,23 +672,14 @@ extern "C" int gh_ctx_create(int device, gh_ctx** out) {
   GH_HIP(hipGetDeviceProperties(&prop, device));
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     return fail(GH_E_NODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
-  gh_ctx* c = new gh_ctx();
+  std::unique_ptr<gh_ctx> c(new gh_ctx());  // (a failure below frees what was made)
   c->device = device;
   c->num_cu = prop.multiProcessorCount;
   GH_HIP(hipSetDevice(device));
-  GH_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  GH_HIP(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
-  GH_HIP(hipMalloc(&c->d_misc, 128));
-  GH_HIP(hipMemset(c->d_misc, 0, 128));
-  for (uint32_t ml : {3u, 4u, 5u})
-    for (uint32_t gv : {2u, 3u, 4u})
-      (void)hipFuncSetAttribute(tile_kernel_for(ml, gv).fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  for (int gl : {2, 3, 4})
-    for (int ns : {4, 6, 8, 10})
-      for (bool fb : {false, true})
-        (void)hipFuncSetAttribute(mtile_kernel_for(gl, ns, fb).fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipGetLastError();
-  *out = c;
+  if (int rc = c->stream.create()) return rc;
+  if (int rc = c->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = c->misc.alloc(128, true)) return rc;
+  *out = c.release();
   return GH_OK;
 }
 
@@ -690,7 +694,7 @@ static int copy_name(const std::string& s, char* buf, size_t cap) {
 extern "C" int gh_ctx_kernel_shape(gh_ctx* c, char* buf, size_t cap) {
   if (!c) return fail(GH_E_ARG, "null ctx");
   if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_kernel_shape before gh_ctx_load");
-  return copy_name(c->shape, buf, cap);
+  return copy_name(c->plan.shape, buf, cap);
 }
 
 extern "C" int gh_kernel_shapes(char* buf, size_t cap) { return copy_name(all_kernel_shapes(), buf, cap); }
@@ -723,42 +727,28 @@ static DevChain& dev_chain(int device) {
   return *d;
 }
 
+gh_ctx::~gh_ctx() {
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (done_rec) (void)hipEventSynchronize(done_ev);
+  // the device chain must not keep one of this context's events
+  DevChain& dc = dev_chain(device);
+  std::lock_guard<std::mutex> g(dc.mu);
+  if (dc.owner == this) {
+    dc.has = false;
+    dc.owner = nullptr;
+    dc.last = nullptr;
+  }
+}  // (then the parts free their memory and events, the stream last)
+
 extern "C" int gh_ctx_destroy(gh_ctx* c) {
-  if (!c) return GH_OK;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->done_rec) (void)hipEventSynchronize(c->done_ev);
-  {  // the device chain must not keep one of this context's events
-    DevChain& dc = dev_chain(c->device);
-    std::lock_guard<std::mutex> g(dc.mu);
-    if (dc.owner == c) {
-      dc.has = false;
-      dc.owner = nullptr;
-      dc.last = nullptr;
-    }
-  }
-  free_shard(c);
-  (void)hipFree(c->d_misc);
-  (void)hipFree(c->d_ga_pieces);
-  (void)hipFree(c->d_ga_out);
-  if (c->ga_ev0) (void)hipEventDestroy(c->ga_ev0);
-  if (c->ga_ev1) (void)hipEventDestroy(c->ga_ev1);
-  for (auto& e : c->pending) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
-  for (auto& e : c->pool) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
-  if (c->done) (void)hipEventDestroy(c->done);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return GH_OK;
 }
 
-static int load_common(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e, uint64_t out_cap) {
-  if (!c || !s) return fail(GH_E_ARG, "null argument");
+// Drops the loaded shard, then plans the decode of segments [b, e) of s: the code, the
+// output buffer and the decode structure with its tables.
+static int plan_shard(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e, uint64_t out_cap) {
   if (b > e || e > s->g) return fail(GH_E_ARG, "shard range outside [0, G]");
   if (e - b >= (1ull << 31))  // 32-bit segment indices in the kernels: 32 GiB of payload per shard
     return fail(GH_E_ARG, "shard of 2^31 or more segments: split the stream into more shards");
@@ -766,92 +756,104 @@ static int load_common(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e, ui
   int rc = build_canon(s->syms, s->nsyms, c->canon);
   if (rc) return rc;
   const Canon& cn = c->canon;
-  c->nseg = e - b;
-  c->seg_begin = b;
-  c->seg_end = e;
-  c->n_total = s->n;
-  c->g_total = s->g;
-  if (c->nseg > 0 && cn.nsyms == 0) return fail(GH_E_TABLE, "empty code");
+  Shard& sh = c->shard;
+  sh.nseg = e - b;
+  sh.seg_begin = b;
+  sh.seg_end = e;
+  sh.n_total = s->n;
+  sh.g_total = s->g;
+  if (sh.nseg > 0 && cn.nsyms == 0) return fail(GH_E_TABLE, "empty code");
   const uint64_t per_seg = cn.minlen ? (128 + cn.minlen - 1) / cn.minlen : 128;  // codewords per segment, at most
-  if (out_cap == 0) out_cap = std::min<uint64_t>(s->n, c->nseg * per_seg);
-  c->out_cap = out_cap;
+  if (out_cap == 0) out_cap = std::min<uint64_t>(s->n, sh.nseg * per_seg);
+  sh.out_cap = out_cap;
   GH_HIP(hipSetDevice(c->device));
-  GH_HIP(hipMalloc(&c->d_out, std::max<uint64_t>(out_cap, 16) + 64));
-  GH_HIP(hipMemset(c->d_misc, 0, 128));
-  c->epoch = 0;
-  c->ntiles = 0;
-  c->grid = 0;
-  if (c->nseg > 0) {
-    // Structure: the tile kernel for grouped codes, the wave split for every other code.
-    // GH_MODE=tile|wsplit forces one; GH_LUT_BITS sets the tile kernel's LUT width (a
-    // width below maxlen leaves the code to the wave split).
-    const char* envm = getenv("GH_MODE");
-    const bool force_tile = envm && !strcmp(envm, "tile"), force_ws = envm && !strcmp(envm, "wsplit");
-    const bool force_mt = envm && !strcmp(envm, "mtile");
-    if (envm && *envm && !force_tile && !force_ws && !force_mt) return fail(GH_E_ARG, "GH_MODE: tile, mtile or wsplit");
-    const char* envk = getenv("GH_LUT_BITS");
-    const uint32_t K = envk ? (uint32_t)std::clamp(atoi(envk), 1, 12) : cn.maxlen;
-    const bool grouped = (grouped_code(cn) || short_code(cn)) && K >= cn.maxlen;
-    if (force_tile && !grouped)
-      return fail(GH_E_ARG, "GH_MODE=tile: the code is not for the tile kernel (complete, 3..12 bits)");
-    const double avg = s->g ? (double)s->n / (double)s->g : 16.0;
-    if (grouped && !force_ws && !force_mt) {
-      if ((rc = tile_setup(c, K, avg))) return rc;
-      if (force_tile && !c->tile) return fail(GH_E_HIP, "GH_MODE=tile: the tile kernel does not fit a CU");
-    }
-    // the two-pass tile kernel: codes of 2..12-bit codewords the single-pass one does not
-    // take (cfg3's r = 0.9 codes; GH_MTILE=0 leaves them to the wave split, GH_MODE=mtile
-    // forces it)
-    const bool multi = cn.maxlen <= 16 && kraft16(cn) == 65536;
-    if (force_mt && !multi)
-      return fail(GH_E_ARG, "GH_MODE=mtile: the code is not for the two-pass tile kernel (complete, 1..16 bits)");
-    static const bool mt_on = [] {
-      const char* e = getenv("GH_MTILE");
-      return !(e && e[0] == '0');
-    }();
-    if (!c->tile && multi && (force_mt || (mt_on && !force_ws && !force_tile))) {
-      if ((rc = mtile_setup(c, avg))) return rc;
-      if (force_mt && !c->tile) return fail(GH_E_HIP, "GH_MODE=mtile: the two-pass tile kernel does not fit a CU");
-    }
-    if (!c->tile && (rc = ws_setup(c, avg))) return rc;
+  if ((rc = sh.out.alloc(std::max<uint64_t>(out_cap, 16) + 64))) return rc;
+  GH_HIP(hipMemset(c->misc.get(), 0, 128));
+  if (sh.nseg == 0) return GH_OK;
+  // Structure: the tile kernel for grouped codes, the wave split for every other code.
+  // GH_MODE=tile|wsplit forces one; GH_LUT_BITS sets the tile kernel's LUT width (a
+  // width below maxlen leaves the code to the wave split).
+  const char* envm = getenv("GH_MODE");
+  const bool force_tile = envm && !strcmp(envm, "tile"), force_ws = envm && !strcmp(envm, "wsplit");
+  const bool force_mt = envm && !strcmp(envm, "mtile");
+  if (envm && *envm && !force_tile && !force_ws && !force_mt) return fail(GH_E_ARG, "GH_MODE: tile, mtile or wsplit");
+  const char* envk = getenv("GH_LUT_BITS");
+  const uint32_t K = envk ? (uint32_t)std::clamp(atoi(envk), 1, 12) : cn.maxlen;
+  const bool grouped = (grouped_code(cn) || short_code(cn)) && K >= cn.maxlen;
+  if (force_tile && !grouped)
+    return fail(GH_E_ARG, "GH_MODE=tile: the code is not for the tile kernel (complete, 3..12 bits)");
+  const double avg = s->g ? (double)s->n / (double)s->g : 16.0;
+  const Mode& mode = c->plan.mode;
+  if (grouped && !force_ws && !force_mt) {
+    if ((rc = tile_setup(c, K, avg))) return rc;
+    if (force_tile && mode == Mode::NONE) return fail(GH_E_HIP, "GH_MODE=tile: the tile kernel does not fit a CU");
   }
-  // tile kernel: per-tile aggregates and prefixes
-  c->gran_words = c->tile ? 2ull * c->ntiles + 2 : 1;
-  GH_HIP(hipMalloc(&c->d_gran, 8ull * c->gran_words));
-  GH_HIP(hipMemset(c->d_gran, 0, 8ull * c->gran_words));
-  // start bit of local segment 0, and the gap nibble base for the rest
-  c->first_start = 0;
-  if (b > 0 && s->gap_words) {  // (gh_ctx_load_device reads it from device memory)
-    const uint64_t nib = b - 1;
-    uint32_t wv;
-    std::memcpy(&wv, (const uint8_t*)s->gap_words + 4 * (nib >> 3), 4);
-    c->first_start = (wv >> (4 * (nib & 7))) & 15u;
+  // the two-pass tile kernel: codes of 2..12-bit codewords the single-pass one does not
+  // take (cfg3's r = 0.9 codes; GH_MTILE=0 leaves them to the wave split, GH_MODE=mtile
+  // forces it)
+  const bool multi = cn.maxlen <= 16 && kraft16(cn) == 65536;
+  if (force_mt && !multi)
+    return fail(GH_E_ARG, "GH_MODE=mtile: the code is not for the two-pass tile kernel (complete, 1..16 bits)");
+  static const bool mt_on = [] {
+    const char* e = getenv("GH_MTILE");
+    return !(e && e[0] == '0');
+  }();
+  if (mode == Mode::NONE && multi && (force_mt || (mt_on && !force_ws && !force_tile))) {
+    if ((rc = mtile_setup(c, avg))) return rc;
+    if (force_mt && mode == Mode::NONE) return fail(GH_E_HIP, "GH_MODE=mtile: the two-pass tile kernel does not fit a CU");
   }
+  if (mode == Mode::NONE) return ws_setup(c, avg);
   return GH_OK;
 }
 
-extern "C" int gh_ctx_load(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e,
-                           uint64_t out_cap) {
-  int rc = load_common(c, s, b, e, out_cap);
-  if (rc) return rc;
-  if (c->nseg == 0) {
+// Where a load reads the stream's words from: host memory (gh_ctx_load) or device memory
+// (gh_ctx_load_device).
+struct ShardSource {
+  bool device;
+  const void* payload;  // payload words, the shard's first at word `skip`
+  uint64_t skip, words;
+  const void* gaps;     // the stream's whole gap array
+};
+
+// End of the last loaded segment (nseg > 0) by the decode's rule (last_segment_end): its
+// words and its start bit from the context's device copies.
+static int loaded_last_end(gh_ctx* c, uint32_t* out) {
+  const Shard& sh = c->shard;
+  uint32_t w5[5] = {};
+  GH_HIP(hipMemcpy(w5, sh.payload.get<uint32_t>() + 4 * (sh.nseg - 1), sizeof(w5), hipMemcpyDeviceToHost));  // (16 padding words follow)
+  uint32_t st = sh.first_start;
+  if (sh.nseg > 1) {
+    const uint64_t nib = sh.gap_nib0 + sh.nseg - 2;
+    uint32_t wv = 0;
+    GH_HIP(hipMemcpy(&wv, sh.gaps.get<uint32_t>() + (nib >> 3), 4, hipMemcpyDeviceToHost));
+    st = gap_nibble(&wv, nib & 7);
+  }
+  *out = last_segment_end(c->canon, w5, st);
+  return GH_OK;
+}
+
+static int load_shard(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e, uint64_t out_cap,
+                      const ShardSource& src) {
+  if (int rc = plan_shard(c, s, b, e, out_cap)) return rc;
+  Shard& sh = c->shard;
+  if (sh.nseg == 0) {
     c->loaded = true;
     return GH_OK;
   }
-  // payload words [4b, 4e+1) (clipped at W) + zero padding
-  const uint64_t w0 = 4 * b;
-  const uint64_t want = 4 * c->nseg + 1;
-  const uint64_t have = (w0 < s->w) ? std::min<uint64_t>(want, s->w - w0) : 0;
-  const uint64_t alloc_words = 4 * c->nseg + 16;
-  GH_HIP(hipMalloc(&c->d_payload, 4 * alloc_words));
+  const hipMemcpyKind kind = src.device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  // payload words [4b, 4e+1) (clipped at what the source holds) + zero padding
+  const uint64_t have = std::min<uint64_t>(4 * sh.nseg + 1, src.skip < src.words ? src.words - src.skip : 0);
+  const uint8_t* from = (const uint8_t*)src.payload + 4 * src.skip;
+  const uint64_t alloc_words = 4 * sh.nseg + 16;
+  if (int rc = sh.payload.alloc(4 * alloc_words)) return rc;
   // zero only the padding past the copied words: the copies below may run on the
   // staging set's non-blocking stream, which is not ordered against this memset
-  GH_HIP(hipMemset(c->d_payload + have, 0, 4 * (alloc_words - have)));
+  GH_HIP(hipMemset(sh.payload.get<uint32_t>() + have, 0, 4 * (alloc_words - have)));
   if (have) {
-    if (use_staged(4 * have)) {  // pinned double-buffered (concurrent across shards' threads)
-      if (int rc2 = h2d_staged(c->device, (const uint8_t*)s->payload + 4 * w0, 4 * have, c->d_payload)) return rc2;
+    if (!src.device && use_staged(4 * have)) {  // pinned double-buffered (concurrent across shards' threads)
+      if (int rc = h2d_staged(c->device, from, 4 * have, sh.payload.get())) return rc;
     } else {
-      GH_HIP(hipMemcpy(c->d_payload, (const uint8_t*)s->payload + 4 * w0, 4 * have, hipMemcpyHostToDevice));
+      GH_HIP(hipMemcpy(sh.payload.get(), from, 4 * have, kind));
     }
   }
   // gap nibbles: starts of local segments 1..nseg-1 and ends of all: global [b-1, e)
@@ -860,84 +862,65 @@ extern "C" int gh_ctx_load(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e
   const uint64_t gwords = std::max<uint64_t>(gw1, gw0 + 1) - gw0;
   const uint64_t total_gw = ceil_div(s->g, GH_GAPS_PER_WORD);
   const uint64_t gcopy = (gw0 < total_gw) ? std::min<uint64_t>(gwords, total_gw - gw0) : 0;
-  GH_HIP(hipMalloc(&c->d_gaps, 4 * (gwords + 4)));
-  GH_HIP(hipMemset(c->d_gaps, 0, 4 * (gwords + 4)));
-  if (gcopy)
-    GH_HIP(hipMemcpy(c->d_gaps, (const uint8_t*)s->gap_words + 4 * gw0, 4 * gcopy,
-                     hipMemcpyHostToDevice));
-  c->gap_nib0 = (uint32_t)(b - 8 * gw0);
-  c->ws_last_end = 0;
-  if (c->ws && e == s->g) {
-    uint32_t w5[5] = {};
-    for (uint64_t i = 0; i < 5; ++i)
-      if (4 * (e - 1) + i < s->w) std::memcpy(&w5[i], (const uint8_t*)s->payload + 4 * (4 * (e - 1) + i), 4);
-    c->ws_last_end = last_segment_end(c->canon, w5, c->nseg == 1 ? c->first_start : seg_start_host(s, e - 1));
+  if (int rc = sh.gaps.alloc(4 * (gwords + 4), true)) return rc;
+  if (gcopy) GH_HIP(hipMemcpy(sh.gaps.get(), (const uint8_t*)src.gaps + 4 * gw0, 4 * gcopy, kind));
+  sh.gap_nib0 = (uint32_t)(b - 8 * gw0);
+  // start bit of local segment 0: nibble b - 1, which the context's copy need not hold
+  if (b > 0 && src.gaps) {
+    if (src.device) {
+      uint32_t wv = 0;
+      GH_HIP(hipMemcpy(&wv, (const uint8_t*)src.gaps + 4 * ((b - 1) >> 3), 4, hipMemcpyDeviceToHost));
+      sh.first_start = gap_nibble(&wv, (b - 1) & 7);
+    } else {
+      sh.first_start = gap_nibble(src.gaps, b - 1);
+    }
   }
+  if (c->plan.mode == Mode::WSPLIT && e == s->g)
+    if (int rc = loaded_last_end(c, &sh.last_end)) return rc;
   c->loaded = true;
   return GH_OK;
+}
+
+extern "C" int gh_ctx_load(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e,
+                           uint64_t out_cap) {
+  if (!c || !s) return fail(GH_E_ARG, "null argument");
+  return load_shard(c, s, b, e, out_cap, {false, s->payload, 4 * b, s->w, s->gap_words});
 }
 
 extern "C" int gh_ctx_load_device(gh_ctx* c, const gh_stream* s, uint64_t b, uint64_t e,
                                   const uint32_t* d_payload, uint64_t d_words,
                                   const uint32_t* d_gap_words, uint64_t out_cap) {
   if (!d_payload || !d_gap_words) return fail(GH_E_ARG, "null device buffer");
-  int rc = load_common(c, s, b, e, out_cap);
-  if (rc) return rc;
-  if (c->nseg == 0) {
-    c->loaded = true;
-    return GH_OK;
-  }
-  const uint64_t want = 4 * c->nseg + 1;
-  const uint64_t have = std::min<uint64_t>(want, d_words);
-  const uint64_t alloc_words = 4 * c->nseg + 16;
-  GH_HIP(hipMalloc(&c->d_payload, 4 * alloc_words));
-  GH_HIP(hipMemset(c->d_payload + have, 0, 4 * (alloc_words - have)));
-  if (have)
-    GH_HIP(hipMemcpy(c->d_payload, d_payload, 4 * have, hipMemcpyDeviceToDevice));
-  const uint64_t gw0 = b >> 3;
-  const uint64_t gw1 = (e >= 1) ? ((e - 1) >> 3) + 1 : gw0 + 1;
-  const uint64_t gwords = std::max<uint64_t>(gw1, gw0 + 1) - gw0;
-  const uint64_t total_gw = ceil_div(s->g, GH_GAPS_PER_WORD);
-  const uint64_t gcopy = (gw0 < total_gw) ? std::min<uint64_t>(gwords, total_gw - gw0) : 0;
-  GH_HIP(hipMalloc(&c->d_gaps, 4 * (gwords + 4)));
-  GH_HIP(hipMemset(c->d_gaps, 0, 4 * (gwords + 4)));
-  if (gcopy)
-    GH_HIP(hipMemcpy(c->d_gaps, d_gap_words + gw0, 4 * gcopy, hipMemcpyDeviceToDevice));
-  c->gap_nib0 = (uint32_t)(b - 8 * gw0);
-  // first_start must come from device memory here
-  c->first_start = 0;
-  if (b > 0) {
-    const uint64_t nib = b - 1;
-    uint32_t wv = 0;
-    GH_HIP(hipMemcpy(&wv, d_gap_words + (nib >> 3), 4, hipMemcpyDeviceToHost));
-    c->first_start = (wv >> (4 * (nib & 7))) & 15u;
-  }
-  c->ws_last_end = 0;
-  if (c->ws && e == s->g) {
-    uint32_t w5[5] = {};
-    const uint64_t lw0 = 4 * (c->nseg - 1);  // local word of the last segment
-    const uint64_t nw = std::min<uint64_t>(5, have > lw0 ? have - lw0 : 0);
-    if (nw) GH_HIP(hipMemcpy(w5, c->d_payload + lw0, 4 * nw, hipMemcpyDeviceToHost));
-    uint32_t st = c->first_start;
-    if (c->nseg > 1) {
-      const uint64_t nib = e - 2;
-      uint32_t wv = 0;
-      GH_HIP(hipMemcpy(&wv, d_gap_words + (nib >> 3), 4, hipMemcpyDeviceToHost));
-      st = (wv >> (4 * (nib & 7))) & 15u;
-    }
-    c->ws_last_end = last_segment_end(c->canon, w5, st);
-  }
-  c->loaded = true;
-  return GH_OK;
+  if (!c || !s) return fail(GH_E_ARG, "null argument");
+  return load_shard(c, s, b, e, out_cap, {true, d_payload, 0, d_words, d_gap_words});
+}
+
+// The WsParams fields that every user of the resident shard fills alike (the wave split's
+// decode, the index build, the gather); each adds its own tables, outputs and status word.
+static WsParams shard_params(const gh_ctx* c) {
+  const Shard& sh = c->shard;
+  WsParams m{};
+  m.payload = sh.payload.get<uint32_t>();
+  m.gaps = sh.gaps.get<uint32_t>();
+  m.nseg = (uint32_t)sh.nseg;
+  m.gap_nib0 = sh.gap_nib0;
+  m.first_start = sh.first_start;
+  m.fb_lo = std::max<uint32_t>(c->canon.minlen, 1);
+  m.fb_hi = std::max<uint32_t>(c->canon.maxlen, m.fb_lo);
+  m.chk_pay = 4 * sh.nseg + 16;
+  m.chk_gap = sh.nseg / 8 + 4;  // (at least; the allocation holds gwords + 4)
+  return m;
 }
 
 extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
   if (!c) return fail(GH_E_ARG, "null ctx");
   if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_decode before gh_ctx_load");
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream;
   GH_HIP(hipSetDevice(c->device));
-  if (c->nseg == 0) {
-    GH_HIP(hipMemsetAsync(c->d_misc + 2, 0, 8, st));
+  const Shard& sh = c->shard;
+  Plan& p = c->plan;
+  if (sh.nseg == 0) {
+    GH_HIP(hipMemsetAsync(c->misc_at(2), 0, 8, st));
     GH_HIP(hipEventRecord(c->done, st));
     c->done_ev = c->done;
     c->done_rec = true;
@@ -945,12 +928,13 @@ extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
   }
   // Tile kernels are chained per device: wait for the previous one before the start
   // event, so a decode's time excludes its queueing behind other contexts' decodes.
+  const bool tiled = p.tiled();
   DevChain& dc = dev_chain(c->device);
   std::unique_lock<std::mutex> chain_lock(dc.mu, std::defer_lock);
-  if (c->tile) {
-    if (++c->epoch >= EPOCH_MAX) {  // granule epochs wrap: start clean
-      GH_HIP(hipMemsetAsync(c->d_gran, 0, 8ull * c->gran_words, st));
-      c->epoch = 1;
+  if (tiled) {
+    if (++p.tile.epoch >= EPOCH_MAX) {  // granule epochs wrap: start clean
+      GH_HIP(hipMemsetAsync(p.tile.gran.get(), 0, 8ull * p.tile.gran_words, st));
+      p.tile.epoch = 1;
     }
     chain_lock.lock();
     // (the context's own stream, which the last tile decode of the device ran on for this
@@ -959,114 +943,97 @@ extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
     const bool ordered = dc.owner == c && dc.last_stream == st && st == c->stream;
     if (dc.has && !ordered) GH_HIP(hipStreamWaitEvent(st, dc.last, 0));
   }
-  std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+  EventPair ev;
   if (timed) {
-    if (!c->pool.empty()) {
-      ev = c->pool.back();
-      c->pool.pop_back();
-    } else {
-      GH_HIP(hipEventCreate(&ev.first));
-      GH_HIP(hipEventCreate(&ev.second));
+    if (!c->timing.pool.empty()) {
+      ev = std::move(c->timing.pool.back());
+      c->timing.pool.pop_back();
+    } else if (int rc = ev.create()) {
+      return rc;
     }
-    if (!c->tile) GH_HIP(hipEventRecord(ev.first, st));  // (tile: in the dispatch itself, below)
+    if (!tiled) GH_HIP(hipEventRecord(ev.a, st));  // (tile: in the dispatch itself, below)
   }
-  if (c->ws) {
-    WsParams m{};
-    m.payload = c->d_payload;
-    m.gaps = c->d_gaps;
-    m.seg_cnt = c->d_seg_cnt;
-    m.rng_tot = c->d_rng_tot;
-    m.rng_off = c->d_rng_off;
-    m.out = c->d_out;
-    m.junk = c->d_ws_junk;
-    m.status = c->d_misc + 1;
-    m.total = (unsigned long long*)(c->d_misc + 2);
-    m.out_cap = c->out_cap;
-    m.nseg = (uint32_t)c->nseg;
-    m.nsb = c->ws_nblocks;
-    m.nranges = c->ws_nranges;
-    m.chk_pay = 4 * c->nseg + 16;
-    m.chk_gap = c->nseg / 8 + 4;  // (at least; the allocation holds gwords + 4)
-    m.chk_out = std::max<uint64_t>(c->out_cap, 16) + 64;
-    m.gap_nib0 = c->gap_nib0;
-    m.first_start = c->first_start;
-    m.stage_bytes = c->stage_bytes;
-    m.last_end = c->ws_last_end;
-    m.fb = c->d_fb;
-    m.fb_lo = std::max<uint32_t>(c->canon.minlen, 1);
-    m.fb_hi = std::max<uint32_t>(c->canon.maxlen, m.fb_lo);
-    static thread_local WsParams wc, ww;
-    static thread_local void* ac[1];
-    static thread_local void* aw[1];
-    wc = m;
-    wc.lut = (const uint2*)c->d_ws_lut_c;
-    wc.kbits = c->ws_kc;
-    wc.lut_bytes = (uint32_t)(4u << c->ws_kc);
-    wc.lgc = c->ws_lgc;
-    ww = m;
-    ww.lut = (const uint2*)c->d_ws_lut_w;
-    ww.kbits = c->ws_k;
-    ww.lut_bytes = (uint32_t)c->lut_bytes;
-    ac[0] = &wc;
-    aw[0] = &ww;
-    const WsKernels wk = ws_kernels(c->ws_kc, c->ws_k, c->ws_ns, c->ws_fb);
-    GH_HIP(hipLaunchKernel(wk.count.fn, dim3(c->ws_grid_c), dim3(WS_TBC), ac, c->lds_count, st));
+  if (p.mode == Mode::WSPLIT) {
+    const WsPlan& w = p.ws;
+    WsParams m = shard_params(c);
+    m.seg_cnt = w.seg_cnt.get<uint8_t>();
+    m.rng_tot = w.rng_tot.get<unsigned long long>();
+    m.rng_off = w.rng_off.get<unsigned long long>();
+    m.out = sh.out.get<uint8_t>();
+    m.junk = w.junk.get<uint4>();
+    m.status = c->misc_at(1);
+    m.total = (unsigned long long*)c->misc_at(2);
+    m.out_cap = sh.out_cap;
+    m.nsb = w.nblocks;
+    m.nranges = w.nranges;
+    m.chk_out = std::max<uint64_t>(sh.out_cap, 16) + 64;
+    m.stage_bytes = w.stage_bytes;
+    m.last_end = sh.last_end;
+    m.fb = w.fb.get<uint32_t>();
+    WsParams wc = m, ww = m;  // the count and scan kernels' / the write kernel's
+    wc.lut = w.lut_c.get<uint2>();
+    wc.kbits = w.kc;
+    wc.lut_bytes = (uint32_t)(4u << w.kc);
+    wc.lgc = w.lgc;
+    ww.lut = w.lut_w.get<uint2>();
+    ww.kbits = w.k;
+    ww.lut_bytes = w.lut_bytes;
+    void* ac[1] = {&wc};
+    void* aw[1] = {&ww};
+    GH_HIP(hipLaunchKernel(w.count.fn, dim3(w.grid_c), dim3(WS_TBC), ac, w.lds_count, st));
     GH_HIP(hipLaunchKernel((const void*)gh_ws_scan_kernel, dim3(1), dim3(WS_SCAN_TB), ac, 0, st));
-    GH_HIP(hipLaunchKernel(wk.write.fn, dim3(c->grid), dim3(WS_TB), aw, c->lds, st));
+    GH_HIP(hipLaunchKernel(p.kern.fn, dim3(p.grid), dim3(p.block), aw, p.lds, st));
   } else {
+    const TilePlan& tp = p.tile;
+    unsigned long long* gran = tp.gran.get<unsigned long long>();
     TileParams t{};
-    t.payload = c->d_payload;
-    t.gaps = c->d_gaps;
-    t.lut = c->d_lut_t;
-    t.out = c->d_out;
-    t.granules = c->d_gran;
-    t.prefix = c->d_gran + c->ntiles;
-    t.status = c->d_misc + 1;
-    t.total = (unsigned long long*)(c->d_misc + 2);
-    t.stats = (unsigned long long*)(c->d_misc + 4);
-    t.tickets = (unsigned int*)(c->d_gran + 2ull * c->ntiles);  // the two spare granule words
-    t.out_cap = c->out_cap;
-    t.nseg = c->nseg;
-    t.gap_nib0 = c->gap_nib0;
-    t.first_start = c->first_start;
-    t.ntiles = c->ntiles;
-    t.kbits = c->tile_k;
-    t.lgr = c->lgr;
-    t.epoch = c->epoch;
-    t.lut_bytes = (uint32_t)c->lut_bytes;
-    t.stage_bytes = c->stage_bytes;
-    t.kbits_c = c->mt_kc;
+    t.payload = sh.payload.get<uint32_t>();
+    t.gaps = sh.gaps.get<uint32_t>();
+    t.lut = tp.lut.get<uint32_t>();
+    t.out = sh.out.get<uint8_t>();
+    t.granules = gran;
+    t.prefix = gran + tp.ntiles;
+    t.status = c->misc_at(1);
+    t.total = (unsigned long long*)c->misc_at(2);
+    t.stats = (unsigned long long*)c->misc_at(4);
+    t.tickets = (unsigned int*)(gran + 2ull * tp.ntiles);  // the two spare granule words
+    t.out_cap = sh.out_cap;
+    t.nseg = sh.nseg;
+    t.gap_nib0 = sh.gap_nib0;
+    t.first_start = sh.first_start;
+    t.ntiles = tp.ntiles;
+    t.kbits = tp.kbits;
+    t.lgr = p.mode == Mode::MTILE ? tp.clut_lgr : tp.lut_lgr;
+    t.epoch = tp.epoch;
+    t.lut_bytes = tp.lut_bytes;
+    t.stage_bytes = tp.stage_bytes;
+    t.kbits_c = tp.kbits_c;
     t.fb_hi = c->canon.maxlen;
-    t.stamps = c->d_stamps;
-    t.tstamps = c->d_stamps ? (unsigned long long*)((uint8_t*)c->d_stamps + 32ull * c->grid * 2 * 128) : nullptr;
-    t.idle_block = c->idle_block;
-    const void* kern = (c->mtile ? mtile_kernel_for(c->mt_gl, c->mt_ns, c->mt_fb) : tile_kernel_for(c->tile_minl, c->tile_g)).fn;
-    static thread_local void* ta[1];
-    static thread_local TileParams tp;
-    tp = t;
-    ta[0] = &tp;
+    t.stamps = tp.stamps.get<uint4>();
+    t.tstamps = tp.stamps ? (unsigned long long*)(tp.stamps.get<uint8_t>() + 32ull * p.grid * 2 * 128) : nullptr;
+    t.idle_block = tp.idle_block;
+    void* ta[1] = {&t};
     // timed: the start and stop timestamps are taken by the dispatch packet itself
     // (hipExtLaunchKernel), not by marker packets around it, so back-to-back decodes
     // have no extra packets between them
     if (timed)
-      GH_HIP(hipExtLaunchKernel(kern, dim3(c->grid), dim3(c->mtile ? MT_TB : TILE_TB), ta, c->lds, st, ev.first,
-                                ev.second, 0));
+      GH_HIP(hipExtLaunchKernel(p.kern.fn, dim3(p.grid), dim3(p.block), ta, p.lds, st, ev.a, ev.b, 0));
     else
-      GH_HIP(hipLaunchKernel(kern, dim3(c->grid), dim3(c->mtile ? MT_TB : TILE_TB), ta, c->lds, st));
+      GH_HIP(hipLaunchKernel(p.kern.fn, dim3(p.grid), dim3(p.block), ta, p.lds, st));
   }
   GH_HIP(hipGetLastError());
   // one event after the kernel(s): the timed decode's end event, or `done` (each marker
   // between back-to-back decodes costs the GPU microseconds)
   if (timed) {
-    if (!c->tile) GH_HIP(hipEventRecord(ev.second, st));
-    c->pending.push_back(ev);
-    c->done_ev = ev.second;
+    if (!tiled) GH_HIP(hipEventRecord(ev.b, st));
+    c->done_ev = ev.b;
+    c->timing.pending.push_back(std::move(ev));
   } else {
     GH_HIP(hipEventRecord(c->done, st));
     c->done_ev = c->done;
   }
   c->done_rec = true;
-  if (c->tile) {  // the device chain's last decode (chain_lock held)
+  if (tiled) {  // the device chain's last decode (chain_lock held)
     dc.last = c->done_ev;
     dc.owner = c;
     dc.has = true;
@@ -1084,22 +1051,24 @@ static int wait_decode(gh_ctx* c) {
 
 extern "C" int gh_ctx_report(gh_ctx* c, void* hip_stream, gh_report* rep) {
   if (!c) return fail(GH_E_ARG, "null ctx");
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream;
   GH_HIP(hipSetDevice(c->device));
   GH_HIP(hipStreamSynchronize(st));
   if (int rc = wait_decode(c)) return rc;
-  for (auto& e : c->pending) {
+  Timing& tm = c->timing;
+  for (EventPair& e : tm.pending) {
     float ms = 0;
-    GH_HIP(hipEventElapsedTime(&ms, e.first, e.second));
-    c->acc_ms += ms;
-    c->nlaunch++;
-    c->pool.push_back(e);
+    if (int rc = e.elapsed(&ms)) return rc;
+    tm.acc_ms += ms;
+    tm.nlaunch++;
+    tm.pool.push_back(std::move(e));
   }
-  c->pending.clear();
-  if (GH_TILE_STAMPS && c->d_stamps) {  // diagnostic builds: the last decode's phase deltas
+  tm.pending.clear();
+  const Plan& p = c->plan;
+  if (GH_TILE_STAMPS && p.tile.stamps) {  // diagnostic builds: the last decode's phase deltas
     if (const char* f = getenv("GH_STAMPS_OUT")) {
-      std::vector<uint8_t> h(32ull * c->grid * 2 * 128 + 8ull * (3ull * c->ntiles + 64 + 4 * 1024 + 4ull * c->grid));
-      GH_HIP(hipMemcpy(h.data(), c->d_stamps, h.size(), hipMemcpyDeviceToHost));
+      std::vector<uint8_t> h(p.tile.stamps.capacity());
+      GH_HIP(hipMemcpy(h.data(), p.tile.stamps.get(), h.size(), hipMemcpyDeviceToHost));
       if (FILE* fp = fopen(f, "wb")) {
         fwrite(h.data(), 1, h.size(), fp);
         fclose(fp);
@@ -1107,111 +1076,75 @@ extern "C" int gh_ctx_report(gh_ctx* c, void* hip_stream, gh_report* rep) {
     }
   }
   unsigned int misc[6] = {};
-  GH_HIP(hipMemcpy(misc, c->d_misc, sizeof(misc), hipMemcpyDeviceToHost));
+  GH_HIP(hipMemcpy(misc, c->misc.get(), sizeof(misc), hipMemcpyDeviceToHost));
   if (rep) {
     std::memset(rep, 0, sizeof(*rep));
     uint64_t tot;
     std::memcpy(&tot, misc + 2, 8);
     rep->symbols = tot;
-    rep->out_bytes = std::min<uint64_t>(tot, c->out_cap);
+    rep->out_bytes = std::min<uint64_t>(tot, c->shard.out_cap);
     rep->status = misc[1];
-    rep->lut_bits = c->tile ? c->tile_k : c->ws_k;
-    rep->grid = c->grid;
-    rep->tiles = c->ntiles;
-    rep->mode = c->mtile ? GH_MODE_MTILE : c->tile ? GH_MODE_TILE : GH_MODE_SPLIT;
+    rep->lut_bits = p.tiled() ? p.tile.kbits : p.ws.k;
+    rep->grid = p.grid;
+    rep->tiles = p.tiled() ? p.tile.ntiles : p.ws.nblocks;  // tiles / wave blocks
+    rep->mode = p.mode == Mode::MTILE ? GH_MODE_MTILE : p.mode == Mode::TILE ? GH_MODE_TILE : GH_MODE_SPLIT;
     std::memcpy(&rep->slow_lookbacks, misc + 4, 8);
-    rep->path = c->mtile ? GH_PATH_MULTI_TILE : c->tile ? GH_PATH_GROUPED : GH_PATH_MULTI_WAVE;
-    rep->launches = c->nlaunch;
-    rep->kernel_ms = c->nlaunch ? (float)(c->acc_ms / c->nlaunch) : 0.f;
+    rep->path = p.mode == Mode::MTILE ? GH_PATH_MULTI_TILE : p.mode == Mode::TILE ? GH_PATH_GROUPED : GH_PATH_MULTI_WAVE;
+    rep->launches = tm.nlaunch;
+    rep->kernel_ms = tm.nlaunch ? (float)(tm.acc_ms / tm.nlaunch) : 0.f;
   }
   return GH_OK;
 }
 
 extern "C" int gh_ctx_reset_timing(gh_ctx* c) {
   if (!c) return fail(GH_E_ARG, "null ctx");
-  c->acc_ms = 0;
-  c->nlaunch = 0;
+  c->timing.acc_ms = 0;
+  c->timing.nlaunch = 0;
   return GH_OK;
 }
 
 extern "C" int gh_ctx_download(gh_ctx* c, uint64_t off, uint8_t* dst, uint64_t nbytes) {
   if (!c || (nbytes && !dst)) return fail(GH_E_ARG, "null argument");
-  if (off + nbytes > c->out_cap) return fail(GH_E_ARG, "download beyond the output capacity");
+  if (off + nbytes > c->shard.out_cap) return fail(GH_E_ARG, "download beyond the output capacity");
   if (!nbytes) return GH_OK;
   GH_HIP(hipSetDevice(c->device));
   if (int rc = wait_decode(c)) return rc;
-  if (use_staged(nbytes)) return d2h_staged(c->device, c->d_out + off, nbytes, dst);
-  GH_HIP(hipMemcpy(dst, c->d_out + off, nbytes, hipMemcpyDeviceToHost));
+  const uint8_t* src = c->shard.out.get<uint8_t>() + off;
+  if (use_staged(nbytes)) return d2h_staged(c->device, src, nbytes, dst);
+  GH_HIP(hipMemcpy(dst, src, nbytes, hipMemcpyDeviceToHost));
   return GH_OK;
 }
 
 extern "C" int gh_ctx_output(gh_ctx* c, void** d_out, uint64_t* cap) {
   if (!c || !d_out) return fail(GH_E_ARG, "null argument");
-  *d_out = c->d_out;
-  if (cap) *cap = c->out_cap;
+  *d_out = c->shard.out.get();
+  if (cap) *cap = c->shard.out_cap;
   return GH_OK;
 }
 
 extern "C" int gh_ctx_copy_output(gh_ctx* c, uint64_t off, void* dst, uint64_t nbytes,
                                   void* hip_stream) {
   if (!c || (nbytes && !dst)) return fail(GH_E_ARG, "null argument");
-  if (off + nbytes > c->out_cap) return fail(GH_E_ARG, "copy beyond the output capacity");
+  if (off + nbytes > c->shard.out_cap) return fail(GH_E_ARG, "copy beyond the output capacity");
   if (!nbytes) return GH_OK;
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream;
   GH_HIP(hipSetDevice(c->device));
   if (c->done_rec) GH_HIP(hipStreamWaitEvent(st, c->done_ev, 0));  // after the last decode
-  GH_HIP(hipMemcpyAsync(dst, c->d_out + off, nbytes, hipMemcpyDefault, st));
+  GH_HIP(hipMemcpyAsync(dst, c->shard.out.get<uint8_t>() + off, nbytes, hipMemcpyDefault, st));
   return GH_OK;
 }
 
 // ---- seek index (gh_index.hip) ------------------------------------------------------
-// The index kernels are not decode shapes: no load picks them, gh_kernel_shapes does not
-// list them.  By the count table's width and the fallback, as ws_kernels' count kernel.
-static const void* index_kernel_for(uint32_t kc, bool fb) {
-  if (fb) return (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 2, true>;
-  const int gl = lookups_per_shift(kc);
-  return gl >= 4 ? (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 4, false>
-       : gl == 3 ? (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 3, false>
-                 : (const void*)gh_index_count_kernel<IDX_U, IDX_TB, 2, false>;
-}
-
-// End of the last loaded segment (nseg > 0) by the decode's rule (last_segment_end): its
-// words and its start bit from the device copies, as gh_ctx_load_device reads them.
-static int loaded_last_end(gh_ctx* c, uint32_t* out) {
-  uint32_t w5[5] = {};
-  GH_HIP(hipMemcpy(w5, c->d_payload + 4 * (c->nseg - 1), sizeof(w5), hipMemcpyDeviceToHost));  // (16 padding words follow)
-  uint32_t st = c->first_start;
-  if (c->nseg > 1) {
-    const uint64_t nib = c->gap_nib0 + c->nseg - 2;
-    uint32_t wv = 0;
-    GH_HIP(hipMemcpy(&wv, c->d_gaps + (nib >> 3), 4, hipMemcpyDeviceToHost));
-    st = (wv >> (4 * (nib & 7))) & 15u;
-  }
-  *out = last_segment_end(c->canon, w5, st);
-  return GH_OK;
-}
-
-namespace {
-struct DevMem {  // device memory of one gh_ctx_build_index call
-  void* p = nullptr;
-  ~DevMem() { if (p) (void)hipFree(p); }
-};
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-}  // namespace
-
+// The index and gather kernels are not decode shapes: no load picks them, gh_kernel_shapes
+// does not list them.  Both go by their count table's width and the fallback.
 extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, uint64_t out_len,
                                   uint64_t* symbols, float* kernel_ms) {
   if (!c || !out) return fail(GH_E_ARG, "null argument");
   if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_build_index before gh_ctx_load");
-  const uint64_t bytes = gh_index_bytes(c->g_total, log2_stride);
+  const Shard& sh = c->shard;
+  const uint64_t bytes = gh_index_bytes(sh.g_total, log2_stride);
   if (bytes == 0) return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
-  if (c->seg_begin != 0 || c->seg_end != c->g_total)
+  if (sh.seg_begin != 0 || sh.seg_end != sh.g_total)
     return fail(GH_E_ARG, "gh_ctx_build_index: the load must cover segments [0, G)");
   if (out_len < bytes) return fail(GH_E_SMALL, "index buffer smaller than gh_index_bytes");
   const uint64_t nblocks = (bytes - 40) / 8 - 1;
@@ -1219,49 +1152,32 @@ extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, ui
   float ms = 0;
   GH_HIP(hipSetDevice(c->device));
   if (int rc = wait_decode(c)) return rc;
-  if (c->nseg > 0) {
+  if (sh.nseg > 0) {
     const Canon& cn = c->canon;
     // The context's decode mode may be a tile kernel, which keeps no count table on the
     // device: the build makes its own table and fallback tables, and frees them.
     const uint32_t kc = ws_count_bits(cn);
     const bool fb = kraft16(cn) != 65536 || cn.maxlen > kc;
-    std::vector<uint32_t> lc;
-    count_lut(cn, kc, &lc);
-    uint32_t fbt[FB_WORDS];
-    fallback_tables(cn, fbt);
-    DevMem d_lut, d_fb, d_cnt, d_status;
-    GH_HIP(hipMalloc(&d_lut.p, 4ull << kc));
-    GH_HIP(hipMemcpy(d_lut.p, lc.data(), 4ull << kc, hipMemcpyHostToDevice));
-    GH_HIP(hipMalloc(&d_fb.p, sizeof(fbt)));
-    GH_HIP(hipMemcpy(d_fb.p, fbt, sizeof(fbt), hipMemcpyHostToDevice));
-    GH_HIP(hipMalloc(&d_cnt.p, 8 * nblocks));
-    GH_HIP(hipMemset(d_cnt.p, 0, 8 * nblocks));
-    GH_HIP(hipMalloc(&d_status.p, 16));
-    GH_HIP(hipMemset(d_status.p, 0, 16));
-    uint32_t last_end = 0;
-    if (int rc = loaded_last_end(c, &last_end)) return rc;
+    DevBuf d_lut, d_fb, d_cnt, d_status;
+    if (int rc = upload_count_tables(cn, kc, d_lut, d_fb)) return rc;
+    if (int rc = d_cnt.alloc(8 * nblocks, true)) return rc;
+    if (int rc = d_status.alloc(16, true)) return rc;
     IdxParams ip{};
-    ip.w.payload = c->d_payload;
-    ip.w.gaps = c->d_gaps;
-    ip.w.lut = (const uint2*)d_lut.p;
-    ip.w.status = (unsigned int*)d_status.p;
-    ip.w.nseg = (uint32_t)c->nseg;
-    ip.w.gap_nib0 = c->gap_nib0;
-    ip.w.first_start = c->first_start;
+    ip.w = shard_params(c);
+    if (int rc = loaded_last_end(c, &ip.w.last_end)) return rc;
+    ip.w.lut = d_lut.get<uint2>();
+    ip.w.status = d_status.get<unsigned int>();
     ip.w.kbits = kc;
     ip.w.lut_bytes = (uint32_t)(4u << kc);
-    ip.w.last_end = last_end;
-    ip.w.fb = (const uint32_t*)d_fb.p;
-    ip.w.fb_lo = std::max<uint32_t>(cn.minlen, 1);
-    ip.w.fb_hi = std::max<uint32_t>(cn.maxlen, ip.w.fb_lo);
-    ip.w.chk_pay = 4 * c->nseg + 16;
-    ip.w.chk_gap = c->nseg / 8 + 4;
-    ip.counts = (unsigned long long*)d_cnt.p;
+    ip.w.fb = d_fb.get<uint32_t>();
+    ip.counts = d_cnt.get<unsigned long long>();
     ip.nblocks = (uint32_t)nblocks;
     ip.log2_stride = log2_stride;
-    const void* kern = index_kernel_for(kc, fb);
+    const void* kern = kernel_by_width(kc, fb, [](auto gl, auto f) {
+      return (const void*)gh_index_count_kernel<IDX_U, IDX_TB, decltype(gl)::value, decltype(f)::value>;
+    });
     const size_t lds = std::max<size_t>(4ull << kc, 64) + (fb ? FB_BYTES : 0);
-    if (lds > 64 * 1024) GH_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = allow_lds(kern, lds)) return rc;
     int pc = 0;
     GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern, IDX_TB, lds));
     if (pc < 1) return fail(GH_E_HIP, "the index kernel does not fit on a CU");
@@ -1270,8 +1186,7 @@ extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, ui
     if (const char* eg = getenv("GH_INDEX_GRID"))  // tests: few workgroups, many index blocks per wave
       grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
     EventPair ev;
-    GH_HIP(hipEventCreate(&ev.a));
-    GH_HIP(hipEventCreate(&ev.b));
+    if (int rc = ev.create()) return rc;
     void* args[1] = {&ip};
     {
       // Joins the device's decode chain: a persistent tile kernel assumes its whole grid
@@ -1287,10 +1202,10 @@ extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, ui
       GH_HIP(hipEventRecord(ev.b, c->stream));
       GH_HIP(hipStreamSynchronize(c->stream));
     }
-    GH_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (int rc = ev.elapsed(&ms)) return rc;
     unsigned int status = 0;
-    GH_HIP(hipMemcpy(&status, d_status.p, 4, hipMemcpyDeviceToHost));
-    GH_HIP(hipMemcpy(counts.data(), d_cnt.p, 8 * nblocks, hipMemcpyDeviceToHost));
+    GH_HIP(hipMemcpy(&status, d_status.get(), 4, hipMemcpyDeviceToHost));
+    GH_HIP(hipMemcpy(counts.data(), d_cnt.get(), 8 * nblocks, hipMemcpyDeviceToHost));
     if (status & GH_ST_LAYOUT) return fail(GH_E_HIP, "index kernel: LDS layout assumption violated");
     if (status & GH_ST_BADCODE) return fail(GH_E_CORRUPT, "invalid code in stream");
   }
@@ -1299,70 +1214,43 @@ extern "C" int gh_ctx_build_index(gh_ctx* c, uint32_t log2_stride, void* out, ui
   auto put64 = [&](size_t at, uint64_t v) { std::memcpy(o + at, &v, 8); };
   uint64_t run = 0;
   for (uint64_t k = 0; k < nblocks; ++k) {
-    if (run > c->n_total) return fail(GH_E_CORRUPT, "stream holds more than N symbols before its last segments");
+    if (run > sh.n_total) return fail(GH_E_CORRUPT, "stream holds more than N symbols before its last segments");
     put64(40 + 8 * k, run);
     run += counts[k];
   }
-  if (run < c->n_total) return fail(GH_E_CORRUPT, "stream holds fewer than N symbols");
-  put64(40 + 8 * nblocks, c->n_total);
-  put64(0, GH_INDEX_MAGIC);
-  const uint32_t hdr[2] = {log2_stride, 0u};
-  std::memcpy(o + 8, hdr, 8);
-  put64(16, c->n_total);
-  put64(24, c->g_total);
-  put64(32, nblocks + 1);
+  if (run < sh.n_total) return fail(GH_E_CORRUPT, "stream holds fewer than N symbols");
+  put64(40 + 8 * nblocks, sh.n_total);
+  index_header(log2_stride, sh.n_total, sh.g_total, nblocks + 1, o);
   if (symbols) *symbols = run;
   if (kernel_ms) *kernel_ms = ms;
   return GH_OK;
 }
 
 // ---- batched range gather (gh_gather.hip) -------------------------------------------
-// Not decode shapes either.  By the count table's width and the fallback, as
-// index_kernel_for.
-static const void* gather_kernel_for(uint32_t kc, bool fb) {
-  if (fb) return (const void*)gh_gather_kernel<GA_U, GA_TB, 2, true>;
-  const int gl = lookups_per_shift(kc);
-  return gl >= 4 ? (const void*)gh_gather_kernel<GA_U, GA_TB, 4, false>
-       : gl == 3 ? (const void*)gh_gather_kernel<GA_U, GA_TB, 3, false>
-                 : (const void*)gh_gather_kernel<GA_U, GA_TB, 2, false>;
-}
-
 // The gather's tables, built on the context's first gather after a load (free_shard drops
 // them): the count table of the index build (ws_count_bits), a single-symbol table of at
 // most 12 bits, the fallback tables and the end of the stream's last segment.
 static int gather_setup(gh_ctx* c) {
   const Canon& cn = c->canon;
-  const uint32_t kc = ws_count_bits(cn);
-  const uint32_t ks = std::min<uint32_t>(std::max<uint32_t>(cn.maxlen, 2), 12);
-  const bool fb = kraft16(cn) != 65536 || cn.maxlen > std::min(kc, ks);
-  {
-    std::vector<uint32_t> lc;
-    count_lut(cn, kc, &lc);
-    const std::vector<uint32_t> ls = single_lut(cn, ks);
-    uint32_t fbt[FB_WORDS];
-    fallback_tables(cn, fbt);
-    GH_HIP(hipMalloc(&c->d_ga_lut_c, 4ull << kc));
-    GH_HIP(hipMemcpy(c->d_ga_lut_c, lc.data(), 4ull << kc, hipMemcpyHostToDevice));
-    GH_HIP(hipMalloc(&c->d_ga_lut_s, 4ull << ks));
-    GH_HIP(hipMemcpy(c->d_ga_lut_s, ls.data(), 4ull << ks, hipMemcpyHostToDevice));
-    GH_HIP(hipMalloc(&c->d_ga_fb, sizeof(fbt)));
-    GH_HIP(hipMemcpy(c->d_ga_fb, fbt, sizeof(fbt), hipMemcpyHostToDevice));
-  }
-  if (int rc = loaded_last_end(c, &c->ga_last_end)) return rc;
-  c->ga_kc = kc;
-  c->ga_ks = ks;
-  c->ga_fb = fb;
-  c->ga_kern = gather_kernel_for(kc, fb);
-  c->ga_lds = (4ull << kc) + (4ull << ks) + (fb ? FB_BYTES : 0);
-  if (c->ga_lds > 64 * 1024)
-    GH_HIP(hipFuncSetAttribute(c->ga_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->ga_lds));
+  GatherTables t;
+  t.kc = ws_count_bits(cn);
+  t.ks = std::min<uint32_t>(std::max<uint32_t>(cn.maxlen, 2), 12);
+  const bool fb = kraft16(cn) != 65536 || cn.maxlen > std::min(t.kc, t.ks);
+  if (int rc = upload_count_tables(cn, t.kc, t.lut_c, t.fb)) return rc;
+  if (int rc = t.lut_s.upload(single_lut(cn, t.ks).data(), 4ull << t.ks)) return rc;
+  if (int rc = loaded_last_end(c, &t.last_end)) return rc;
+  t.kern = kernel_by_width(t.kc, fb, [](auto gl, auto f) {
+    return (const void*)gh_gather_kernel<GA_U, GA_TB, decltype(gl)::value, decltype(f)::value>;
+  });
+  t.lds = (4ull << t.kc) + (4ull << t.ks) + (fb ? FB_BYTES : 0);
+  if (int rc = allow_lds(t.kern, t.lds)) return rc;
   int pc = 0;
-  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, c->ga_kern, GA_TB, c->ga_lds));
+  GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, t.kern, GA_TB, t.lds));
   if (pc < 1) return fail(GH_E_HIP, "the gather kernel does not fit on a CU");
-  c->ga_wgs = (uint32_t)pc * (uint32_t)c->num_cu;
-  if (!c->ga_ev0) GH_HIP(hipEventCreate(&c->ga_ev0));
-  if (!c->ga_ev1) GH_HIP(hipEventCreate(&c->ga_ev1));
-  c->ga_ready = true;
+  t.wgs = (uint32_t)pc * (uint32_t)c->num_cu;
+  if (int rc = c->gather.ev.create()) return rc;
+  t.ready = true;
+  c->gather.tab = std::move(t);
   return GH_OK;
 }
 
@@ -1371,66 +1259,50 @@ extern "C" int gh_ctx_gather(gh_ctx* c, const gh_index* ix, const gh_range* rang
   if (!c || !ix || !ix->offsets || (nranges && !ranges)) return fail(GH_E_ARG, "null argument");
   if (kernel_ms) *kernel_ms = 0;
   if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_gather before gh_ctx_load");
-  if (c->seg_begin != 0 || c->seg_end != c->g_total)
+  const Shard& sh = c->shard;
+  Gather& ga = c->gather;
+  if (sh.seg_begin != 0 || sh.seg_end != sh.g_total)
     return fail(GH_E_ARG, "gh_ctx_gather: the load must cover segments [0, G)");
-  if (ix->n != c->n_total || ix->g != c->g_total) return fail(GH_E_ARG, "gh_ctx_gather: the index is another stream's (N, G)");
+  if (ix->n != sh.n_total || ix->g != sh.g_total) return fail(GH_E_ARG, "gh_ctx_gather: the index is another stream's (N, G)");
   const uint64_t ibytes = gh_index_bytes(ix->g, ix->log2_stride);
   if (ibytes == 0 || ix->nentries != (ibytes - 40) / 8) return fail(GH_E_ARG, "gh_ctx_gather: malformed index");
   // plan into the context's piece vector (sized by a first pass)
   uint64_t np = 0, total = 0;
-  int rc = gh_gather_plan(ix, ranges, nranges, c->ga_pieces.data(), c->ga_pieces.size(), &np, &total);
+  int rc = gh_gather_plan(ix, ranges, nranges, ga.pieces.data(), ga.pieces.size(), &np, &total);
   if (rc == GH_E_SMALL) {
-    c->ga_pieces.resize(np);
-    rc = gh_gather_plan(ix, ranges, nranges, c->ga_pieces.data(), c->ga_pieces.size(), &np, &total);
+    ga.pieces.resize(np);
+    rc = gh_gather_plan(ix, ranges, nranges, ga.pieces.data(), ga.pieces.size(), &np, &total);
   }
   if (rc) return rc;
   if (total > dst_len) return fail(GH_E_SMALL, "gather destination smaller than the ranges' bytes");
   if (total == 0) return GH_OK;  // (no range, only empty ranges, or an empty stream)
   if (!dst) return fail(GH_E_ARG, "null argument");
   if (np >= (1ull << 31)) return fail(GH_E_ARG, "gh_ctx_gather: 2^31 or more pieces in one batch");
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream;
   GH_HIP(hipSetDevice(c->device));
   if (int rc2 = wait_decode(c)) return rc2;
-  if (!c->ga_ready)
+  if (!ga.tab.ready)
     if (int rc2 = gather_setup(c)) return rc2;
-  if (np > c->ga_pieces_cap) {
-    (void)hipFree(c->d_ga_pieces);
-    c->d_ga_pieces = nullptr;
-    c->ga_pieces_cap = 0;
-    GH_HIP(hipMalloc(&c->d_ga_pieces, np * sizeof(gh_gather_piece)));
-    c->ga_pieces_cap = np;
-  }
-  if (total > c->ga_out_cap) {
-    (void)hipFree(c->d_ga_out);
-    c->d_ga_out = nullptr;
-    c->ga_out_cap = 0;
-    GH_HIP(hipMalloc(&c->d_ga_out, total));
-    c->ga_out_cap = total;
-  }
+  const GatherTables& t = ga.tab;
+  if (int rc2 = ga.d_pieces.reserve(np * sizeof(gh_gather_piece))) return rc2;
+  if (int rc2 = ga.d_out.reserve(total)) return rc2;
+  unsigned int* d_status = c->misc_at(16);  // (a word of its own: [1] is the decode's)
   GatherParams gp{};
-  gp.w.payload = c->d_payload;
-  gp.w.gaps = c->d_gaps;
-  gp.w.lut = (const uint2*)c->d_ga_lut_c;
-  gp.w.out = c->d_ga_out;
-  gp.w.status = c->d_misc + 16;  // (a word of its own: [1] is the decode's)
-  gp.w.nseg = (uint32_t)c->nseg;
-  gp.w.gap_nib0 = c->gap_nib0;
-  gp.w.first_start = c->first_start;
-  gp.w.kbits = c->ga_kc;
-  gp.w.lut_bytes = (uint32_t)(4u << c->ga_kc);
-  gp.w.last_end = c->ga_last_end;
-  gp.w.fb = c->d_ga_fb;
-  gp.w.fb_lo = std::max<uint32_t>(c->canon.minlen, 1);
-  gp.w.fb_hi = std::max<uint32_t>(c->canon.maxlen, gp.w.fb_lo);
-  gp.w.chk_pay = 4 * c->nseg + 16;
-  gp.w.chk_gap = c->nseg / 8 + 4;
-  gp.pieces = c->d_ga_pieces;
-  gp.sym_lut = c->d_ga_lut_s;
+  gp.w = shard_params(c);
+  gp.w.lut = t.lut_c.get<uint2>();
+  gp.w.out = ga.d_out.get<uint8_t>();
+  gp.w.status = d_status;
+  gp.w.kbits = t.kc;
+  gp.w.lut_bytes = (uint32_t)(4u << t.kc);
+  gp.w.last_end = t.last_end;
+  gp.w.fb = t.fb.get<uint32_t>();
+  gp.pieces = ga.d_pieces.get<gh_gather_piece>();
+  gp.sym_lut = t.lut_s.get<uint32_t>();
   gp.npieces = (uint32_t)np;
   gp.log2_stride = ix->log2_stride;
-  gp.sym_bits = c->ga_ks;
+  gp.sym_bits = t.ks;
   // every workgroup that has a piece, at most what the device holds at once
-  uint32_t grid = (uint32_t)std::min<uint64_t>(c->ga_wgs, ceil_div(np, (uint64_t)(GA_TB / 64)));
+  uint32_t grid = (uint32_t)std::min<uint64_t>(t.wgs, ceil_div(np, (uint64_t)(GA_TB / 64)));
   if (const char* eg = getenv("GH_GATHER_GRID"))  // tests: few workgroups, many pieces per wave
     grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
   void* args[1] = {&gp};
@@ -1442,17 +1314,17 @@ extern "C" int gh_ctx_gather(gh_ctx* c, const gh_index* ix, const gh_range* rang
     DevChain& dc = dev_chain(c->device);
     std::lock_guard<std::mutex> chain_lock(dc.mu);
     if (dc.has) GH_HIP(hipStreamWaitEvent(st, dc.last, 0));
-    GH_HIP(hipMemsetAsync(c->d_misc + 16, 0, 4, st));
-    GH_HIP(hipMemcpyAsync(c->d_ga_pieces, c->ga_pieces.data(), np * sizeof(gh_gather_piece), hipMemcpyHostToDevice, st));
-    GH_HIP(hipEventRecord(c->ga_ev0, st));
-    GH_HIP(hipLaunchKernel(c->ga_kern, dim3(grid), dim3(GA_TB), args, c->ga_lds, st));
+    GH_HIP(hipMemsetAsync(d_status, 0, 4, st));
+    GH_HIP(hipMemcpyAsync(ga.d_pieces.get(), ga.pieces.data(), np * sizeof(gh_gather_piece), hipMemcpyHostToDevice, st));
+    GH_HIP(hipEventRecord(ga.ev.a, st));
+    GH_HIP(hipLaunchKernel(t.kern, dim3(grid), dim3(GA_TB), args, t.lds, st));
     GH_HIP(hipGetLastError());
-    GH_HIP(hipEventRecord(c->ga_ev1, st));
-    GH_HIP(hipMemcpyAsync(dst, c->d_ga_out, total, hipMemcpyDefault, st));
+    GH_HIP(hipEventRecord(ga.ev.b, st));
+    GH_HIP(hipMemcpyAsync(dst, ga.d_out.get(), total, hipMemcpyDefault, st));
     GH_HIP(hipStreamSynchronize(st));
   }
-  GH_HIP(hipEventElapsedTime(&ms, c->ga_ev0, c->ga_ev1));
-  GH_HIP(hipMemcpy(&status, c->d_misc + 16, 4, hipMemcpyDeviceToHost));
+  if (int rc2 = ga.ev.elapsed(&ms)) return rc2;
+  GH_HIP(hipMemcpy(&status, d_status, 4, hipMemcpyDeviceToHost));
   if (status & GH_ST_LAYOUT) return fail(GH_E_HIP, "gather kernel: LDS layout assumption violated");
   if (status & GH_ST_BADCODE) return fail(GH_E_CORRUPT, "gather: invalid code in stream, or the index is another stream's");
   if (kernel_ms) *kernel_ms = ms;

@@ -41,11 +41,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "gaphuff.h"
+#include "gh_hip.hpp"
 #include "gh_internal.hpp"
 
 namespace gh {
@@ -611,40 +613,31 @@ __global__ __launch_bounds__(ETB) void gh_enc_index_kernel(const EncIndexParams 
 
 using namespace gh;
 
-#define GH_EHIP(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(GH_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
-
 struct gh_ectx {
   int device = 0;
   int num_cu = 0;
-  hipStream_t stream = nullptr;
-  uint8_t* d_in = nullptr;
-  uint64_t n = 0, in_cap = 0;
-  unsigned long long* d_count = nullptr;   // 256
-  uint32_t* d_lut = nullptr;               // 256
-  uint32_t* d_chunk_bits = nullptr;
-  unsigned long long* d_chunk_off = nullptr;
-  uint64_t chunk_cap = 0;
-  uint32_t* d_words = nullptr;
-  uint32_t* d_gaps = nullptr;
-  uint32_t* d_junk = nullptr;              // write kernel padding stores: one dword per thread
-  uint64_t junk_cap = 0;
-  uint64_t words_cap = 0, gaps_cap = 0;
+  Stream stream;
+  uint64_t n = 0;
+  DevBuf d_in;                                 // the input, padded (grown on demand, as the buffers below)
+  DevBuf d_count;                              // 256 u64
+  DevBuf d_lut;                                // 256 u32
+  DevBuf d_chunk_bits, d_chunk_off;            // u32 per chunk; u32 local offsets, then u64 per scan block
+  DevBuf d_words, d_gaps;
+  DevBuf d_junk;                               // write kernel padding stores: one dword per thread
   const uint32_t* d_loc = nullptr;             // the last encode's chunk offsets: views into d_chunk_off
   const unsigned long long* d_blk = nullptr;
-  unsigned long long* d_index = nullptr;       // gh_ectx_index: the entries
-  uint64_t index_cap = 0;
+  DevBuf d_index;                              // gh_ectx_index: the entries
   gh_encode_plan plan{};
   bool planned = false, encoded = false;
   uint64_t counts[256] = {};                   // histogram of the loaded input, when `counted`
   bool counted = false;
   bool sliced = false;                         // the last encode was a slice encode: `slice`
   gh_slice slice{};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  EventPair ev;
+  ~gh_ectx() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }  // (then the members free their memory and events, the stream last)
 };
 
 extern "C" int gh_ectx_create(int device, gh_ectx** out) {
@@ -655,50 +648,33 @@ extern "C" int gh_ectx_create(int device, gh_ectx** out) {
     return fail(GH_E_NODEV, "no HIP device visible (the GPU encoder has no CPU fallback)");
   if (device < 0 || device >= nd) return fail(GH_E_ARG, "device ordinal out of range");
   hipDeviceProp_t prop;
-  GH_EHIP(hipGetDeviceProperties(&prop, device));
+  GH_HIP(hipGetDeviceProperties(&prop, device));
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     return fail(GH_E_NODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
-  GH_EHIP(hipSetDevice(device));
-  gh_ectx* e = new gh_ectx();
+  GH_HIP(hipSetDevice(device));
+  std::unique_ptr<gh_ectx> e(new gh_ectx());  // (a failure below frees what was made)
   e->device = device;
   e->num_cu = prop.multiProcessorCount;
-  GH_EHIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  GH_EHIP(hipMalloc(&e->d_count, 256 * 8));
-  GH_EHIP(hipMalloc(&e->d_lut, 256 * 4));
-  GH_EHIP(hipEventCreate(&e->ev0));
-  GH_EHIP(hipEventCreate(&e->ev1));
-  *out = e;
+  if (int rc = e->stream.create()) return rc;
+  if (int rc = e->d_count.alloc(256 * 8)) return rc;
+  if (int rc = e->d_lut.alloc(256 * 4)) return rc;
+  if (int rc = e->ev.create()) return rc;
+  *out = e.release();
   return GH_OK;
 }
 
 extern "C" int gh_ectx_destroy(gh_ectx* e) {
-  if (!e) return GH_OK;
-  (void)hipSetDevice(e->device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  for (void* p : {(void*)e->d_in, (void*)e->d_count, (void*)e->d_lut, (void*)e->d_chunk_bits,
-                  (void*)e->d_chunk_off, (void*)e->d_words, (void*)e->d_gaps, (void*)e->d_junk, (void*)e->d_index})
-    (void)hipFree(p);
-  if (e->ev0) (void)hipEventDestroy(e->ev0);
-  if (e->ev1) (void)hipEventDestroy(e->ev1);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
   return GH_OK;
 }
 
 extern "C" int gh_ectx_load(gh_ectx* e, const uint8_t* in, uint64_t n) {
   if (!e || (n && !in)) return fail(GH_E_ARG, "null argument");
-  GH_EHIP(hipSetDevice(e->device));
+  GH_HIP(hipSetDevice(e->device));
   // padded: the write kernel's loads are unconditional (up to a chunk + 32 bytes past n)
-  const uint64_t need = n + ECHUNK + 64;
-  if (need > e->in_cap) {
-    (void)hipFree(e->d_in);
-    e->d_in = nullptr;
-    e->in_cap = 0;
-    GH_EHIP(hipMalloc(&e->d_in, need));
-    e->in_cap = need;
-  }
-  if (n) GH_EHIP(hipMemcpyAsync(e->d_in, in, n, hipMemcpyHostToDevice, e->stream));
-  GH_EHIP(hipStreamSynchronize(e->stream));
+  if (int rc = e->d_in.reserve(n + ECHUNK + 64)) return rc;
+  if (n) GH_HIP(hipMemcpyAsync(e->d_in.get(), in, n, hipMemcpyHostToDevice, e->stream));
+  GH_HIP(hipStreamSynchronize(e->stream));
   e->n = n;
   e->planned = e->encoded = e->counted = e->sliced = false;
   return GH_OK;
@@ -706,22 +682,23 @@ extern "C" int gh_ectx_load(gh_ectx* e, const uint8_t* in, uint64_t n) {
 
 // Byte histogram of the loaded input into e->counts (synchronous).
 static int ectx_hist(gh_ectx* e) {
-  GH_EHIP(hipMemsetAsync(e->d_count, 0, 256 * 8, e->stream));
+  GH_HIP(hipMemsetAsync(e->d_count.get(), 0, 256 * 8, e->stream));
   const uint64_t nchunks = ceil_div(e->n, ECHUNK);
   if (nchunks) {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(nchunks, 4ull * e->num_cu);
-    hipLaunchKernelGGL(gh_enc_hist_kernel, dim3(grid), dim3(ETB), 0, e->stream, e->d_in, e->n, e->d_count);
-    GH_EHIP(hipGetLastError());
+    hipLaunchKernelGGL(gh_enc_hist_kernel, dim3(grid), dim3(ETB), 0, e->stream, e->d_in.get<uint8_t>(), e->n,
+                       e->d_count.get<unsigned long long>());
+    GH_HIP(hipGetLastError());
   }
-  GH_EHIP(hipMemcpyAsync(e->counts, e->d_count, 256 * 8, hipMemcpyDeviceToHost, e->stream));
-  GH_EHIP(hipStreamSynchronize(e->stream));
+  GH_HIP(hipMemcpyAsync(e->counts, e->d_count.get(), 256 * 8, hipMemcpyDeviceToHost, e->stream));
+  GH_HIP(hipStreamSynchronize(e->stream));
   e->counted = true;
   return GH_OK;
 }
 
 extern "C" int gh_ectx_plan(gh_ectx* e, int force_version, gh_encode_plan* plan) {
   if (!e) return fail(GH_E_ARG, "null ctx");
-  GH_EHIP(hipSetDevice(e->device));
+  GH_HIP(hipSetDevice(e->device));
   e->planned = e->encoded = e->sliced = false;
   int rc = ectx_hist(e);
   if (rc) return rc;
@@ -738,7 +715,7 @@ extern "C" int gh_ectx_plan(gh_ectx* e, int force_version, gh_encode_plan* plan)
 
 extern "C" int gh_ectx_counts(gh_ectx* e, uint64_t counts[256]) {
   if (!e || !counts) return fail(GH_E_ARG, "null argument");
-  GH_EHIP(hipSetDevice(e->device));
+  GH_HIP(hipSetDevice(e->device));
   e->planned = e->encoded = e->sliced = false;
   const int rc = ectx_hist(e);
   if (rc) return rc;
@@ -771,34 +748,14 @@ static int ectx_encode_run(gh_ectx* e, const gh_encode_plan& pl, bool slice, uin
   const uint64_t org = base_bit & ~1023ull, end = base_bit + bits;
   const uint64_t NW = ceil_div(end, 32) - (org >> 5);    // a whole stream: pl.w
   const uint64_t GW = ceil_div(end, 1024) - (org >> 10);  // a whole stream: ceil(pl.g / 8)
-  if (nchunks + 1 > e->chunk_cap) {
-    (void)hipFree(e->d_chunk_bits);
-    (void)hipFree(e->d_chunk_off);
-    e->d_chunk_bits = nullptr;
-    e->d_chunk_off = nullptr;
-    e->chunk_cap = 0;
-    GH_EHIP(hipMalloc(&e->d_chunk_bits, 4 * (nchunks + 1)));
-    GH_EHIP(hipMalloc(&e->d_chunk_off, 4 * (nchunks + 1) + 8 * (nchunks / SCAN_BLK + 2) + 64));
-    e->chunk_cap = nchunks + 1;
-  }
-  if (NW + 4 > e->words_cap) {
-    (void)hipFree(e->d_words);
-    e->d_words = nullptr;
-    e->words_cap = 0;
-    GH_EHIP(hipMalloc(&e->d_words, 4 * (NW + 4)));
-    e->words_cap = NW + 4;
-  }
-  if (GW + 4 > e->gaps_cap) {
-    (void)hipFree(e->d_gaps);
-    e->d_gaps = nullptr;
-    e->gaps_cap = 0;
-    GH_EHIP(hipMalloc(&e->d_gaps, 4 * (GW + 4)));
-    e->gaps_cap = GW + 4;
-  }
+  if (int rc = e->d_chunk_bits.reserve(4 * (nchunks + 1))) return rc;
+  if (int rc = e->d_chunk_off.reserve(4 * (nchunks + 1) + 8 * (nchunks / SCAN_BLK + 2) + 64)) return rc;
+  if (int rc = e->d_words.reserve(4 * (NW + 4))) return rc;
+  if (int rc = e->d_gaps.reserve(4 * (GW + 4))) return rc;
   if (nchunks >= (1ull << 32)) return fail(GH_E_ARG, "input too large for the GPU encoder");
-  GH_EHIP(hipMemcpyAsync(e->d_lut, lut, sizeof(lut), hipMemcpyHostToDevice, e->stream));
-  GH_EHIP(hipEventRecord(e->ev0, e->stream));
-  GH_EHIP(hipMemsetAsync(e->d_gaps, 0, 4 * (GW + 4), e->stream));
+  GH_HIP(hipMemcpyAsync(e->d_lut.get(), lut, sizeof(lut), hipMemcpyHostToDevice, e->stream));
+  GH_HIP(hipEventRecord(e->ev.a, e->stream));
+  GH_HIP(hipMemsetAsync(e->d_gaps.get(), 0, 4 * (GW + 4), e->stream));
   if (nchunks) {
     // payload words per chunk ~ 4096 * W / n: NSW = store instructions per thread
     const double wpc = (double)ECHUNK * (double)ceil_div(bits, 32) / (double)std::max<uint64_t>(e->n, 1) + 2.0;
@@ -811,44 +768,42 @@ static int ectx_encode_run(gh_ectx* e, const gh_encode_plan& pl, bool slice, uin
     if (ew > (uint32_t)EWORDS || eg > (uint32_t)EGAPW) return fail(GH_E_TABLE, "code longer than 16 bits");
     const size_t dyn = 4ull * (ew + eg);
     int pb = 0, pw = 0;  // persistent grids: what is resident at once
-    GH_EHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)gh_enc_bits_kernel, ETB, 0));
-    GH_EHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pw, wk, ETB, dyn));
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)gh_enc_bits_kernel, ETB, 0));
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pw, wk, ETB, dyn));
     const uint32_t gb = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pb, 1) * e->num_cu);
-    hipLaunchKernelGGL(gh_enc_bits_kernel, dim3(gb), dim3(ETB), 0, e->stream, e->d_in, e->n, (uint32_t)nchunks,
-                       e->d_lut, e->d_chunk_bits);
+    const uint8_t* d_in = e->d_in.get<uint8_t>();
+    const uint32_t* d_lut = e->d_lut.get<uint32_t>();
+    uint32_t* d_chunk_bits = e->d_chunk_bits.get<uint32_t>();
+    unsigned long long* d_chunk_off = e->d_chunk_off.get<unsigned long long>();
+    hipLaunchKernelGGL(gh_enc_bits_kernel, dim3(gb), dim3(ETB), 0, e->stream, d_in, e->n, (uint32_t)nchunks,
+                       d_lut, d_chunk_bits);
     const uint32_t nblk = (uint32_t)ceil_div(nchunks, SCAN_BLK);
-    uint32_t* loc = (uint32_t*)e->d_chunk_off;
-    unsigned long long* blk = e->d_chunk_off + (nchunks + 2) / 2 + 1;  // after the local offsets
-    hipLaunchKernelGGL(gh_enc_scan_kernel, dim3(nblk), dim3(SCAN_TB), 0, e->stream, e->d_chunk_bits,
+    uint32_t* loc = (uint32_t*)d_chunk_off;
+    unsigned long long* blk = d_chunk_off + (nchunks + 2) / 2 + 1;  // after the local offsets
+    hipLaunchKernelGGL(gh_enc_scan_kernel, dim3(nblk), dim3(SCAN_TB), 0, e->stream, d_chunk_bits,
                        (uint32_t)nchunks, loc, blk);
     hipLaunchKernelGGL(gh_enc_blkscan_kernel, dim3(1), dim3(SCAN_TB), 0, e->stream, blk, nblk,
                        (unsigned long long)base_bit);
     const uint32_t gw = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pw, 1) * e->num_cu);
-    if ((uint64_t)gw * ETB > e->junk_cap) {
-      (void)hipFree(e->d_junk);
-      e->d_junk = nullptr;
-      e->junk_cap = 0;
-      GH_EHIP(hipMalloc(&e->d_junk, 4ull * gw * ETB));
-      e->junk_cap = (uint64_t)gw * ETB;
-    }
+    if (int rc = e->d_junk.reserve(4ull * gw * ETB)) return rc;
     e->d_loc = loc;
     e->d_blk = blk;
-    EncParams p{e->d_in, e->d_lut, loc, blk, e->d_words, e->d_gaps, e->d_junk, e->n, (uint32_t)nchunks, ew, eg,
-                org};
+    EncParams p{d_in, d_lut, loc, blk, e->d_words.get<uint32_t>(), e->d_gaps.get<uint32_t>(),
+                e->d_junk.get<uint32_t>(), e->n, (uint32_t)nchunks, ew, eg, org};
     void* args[] = {&p};
-    GH_EHIP(hipLaunchKernel(wk, dim3(gw), dim3(ETB), args, dyn, e->stream));
-    GH_EHIP(hipGetLastError());
+    GH_HIP(hipLaunchKernel(wk, dim3(gw), dim3(ETB), args, dyn, e->stream));
+    GH_HIP(hipGetLastError());
   }
-  GH_EHIP(hipEventRecord(e->ev1, e->stream));
-  GH_EHIP(hipStreamSynchronize(e->stream));
-  if (kernel_ms) GH_EHIP(hipEventElapsedTime(kernel_ms, e->ev0, e->ev1));
+  GH_HIP(hipEventRecord(e->ev.b, e->stream));
+  GH_HIP(hipStreamSynchronize(e->stream));
+  if (kernel_ms) return e->ev.elapsed(kernel_ms);
   return GH_OK;
 }
 
 extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
   if (!e) return fail(GH_E_ARG, "null ctx");
   if (!e->planned) return fail(GH_E_STATE, "gh_ectx_encode before gh_ectx_plan");
-  GH_EHIP(hipSetDevice(e->device));
+  GH_HIP(hipSetDevice(e->device));
   e->encoded = e->sliced = false;
   const int rc = ectx_encode_run(e, e->plan, false, 0, e->plan.bits, kernel_ms);
   if (rc) return rc;
@@ -859,7 +814,7 @@ extern "C" int gh_ectx_encode(gh_ectx* e, float* kernel_ms) {
 extern "C" int gh_ectx_encode_slice(gh_ectx* e, const gh_encode_plan* sp, uint64_t base_bit, gh_slice* out,
                                     float* kernel_ms) {
   if (!e || !sp) return fail(GH_E_ARG, "null argument");
-  GH_EHIP(hipSetDevice(e->device));
+  GH_HIP(hipSetDevice(e->device));
   e->encoded = e->sliced = false;  // (the buffers of an earlier encode are reused)
   if (!e->counted) {
     const int rc = ectx_hist(e);
@@ -888,12 +843,12 @@ extern "C" int gh_ectx_download_slice(gh_ectx* e, uint32_t* words, uint64_t word
   const gh_slice& sl = e->slice;
   if (words_cap < sl.nwords || gaps_cap < sl.ngapw) return fail(GH_E_SMALL, "slice buffer too small");
   if ((sl.nwords && !words) || (sl.ngapw && !gapw)) return fail(GH_E_ARG, "null argument");
-  GH_EHIP(hipSetDevice(e->device));
+  GH_HIP(hipSetDevice(e->device));
   // the device buffers start at the gap word holding base_bit: up to 31 words before word0
   const uint64_t lead = sl.word0 - ((sl.base_bit & ~1023ull) >> 5);
-  if (sl.ngapw) GH_EHIP(hipMemcpyAsync(gapw, e->d_gaps, 4 * sl.ngapw, hipMemcpyDeviceToHost, e->stream));
-  if (sl.nwords) GH_EHIP(hipMemcpyAsync(words, e->d_words + lead, 4 * sl.nwords, hipMemcpyDeviceToHost, e->stream));
-  GH_EHIP(hipStreamSynchronize(e->stream));
+  if (sl.ngapw) GH_HIP(hipMemcpyAsync(gapw, e->d_gaps.get(), 4 * sl.ngapw, hipMemcpyDeviceToHost, e->stream));
+  if (sl.nwords) GH_HIP(hipMemcpyAsync(words, e->d_words.get<uint32_t>() + lead, 4 * sl.nwords, hipMemcpyDeviceToHost, e->stream));
+  GH_HIP(hipStreamSynchronize(e->stream));
   return GH_OK;
 }
 
@@ -902,13 +857,13 @@ extern "C" int gh_ectx_download(gh_ectx* e, void* out, uint64_t out_len) {
   if (!e->encoded) return fail(GH_E_STATE, "gh_ectx_download before gh_ectx_encode");
   const gh_encode_plan& pl = e->plan;
   if (out_len < pl.file_bytes) return fail(GH_E_SMALL, "output buffer too small");
-  GH_EHIP(hipSetDevice(e->device));
+  GH_HIP(hipSetDevice(e->device));
   uint8_t* o = (uint8_t*)out;
   const size_t hdr = encode_header(&pl, o);
   const uint64_t GW = ceil_div(pl.g, GH_GAPS_PER_WORD);
-  if (GW) GH_EHIP(hipMemcpyAsync(o + hdr, e->d_gaps, 4 * GW, hipMemcpyDeviceToHost, e->stream));
-  if (pl.w) GH_EHIP(hipMemcpyAsync(o + hdr + 4 * GW, e->d_words, 4 * pl.w, hipMemcpyDeviceToHost, e->stream));
-  GH_EHIP(hipStreamSynchronize(e->stream));
+  if (GW) GH_HIP(hipMemcpyAsync(o + hdr, e->d_gaps.get(), 4 * GW, hipMemcpyDeviceToHost, e->stream));
+  if (pl.w) GH_HIP(hipMemcpyAsync(o + hdr + 4 * GW, e->d_words.get(), 4 * pl.w, hipMemcpyDeviceToHost, e->stream));
+  GH_HIP(hipStreamSynchronize(e->stream));
   return GH_OK;
 }
 
@@ -921,33 +876,29 @@ extern "C" int gh_ectx_index(gh_ectx* e, uint32_t log2_stride, void* out, uint64
   const uint64_t bytes = gh_index_bytes(pl.g, log2_stride);
   if (bytes == 0) return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
   if (out_len < bytes) return fail(GH_E_SMALL, "index buffer too small");
-  GH_EHIP(hipSetDevice(e->device));
+  GH_HIP(hipSetDevice(e->device));
   uint8_t* o = (uint8_t*)out;
   const uint64_t nblocks = (bytes - 40) / 8 - 1;
   const uint64_t nchunks = ceil_div(e->n, ECHUNK);
-  if (nblocks > e->index_cap) {
-    (void)hipFree(e->d_index);
-    e->d_index = nullptr;
-    e->index_cap = 0;
-    GH_EHIP(hipMalloc(&e->d_index, 8 * nblocks));
-    e->index_cap = nblocks;
-  }
-  GH_EHIP(hipEventRecord(e->ev0, e->stream));
+  if (int rc = e->d_index.reserve(8 * nblocks)) return rc;
+  GH_HIP(hipEventRecord(e->ev.a, e->stream));
   if (nblocks) {  // (then N > 0: the encode ran its kernels)
     int pc = 0;
-    GH_EHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, (const void*)gh_enc_index_kernel, ETB, 0));
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, (const void*)gh_enc_index_kernel, ETB, 0));
     uint32_t grid = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pc, 1) * e->num_cu);
     if (const char* eg = getenv("GH_ENC_INDEX_GRID"))  // tests: few workgroups, many chunks each
       grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
-    const EncIndexParams p{e->d_in, e->d_lut, e->d_chunk_bits, e->d_loc, e->d_blk, e->d_index, e->n, nblocks,
+    const EncIndexParams p{e->d_in.get<uint8_t>(), e->d_lut.get<uint32_t>(), e->d_chunk_bits.get<uint32_t>(),
+                           e->d_loc, e->d_blk, e->d_index.get<unsigned long long>(), e->n, nblocks,
                            (uint32_t)nchunks, 7u + log2_stride};
     hipLaunchKernelGGL(gh_enc_index_kernel, dim3(grid), dim3(ETB), 0, e->stream, p);
-    GH_EHIP(hipGetLastError());
+    GH_HIP(hipGetLastError());
   }
-  GH_EHIP(hipEventRecord(e->ev1, e->stream));
-  if (nblocks) GH_EHIP(hipMemcpyAsync(o + 40, e->d_index, 8 * nblocks, hipMemcpyDeviceToHost, e->stream));
-  GH_EHIP(hipStreamSynchronize(e->stream));
-  if (kernel_ms) GH_EHIP(hipEventElapsedTime(kernel_ms, e->ev0, e->ev1));
+  GH_HIP(hipEventRecord(e->ev.b, e->stream));
+  if (nblocks) GH_HIP(hipMemcpyAsync(o + 40, e->d_index.get(), 8 * nblocks, hipMemcpyDeviceToHost, e->stream));
+  GH_HIP(hipStreamSynchronize(e->stream));
+  if (kernel_ms)
+    if (int rc = e->ev.elapsed(kernel_ms)) return rc;
   index_header(log2_stride, pl.n, pl.g, nblocks + 1, o);
   std::memcpy(o + 40 + 8 * nblocks, &pl.n, 8);
   return GH_OK;

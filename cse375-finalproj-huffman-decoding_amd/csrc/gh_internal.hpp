@@ -1,5 +1,6 @@
 // Internal helpers shared by the host library (gh_core.cpp) and the HIP decoder
-// (gh_decode.hip).  Not part of the C ABI.
+// (gh_decode.hip).  The host-only HIP helpers (the GH_HIP error macro and the owners of
+// device memory, streams and events) are in gh_hip.hpp.  Not part of the C ABI.
 #pragma once
 #include <cstdint>
 #include <string>

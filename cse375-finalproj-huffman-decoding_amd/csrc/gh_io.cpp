@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "gh_hip.hpp"
 #include "gh_internal.hpp"
 
 namespace gh {
@@ -32,13 +33,6 @@ namespace {
 
 constexpr size_t IO_CHUNK = 32ull << 20;  // bytes per staging buffer
 constexpr size_t HDR_MAX = 8 + 8 + 2 * GH_MAX_SYMBOLS + 24;
-
-#define GH_HIPI(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(GH_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
 
 double now_ms() {
   using namespace std::chrono;
@@ -57,32 +51,21 @@ struct Fd {
 // handed to one call at a time.
 struct Staging {
   void* buf[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipStream_t st = nullptr;
+  Stream st;
+  Event ev[2];
   bool ready() const { return st && buf[0] && buf[1] && ev[0] && ev[1]; }
-  // Frees whatever a failed init() left (a set is pooled only when ready()).
-  void release() {
-    for (int i = 0; i < 2; ++i) {
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
-      if (buf[i]) (void)hipHostFree(buf[i]);
-      ev[i] = nullptr;
-      buf[i] = nullptr;
-    }
-    if (st) (void)hipStreamDestroy(st);
-    st = nullptr;
+  // Frees whatever a failed init() left too (a set is pooled only when ready()).
+  ~Staging() {
+    for (void* b : buf)
+      if (b) (void)hipHostFree(b);
   }
+  // Of a new set (the pooled ones are ready).
   int init() {
     if (ready()) return GH_OK;
-    release();
-    int rc = init_parts();
-    if (rc) release();
-    return rc;
-  }
-  int init_parts() {
-    GH_HIPI(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    if (int rc = st.create()) return rc;
     for (int i = 0; i < 2; ++i) {
-      GH_HIPI(hipHostMalloc(&buf[i], IO_CHUNK, hipHostMallocDefault));
-      GH_HIPI(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+      GH_HIP(hipHostMalloc(&buf[i], IO_CHUNK, hipHostMallocDefault));
+      if (int rc = ev[i].create(hipEventDisableTiming)) return rc;
     }
     return GH_OK;
   }
@@ -134,10 +117,7 @@ struct StagingLease {
       }
     }
     g_pool_cv.notify_all();
-    if (s) {
-      s->release();
-      delete s;
-    }
+    delete s;
   }
 };
 
@@ -187,23 +167,18 @@ int stream_h2d(Staging& s, int fd, uint64_t off, uint64_t n, uint8_t* dst) {
   int b = 0;
   for (uint64_t done = 0; done < n; b ^= 1) {
     const size_t c = (size_t)std::min<uint64_t>(IO_CHUNK, n - done);
-    GH_HIPI(hipEventSynchronize(s.ev[b]));  // the DMA that last used this buffer
+    GH_HIP(hipEventSynchronize(s.ev[b]));  // the DMA that last used this buffer
     uint8_t* hb = (uint8_t*)s.buf[b];
     const uint64_t base = off + done;
     if (!par_io(c, [&](size_t a, size_t m) { return read_full(fd, hb + a, m, base + a); }))
       return fail(GH_E_FORMAT, "short read of the stream file");
-    GH_HIPI(hipMemcpyAsync(dst + done, s.buf[b], c, hipMemcpyHostToDevice, s.st));
-    GH_HIPI(hipEventRecord(s.ev[b], s.st));
+    GH_HIP(hipMemcpyAsync(dst + done, s.buf[b], c, hipMemcpyHostToDevice, s.st));
+    GH_HIP(hipEventRecord(s.ev[b], s.st));
     done += c;
   }
-  GH_HIPI(hipStreamSynchronize(s.st));
+  GH_HIP(hipStreamSynchronize(s.st));
   return GH_OK;
 }
-
-struct DevMem {
-  void* p = nullptr;
-  ~DevMem() { (void)hipFree(p); }
-};
 
 }  // namespace
 
@@ -218,7 +193,7 @@ bool use_staged(uint64_t n) {
 // Host bytes -> device, double-buffered: the host copy of chunk c+1 (split over
 // IO_THREADS threads) overlaps the DMA of chunk c.
 int h2d_staged(int device, const void* src, uint64_t n, void* dst) {
-  GH_HIPI(hipSetDevice(device));
+  GH_HIP(hipSetDevice(device));
   StagingLease lease(device);
   int rc = lease.acquire();
   if (rc) return rc;
@@ -226,21 +201,21 @@ int h2d_staged(int device, const void* src, uint64_t n, void* dst) {
   int b = 0;
   for (uint64_t done = 0; done < n; b ^= 1) {
     const size_t c = (size_t)std::min<uint64_t>(IO_CHUNK, n - done);
-    GH_HIPI(hipEventSynchronize(s.ev[b]));  // the DMA that last used this buffer
+    GH_HIP(hipEventSynchronize(s.ev[b]));  // the DMA that last used this buffer
     uint8_t* hb = (uint8_t*)s.buf[b];
     const uint8_t* sp = (const uint8_t*)src + done;
     par_io(c, [&](size_t a, size_t m) { std::memcpy(hb + a, sp + a, m); return true; });
-    GH_HIPI(hipMemcpyAsync((uint8_t*)dst + done, hb, c, hipMemcpyHostToDevice, s.st));
-    GH_HIPI(hipEventRecord(s.ev[b], s.st));
+    GH_HIP(hipMemcpyAsync((uint8_t*)dst + done, hb, c, hipMemcpyHostToDevice, s.st));
+    GH_HIP(hipEventRecord(s.ev[b], s.st));
     done += c;
   }
-  GH_HIPI(hipStreamSynchronize(s.st));
+  GH_HIP(hipStreamSynchronize(s.st));
   return GH_OK;
 }
 
 // Device bytes -> host: the DMA of chunk c+1 overlaps the host copy of chunk c.
 int d2h_staged(int device, const void* src, uint64_t n, void* dst) {
-  GH_HIPI(hipSetDevice(device));
+  GH_HIP(hipSetDevice(device));
   StagingLease lease(device);
   int rc = lease.acquire();
   if (rc) return rc;
@@ -251,11 +226,11 @@ int d2h_staged(int device, const void* src, uint64_t n, void* dst) {
   for (uint64_t done = 0;; b ^= 1) {
     const size_t c = (size_t)std::min<uint64_t>(IO_CHUNK, n - done);
     if (c) {
-      GH_HIPI(hipMemcpyAsync(s.buf[b], (const uint8_t*)src + done, c, hipMemcpyDeviceToHost, s.st));
-      GH_HIPI(hipEventRecord(s.ev[b], s.st));
+      GH_HIP(hipMemcpyAsync(s.buf[b], (const uint8_t*)src + done, c, hipMemcpyDeviceToHost, s.st));
+      GH_HIP(hipEventRecord(s.ev[b], s.st));
     }
     if (pend_b >= 0) {
-      GH_HIPI(hipEventSynchronize(s.ev[pend_b]));
+      GH_HIP(hipEventSynchronize(s.ev[pend_b]));
       const uint8_t* hb = (const uint8_t*)s.buf[pend_b];
       uint8_t* dp = (uint8_t*)dst + pend_off;
       par_io(pend_n, [&](size_t a, size_t m) { std::memcpy(dp + a, hb + a, m); return true; });
@@ -297,19 +272,18 @@ extern "C" int gh_ctx_load_file(gh_ctx* ctx, const char* path, uint64_t seg_begi
   const uint64_t pay_off = gap_off + 4 * gw;
   int dev = 0;
   if ((rc = gh_ctx_device(ctx, &dev))) return rc;
-  GH_HIPI(hipSetDevice(dev));
+  GH_HIP(hipSetDevice(dev));
   // the shard's payload words [4b, 4e+1) clipped at W, and the whole gap array
   const uint64_t w0 = std::min<uint64_t>(4 * seg_begin, s.w);
   const uint64_t w1 = std::min<uint64_t>(4 * seg_end + 1, s.w);
-  DevMem dpay, dgap;
-  GH_HIPI(hipMalloc(&dpay.p, 4 * (w1 - w0) + 64));
-  GH_HIPI(hipMalloc(&dgap.p, 4 * gw + 64));
+  DevBuf dpay, dgap;
+  if ((rc = dpay.alloc(4 * (w1 - w0) + 64)) || (rc = dgap.alloc(4 * gw + 64))) return rc;
   StagingLease lease(dev);
   if ((rc = lease.acquire())) return rc;
   Staging& stg = *lease.s;
   const double t1 = now_ms();
-  if ((rc = stream_h2d(stg, f.fd, gap_off, 4 * gw, (uint8_t*)dgap.p))) return rc;
-  if ((rc = stream_h2d(stg, f.fd, pay_off + 4 * w0, 4 * (w1 - w0), (uint8_t*)dpay.p))) return rc;
+  if ((rc = stream_h2d(stg, f.fd, gap_off, 4 * gw, dgap.get<uint8_t>()))) return rc;
+  if ((rc = stream_h2d(stg, f.fd, pay_off + 4 * w0, 4 * (w1 - w0), dpay.get<uint8_t>()))) return rc;
   const double t2 = now_ms();
   // copy the (<= 256-entry) symbol list: s.syms points into hdr
   gh_sym syms[GH_MAX_SYMBOLS];
@@ -318,8 +292,8 @@ extern "C" int gh_ctx_load_file(gh_ctx* ctx, const char* path, uint64_t seg_begi
   hs.syms = syms;
   hs.gap_words = nullptr;
   hs.payload = nullptr;
-  rc = gh_ctx_load_device(ctx, &hs, seg_begin, seg_end, (const uint32_t*)dpay.p, w1 - w0,
-                          (const uint32_t*)dgap.p, out_cap);
+  rc = gh_ctx_load_device(ctx, &hs, seg_begin, seg_end, dpay.get<uint32_t>(), w1 - w0,
+                          dgap.get<uint32_t>(), out_cap);
   if (rc) return rc;
   if (info) {
     std::memset(info, 0, sizeof(*info));
@@ -347,7 +321,7 @@ extern "C" int gh_ctx_save_file(gh_ctx* ctx, const char* path, uint64_t file_off
   if (byte_offset > cap || nbytes > cap - byte_offset) return fail(GH_E_ARG, "save beyond the output capacity");
   int dev = 0;
   if ((rc = gh_ctx_device(ctx, &dev))) return rc;
-  GH_HIPI(hipSetDevice(dev));
+  GH_HIP(hipSetDevice(dev));
   Fd f;
   f.fd = open(path, O_WRONLY | O_CREAT | (truncate ? O_TRUNC : 0), 0644);
   if (f.fd < 0) return fail(GH_E_ARG, std::string("cannot open ") + path + " for writing");
@@ -365,11 +339,11 @@ extern "C" int gh_ctx_save_file(gh_ctx* ctx, const char* path, uint64_t file_off
   for (uint64_t done = 0;; b ^= 1) {
     const size_t c = (size_t)std::min<uint64_t>(IO_CHUNK, nbytes - done);
     if (c) {
-      GH_HIPI(hipMemcpyAsync(stg.buf[b], src + done, c, hipMemcpyDeviceToHost, stg.st));
-      GH_HIPI(hipEventRecord(stg.ev[b], stg.st));
+      GH_HIP(hipMemcpyAsync(stg.buf[b], src + done, c, hipMemcpyDeviceToHost, stg.st));
+      GH_HIP(hipEventRecord(stg.ev[b], stg.st));
     }
     if (pend_b >= 0) {
-      GH_HIPI(hipEventSynchronize(stg.ev[pend_b]));
+      GH_HIP(hipEventSynchronize(stg.ev[pend_b]));
       const uint8_t* hb = (const uint8_t*)stg.buf[pend_b];
       const uint64_t base = file_offset + pend_off;
       const int fd = f.fd;

@@ -8,6 +8,8 @@
 //                                the Kc-bit window (bit e-1 of the mask per codeword
 //                                end e, b = their bits);
 //   wave split, write pass       u64 {up to four symbol bytes, b | n << 8};
+//   two-pass tile, both passes   u64 write entries with the codewords' starts (multi_lut),
+//                                u32 {b | start mask << 16} count entries (start_count_lut);
 //   range gather, decode pass    u32 {len | sym << 8}, one codeword per lookup, any width;
 //   canonical fallback           FB_WORDS u32: running limit16[1..16], base16[1..16],
 //                                first[1..16], then the symbol bytes (file order) —
@@ -152,6 +154,20 @@ inline double count_lut(const Canon& c, uint32_t Kc, std::vector<uint32_t>* out)
     if (out) (*out)[i] = b | (m << 16);
   }
   return sum / (double)(1u << Kc);
+}
+
+// Two-pass tile kernel count LUT (gh_mtile.hip): entry i = b | start mask << 16, every
+// codeword of the Kc-bit window (the starts as in multi_lut), replicated 2^lgr times:
+// dword i = entry i >> lgr.
+inline std::vector<uint32_t> start_count_lut(const Canon& c, uint32_t Kc, uint32_t lgr) {
+  std::vector<uint32_t> t(1u << (Kc + lgr));
+  for (uint32_t i = 0; i < (1u << Kc); ++i) {
+    uint32_t n = 0, m = 0;
+    const uint32_t b = window_codewords(c, i, Kc, 32, &n, nullptr, &m);
+    const uint32_t e = b | ((n ? (1u | (m << 1)) & ((1u << b) - 1u) : 0u) << 16);
+    std::fill_n(t.begin() + ((size_t)i << lgr), (size_t)1 << lgr, e);
+  }
+  return t;
 }
 
 // Canonical fallback tables.  limit16 is carried forward over empty lengths, so a

@@ -57,6 +57,7 @@
 #include <string>
 #include <vector>
 
+#include "gh_hip.hpp"
 #include "gh_internal.hpp"
 
 namespace gh {
@@ -89,13 +90,6 @@ static_assert(SYNC_M % 8 == 0, "a lane writes whole gap words");
 #endif
 // warm-up segments per lane: from the stream's resynchronisation distances (sync_halo_for;
 // GH_SYNC_HALO overrides)
-
-#define GH_HIPS(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(GH_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
 
 struct SyncParams {
   const uint32_t* words;  // raw stream, 16-byte aligned
@@ -583,11 +577,6 @@ uint32_t sync_halo_for(const SyncTables& st, const std::vector<uint32_t>& sample
   return best;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { (void)hipFree(p); }
-};
-
 int grid_for(const void* k, uint64_t items) {
   int dev = 0, ncu = 0, per = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 1;
@@ -614,28 +603,26 @@ extern "C" int gh_sync_gaps(int device, const gh_sym* syms, uint32_t nsyms, cons
   const uint64_t g = ceil_div(w, 4);
   if (rep) rep->g = g;
   if (g == 0) return GH_OK;
-  GH_HIPS(hipSetDevice(device));
+  GH_HIP(hipSetDevice(device));
   hipStream_t st = (hipStream_t)hip_stream;
   SyncTables tabs;
   build_sync_tables(canon, tabs);
   DevBuf lut, check, counter;
   const uint64_t nblk = ceil_div(g, (uint64_t)SYNC_M);  // lanes of the walk kernel
-  GH_HIPS(hipMalloc(&lut.p, 2u << SK));
-  GH_HIPS(hipMalloc(&check.p, nblk + 16));
-  GH_HIPS(hipMalloc(&counter.p, 16));
-  GH_HIPS(hipMemcpyAsync(lut.p, tabs.lut.data(), 2u << SK, hipMemcpyHostToDevice, st));
+  if ((rc = lut.alloc(2u << SK)) || (rc = check.alloc(nblk + 16)) || (rc = counter.alloc(16))) return rc;
+  GH_HIP(hipMemcpyAsync(lut.get(), tabs.lut.data(), 2u << SK, hipMemcpyHostToDevice, st));
   SyncParams p{};
   p.words = d_words;
   p.w = w;
   p.g = g;
-  p.lut = (const uint16_t*)lut.p;
+  p.lut = lut.get<uint16_t>();
   p.t13 = tabs.T[13];
   p.t14 = tabs.T[14];
   p.t15 = tabs.T[15];
   p.t16 = tabs.T[16];
   p.gaps = d_gap_words;
-  p.check = (uint8_t*)check.p;
-  p.counter = (unsigned int*)counter.p;
+  p.check = check.get<uint8_t>();
+  p.counter = counter.get<unsigned int>();
   float host_ms = 0;
   {
     const char* eh = getenv("GH_SYNC_HALO");
@@ -645,8 +632,8 @@ extern "C" int gh_sync_gaps(int device, const gh_sym* syms, uint32_t nsyms, cons
     } else {  // from the stream's first words (at most 64 KiB; before the timed region)
       const uint64_t ns = std::min<uint64_t>(w, 16384);
       std::vector<uint32_t> sample(ns + 2, 0);
-      GH_HIPS(hipMemcpyAsync(sample.data(), d_words, 4 * ns, hipMemcpyDeviceToHost, st));
-      GH_HIPS(hipStreamSynchronize(st));
+      GH_HIP(hipMemcpyAsync(sample.data(), d_words, 4 * ns, hipMemcpyDeviceToHost, st));
+      GH_HIP(hipStreamSynchronize(st));
       int ncu = 256;
       if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ncu = 256;
       const bool short_stream = ceil_div(nblk, (uint64_t)64) < 8ull * 4 * (uint64_t)ncu;  // < 8 waves per SIMD
@@ -655,41 +642,36 @@ extern "C" int gh_sync_gaps(int device, const gh_sym* syms, uint32_t nsyms, cons
     }
     if (getenv("GH_SYNC_VERBOSE")) fprintf(stderr, "gh_sync: %u segments per lane, halo %u\n", SYNC_M, p.halo);
   }
-  hipEvent_t e0, e1;
-  GH_HIPS(hipEventCreate(&e0));
-  GH_HIPS(hipEventCreate(&e1));
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-  } evg{e0, e1};
+  EventPair ev;
+  if ((rc = ev.create())) return rc;
   const bool lng = canon.maxlen > (uint32_t)SK;
   const void* ks = lng ? (const void*)gh_sync_kernel<true> : (const void*)gh_sync_kernel<false>;
   const void* kf = lng ? (const void*)gh_sync_fix_kernel<true> : (const void*)gh_sync_fix_kernel<false>;
   const int gs = (int)ceil_div(nblk, (uint64_t)SYNC_TB);  // one lane per block (not persistent)
   const int gf = grid_for(kf, ceil_div(nblk, (uint64_t)64));  // one thread per wave of the walk
   void* kargs[] = {&p};
-  GH_HIPS(hipMemsetAsync(counter.p, 0, 12, st));
-  GH_HIPS(hipEventRecord(e0, st));
-  GH_HIPS(hipLaunchKernel(ks, dim3(gs), dim3(SYNC_TB), kargs, 0, st));
-  GH_HIPS(hipGetLastError());
+  GH_HIP(hipMemsetAsync(counter.get(), 0, 12, st));
+  GH_HIP(hipEventRecord(ev.a, st));
+  GH_HIP(hipLaunchKernel(ks, dim3(gs), dim3(SYNC_TB), kargs, 0, st));
+  GH_HIP(hipGetLastError());
   uint64_t mism = 0;
   uint32_t passes = 0;
   float ms = 0;
   for (;;) {
-    GH_HIPS(hipLaunchKernel(kf, dim3(gf), dim3(SYNC_TB), kargs, 0, st));
-    GH_HIPS(hipGetLastError());
-    GH_HIPS(hipEventRecord(e1, st));
+    GH_HIP(hipLaunchKernel(kf, dim3(gf), dim3(SYNC_TB), kargs, 0, st));
+    GH_HIP(hipGetLastError());
+    GH_HIP(hipEventRecord(ev.b, st));
     unsigned int cnt[3] = {};
-    GH_HIPS(hipMemcpyAsync(cnt, counter.p, 12, hipMemcpyDeviceToHost, st));
-    GH_HIPS(hipStreamSynchronize(st));
-    GH_HIPS(hipEventElapsedTime(&ms, e0, e1));
+    GH_HIP(hipMemcpyAsync(cnt, counter.get(), 12, hipMemcpyDeviceToHost, st));
+    GH_HIP(hipStreamSynchronize(st));
+    if ((rc = ev.elapsed(&ms))) return rc;
     ++passes;
     mism += cnt[0] + (passes == 1 ? cnt[2] : 0u);
     if (cnt[1] == 0) break;  // no repair reached a wave's last block: every block verified
     // each pass makes at least the lowest mismatching wave true, so one pass per wave
     // always suffices
     if (passes > nblk / 64 + 2) return fail(GH_E_CORRUPT, "self-synchronisation did not converge");
-    GH_HIPS(hipMemsetAsync(counter.p, 0, 8, st));
+    GH_HIP(hipMemsetAsync(counter.get(), 0, 8, st));
   }
   if (rep) {
     rep->mismatches = mism;
@@ -708,7 +690,7 @@ extern "C" int gh_ctx_load_raw(gh_ctx* ctx, const gh_sym* syms, uint32_t nsyms, 
   int dev = 0;
   int rc = gh_ctx_device(ctx, &dev);
   if (rc) return rc;
-  GH_HIPS(hipSetDevice(dev));
+  GH_HIP(hipSetDevice(dev));
   const uint64_t g = ceil_div(w, 4);
   {  // N symbols of at least minlen bits each must fit the 32 w bits
     Canon cn;
@@ -718,12 +700,9 @@ extern "C" int gh_ctx_load_raw(gh_ctx* ctx, const gh_sym* syms, uint32_t nsyms, 
       return fail(GH_E_FORMAT, "raw stream holds fewer bits than N symbols need");
   }
   DevBuf dw, dg;
-  GH_HIPS(hipMalloc(&dw.p, 4 * (w + 16)));
-  GH_HIPS(hipMemset(dw.p, 0, 4 * (w + 16)));
-  if (w) GH_HIPS(hipMemcpy(dw.p, words, 4 * w, hipMemcpyHostToDevice));
-  GH_HIPS(hipMalloc(&dg.p, 4 * (ceil_div(g, 8) + 4)));
-  GH_HIPS(hipMemset(dg.p, 0, 4 * (ceil_div(g, 8) + 4)));
-  rc = gh_sync_gaps(dev, syms, nsyms, (const uint32_t*)dw.p, w, (uint32_t*)dg.p, nullptr, rep);
+  if ((rc = dw.alloc(4 * (w + 16), true)) || (rc = dg.alloc(4 * (ceil_div(g, 8) + 4), true))) return rc;
+  if (w) GH_HIP(hipMemcpy(dw.get(), words, 4 * w, hipMemcpyHostToDevice));
+  rc = gh_sync_gaps(dev, syms, nsyms, dw.get<uint32_t>(), w, dg.get<uint32_t>(), nullptr, rep);
   if (rc) return rc;
   gh_stream s{};
   s.syms = syms;
@@ -732,7 +711,7 @@ extern "C" int gh_ctx_load_raw(gh_ctx* ctx, const gh_sym* syms, uint32_t nsyms, 
   s.n = n;
   s.w = w;
   s.g = g;
-  return gh_ctx_load_device(ctx, &s, 0, g, (const uint32_t*)dw.p, w, (const uint32_t*)dg.p, out_cap);
+  return gh_ctx_load_device(ctx, &s, 0, g, dw.get<uint32_t>(), w, dg.get<uint32_t>(), out_cap);
 }
 
 // Device-memory helpers for C/FFI callers that have no HIP binding of their own (e.g.
@@ -740,18 +719,18 @@ extern "C" int gh_ctx_load_raw(gh_ctx* ctx, const gh_sym* syms, uint32_t nsyms, 
 extern "C" int gh_dev_alloc(int device, uint64_t bytes, void** out) {
   if (!out) return fail(GH_E_ARG, "null argument");
   *out = nullptr;
-  GH_HIPS(hipSetDevice(device));
-  GH_HIPS(hipMalloc(out, std::max<uint64_t>(bytes, 1)));
+  GH_HIP(hipSetDevice(device));
+  GH_HIP(hipMalloc(out, std::max<uint64_t>(bytes, 1)));
   return GH_OK;
 }
 
 extern "C" int gh_dev_free(void* p) {
-  GH_HIPS(hipFree(p));
+  GH_HIP(hipFree(p));
   return GH_OK;
 }
 
 extern "C" int gh_dev_copy(void* dst, const void* src, uint64_t bytes) {
   if (bytes && (!dst || !src)) return fail(GH_E_ARG, "null argument");
-  if (bytes) GH_HIPS(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
+  if (bytes) GH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
   return GH_OK;
 }

@@ -144,6 +144,100 @@ def test_raw_stream_shorter_than_n_is_an_error(gpu):
     assert np.array_equal(gpu.decode_raw(units, syms, data.size), data)
 
 
+# ---- one loader behind gh_ctx_load and gh_ctx_load_device ------------------------------
+LOADER_N = 200_003
+LOADER_STREAMS = {"tile": 0.1, "mtile": 0.9, "wsplit": 0.9}  # forced GH_MODE -> generator r
+
+
+def _tile_kernel_takes(lengths):
+    """gh_lut.hpp's grouped_code / short_code from the code lengths alone: complete, at
+    most 12 bits, shortest codeword 3 bits, or >= 4 bits with fewer than 1.5 codewords
+    expected in a 12-bit window of random bits (at most four are counted)."""
+    if sum(2.0 ** -l for l in lengths) != 1.0 or max(lengths) > 12 or min(lengths) < 3:
+        return False
+    if min(lengths) == 3:
+        return True
+    prob = {}
+    for l in lengths:
+        prob[l] = prob.get(l, 0.0) + 2.0 ** -l
+    state, gain = {(0, 0): 1.0}, 0.0  # (window bits used, codewords) -> probability
+    while state:
+        nxt = {}
+        for (pos, k), p in state.items():
+            for l, q in prob.items():
+                if k < 4 and pos + l <= 12:
+                    nxt[(pos + l, k + 1)] = nxt.get((pos + l, k + 1), 0.0) + p * q
+                else:
+                    gain += p * q * k
+        state = nxt
+    return gain < 1.5
+
+
+def _loader_case(gh, tmp_path, mode):
+    """The stream of a forced mode, its file and three shard ranges whose inner bounds are
+    no multiple of 8 (the gap words start inside a word) and not plan_shards' own."""
+    d, path = _write(tmp_path, gh, 11, LOADER_STREAMS[mode], LOADER_N, f"{mode}.huff")
+    s = gh.parse(np.fromfile(path, dtype=np.uint8))
+    lengths = [l for _, l in s.symbols]
+    if mode == "tile":
+        assert _tile_kernel_takes(lengths), "GH_MODE=tile would refuse this code"
+    else:  # the two-pass tile kernel's codes; the wave split takes any
+        assert sum(2.0 ** -l for l in lengths) == 1.0 and max(lengths) <= 16
+    b1, b2 = s.g // 3 + 1, 2 * (s.g // 3) + 3
+    while b1 % 8 == 0 or b1 in gh.plan_shards(s.g, 3):
+        b1 += 1
+    assert 0 < b1 < b2 < s.g - 1
+    return d, path, s, [(0, b1), (b1, b2), (b2, s.g)]
+
+
+@pytest.mark.parametrize("mode", LOADER_STREAMS)
+def test_loader_streams_meet_their_preconditions(gh, tmp_path, mode):
+    _loader_case(gh, tmp_path, mode)
+
+
+def _both_loads(gpu, mode, s, path, b, e):
+    """Segments [b, e) through gh_ctx_load (Decoder.load) and through gh_ctx_load_device
+    (Decoder.load_file), each decoded: (symbols, output bytes kept) of the two, equal."""
+    got = []
+    for from_file in (False, True):
+        with gpu.Decoder(0) as dec:
+            if from_file:
+                dec.load_file(path, b, e)
+            else:
+                dec.load(s, b, e)
+            dec.decode()
+            rep = dec.report()
+            assert rep.status == 0 and gpu.MODE_NAMES[rep.mode] == {"wsplit": "split"}.get(mode, mode)
+            got.append((int(rep.symbols), dec.download(int(rep.out_bytes))))
+    (sym_h, out_h), (sym_d, out_d) = got
+    assert sym_h == sym_d
+    assert np.array_equal(out_h, out_d)
+    return sym_h, out_h
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", LOADER_STREAMS)
+def test_gpu_load_and_load_device_agree_on_unaligned_shards(gpu, tmp_path, monkeypatch, mode):
+    """The host loader and the device loader share one body: for shards that begin inside
+    a gap word, in every decode mode, both loads decode to the same bytes and report the
+    same symbol count, and the bytes are the input's at the running sum of the symbol
+    counts.  On the wave split the one-segment shard [G - 1, G) takes the last-segment
+    rule's nseg == 1 branch (its start bit is the shard's first_start)."""
+    d, path, s, shards = _loader_case(gpu, tmp_path, mode)
+    monkeypatch.setenv("GH_MODE", mode)
+    off = 0
+    for b, e in shards:
+        sym, out = _both_loads(gpu, mode, s, path, b, e)
+        keep = min(sym, d.size - off)
+        assert out.size >= keep and np.array_equal(out[:keep], d[off: off + keep]), (mode, b, e)
+        off += sym
+    assert off >= d.size
+    if mode == "wsplit":  # (segments own the codewords that start in them: the last one's are the tail)
+        sym, out = _both_loads(gpu, mode, s, path, s.g - 1, s.g)
+        keep = min(sym, d.size - (off - sym))
+        assert np.array_equal(out[:keep], d[off - sym: off - sym + keep])
+
+
 def _load_shards(gpu, path, bounds, concurrent):
     """Loads every shard of `path` into its own context on device 0, one host thread per
     shard (ctypes releases the GIL) or one after another; returns (ms, contexts)."""
