@@ -376,6 +376,13 @@ extern "C" int gh_gather_plan(const gh_index* ix, const gh_range* ranges, uint32
   return GH_OK;
 }
 
+// Piece bound of a device-planned batch (derivation: gaphuff.h): every range has a first
+// and a last piece, and any other piece holds at least 8 * stride of the batch's bytes.
+extern "C" uint64_t gh_gather_piece_bound(uint32_t nranges, uint64_t dst_len, uint32_t log2_stride) {
+  if (log2_stride < GH_INDEX_MIN_LOG2 || log2_stride > GH_INDEX_MAX_LOG2) return 0;
+  return 2ull * nranges + (dst_len >> (log2_stride + 3));
+}
+
 // ---------------------------------------------------------------------------
 // Encoder
 // ---------------------------------------------------------------------------

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "gh_device.hpp"
+#include "gh_gather_range.hpp"
 #include "gh_hip.hpp"
 #include "gh_internal.hpp"
 #include "gh_lut.hpp"
@@ -45,6 +46,7 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 #include "gh_wsplit.hip"
 #include "gh_index.hip"
 #include "gh_gather.hip"
+#include "gh_gather_plan.hip"
 #include "gh_mtile.hip"
 
 }  // namespace gh
@@ -264,6 +266,19 @@ struct Gather {
   std::vector<gh_gather_piece> pieces;
   EventPair ev;
 };
+// Device-planned gather (gh_ctx_gather_device): the resident index lives from
+// gh_ctx_set_index to the next load, the plan's buffers for the life of the context (grown
+// on demand; its pieces are not the host gather's, which may run while one is in flight).
+struct DevGather {
+  bool has_index = false;
+  uint32_t log2_stride = 0;
+  uint64_t nblocks = 0;
+  DevBuf offsets, rank;  // nblocks + 1 entries as aligned u64; gh_gather_range.hpp's rank
+  DevBuf loc, slot, dst0, pieces;
+  Event ev_a, ev_b, ev_c;  // before the plan kernels, after them, after the gather kernel
+  bool enqueued = false;   // a device gather since the load: ev_c marks the last one
+  hipStream_t last_stream = nullptr;
+};
 
 struct Timing {
   std::vector<EventPair> pending, pool;  // timed decodes not yet reported; idle pairs
@@ -280,10 +295,12 @@ struct gh_ctx {
   hipEvent_t done_ev = nullptr;  // marks the last decode: `done`, or the timed decode's end event
   bool loaded = false;
   Canon canon;
-  DevBuf misc;  // u32 [1] status, [2..3] symbol total, [4..11] tile poll counters, [16] gather status
+  DevBuf misc;  // u32 [1] status, [2..3] symbol total, [4..11] tile poll counters, [16] gather status,
+                // device-planned gather: [18] status, [19] piece count, [20..21] bytes, [22..23] pieces (u64)
   Shard shard;
   Plan plan;
   Gather gather;
+  DevGather dgather;
   Timing timing;
   ~gh_ctx();
   unsigned int* misc_at(int i) const { return misc.get<unsigned int>() + i; }
@@ -294,6 +311,10 @@ static void free_shard(gh_ctx* c) {
   c->shard = Shard{};
   c->plan = Plan{};
   c->gather.tab = GatherTables{};
+  c->dgather.has_index = false;  // (releasing device memory waits for a gather still in flight)
+  c->dgather.offsets.reset();
+  c->dgather.rank.reset();
+  c->dgather.enqueued = false;
   c->loaded = false;
 }
 
@@ -713,7 +734,8 @@ extern "C" int gh_ctx_device(gh_ctx* c, int* device) {
 // completion event, whatever stream either was launched on.
 struct DevChain {
   std::mutex mu;
-  hipEvent_t last = nullptr;          // the last tile decode's done_ev (owned by `owner`)
+  hipEvent_t last = nullptr;          // the last tile decode's done_ev, or the end event of a
+                                      // device-planned gather (owned by `owner`)
   const gh_ctx* owner = nullptr;
   bool has = false;
   hipStream_t last_stream = nullptr;  // the stream the last tile kernel ran on
@@ -731,6 +753,7 @@ gh_ctx::~gh_ctx() {
   (void)hipSetDevice(device);
   if (stream) (void)hipStreamSynchronize(stream);
   if (done_rec) (void)hipEventSynchronize(done_ev);
+  if (dgather.enqueued) (void)hipEventSynchronize(dgather.ev_c);  // (it may run on a caller's stream)
   // the device chain must not keep one of this context's events
   DevChain& dc = dev_chain(device);
   std::lock_guard<std::mutex> g(dc.mu);
@@ -1328,6 +1351,206 @@ extern "C" int gh_ctx_gather(gh_ctx* c, const gh_index* ix, const gh_range* rang
   if (status & GH_ST_LAYOUT) return fail(GH_E_HIP, "gather kernel: LDS layout assumption violated");
   if (status & GH_ST_BADCODE) return fail(GH_E_CORRUPT, "gather: invalid code in stream, or the index is another stream's");
   if (kernel_ms) *kernel_ms = ms;
+  return GH_OK;
+}
+
+// ---- device-planned gather (gh_gather_plan.hip) ---------------------------------------
+extern "C" int gh_ctx_set_index(gh_ctx* c, const gh_index* ix) {
+  if (!c || !ix || !ix->offsets) return fail(GH_E_ARG, "null argument");
+  if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_set_index before gh_ctx_load");
+  const Shard& sh = c->shard;
+  DevGather& dg = c->dgather;
+  if (sh.seg_begin != 0 || sh.seg_end != sh.g_total)
+    return fail(GH_E_ARG, "gh_ctx_set_index: the load must cover segments [0, G)");
+  if (ix->n != sh.n_total || ix->g != sh.g_total) return fail(GH_E_ARG, "gh_ctx_set_index: the index is another stream's (N, G)");
+  const uint64_t ibytes = gh_index_bytes(ix->g, ix->log2_stride);
+  if (ibytes == 0 || ix->nentries != (ibytes - 40) / 8) return fail(GH_E_ARG, "gh_ctx_set_index: malformed index");
+  // the entries as aligned u64 (the image's may lie at any address), checked as
+  // gh_index_parse checks them: the kernels' piece arithmetic relies on it
+  std::vector<uint64_t> off(ix->nentries);
+  std::memcpy(off.data(), ix->offsets, 8 * ix->nentries);
+  const uint64_t nblocks = ix->nentries - 1;
+  bool ok = off[0] == 0 && off[nblocks] == ix->n;
+  for (uint64_t k = 0; k < nblocks && ok; ++k) ok = off[k + 1] >= off[k] && off[k + 1] - off[k] <= (143ull << ix->log2_stride);
+  if (!ok) return fail(GH_E_ARG, "gh_ctx_set_index: the entries are not those of a parsed index");
+  std::vector<uint32_t> rank(ix->nentries);  // (nblocks < 2^23: a load holds fewer than 2^31 segments)
+  gr_rank(off.data(), nblocks, rank.data());
+  GH_HIP(hipSetDevice(c->device));
+  if (dg.enqueued) GH_HIP(hipEventSynchronize(dg.ev_c));  // a gather in flight reads the old entries
+  dg.has_index = false;
+  if (int rc = dg.offsets.upload(off.data(), 8 * ix->nentries)) return rc;
+  if (int rc = dg.rank.upload(rank.data(), 4 * ix->nentries)) return rc;
+  dg.nblocks = nblocks;
+  dg.log2_stride = ix->log2_stride;
+  dg.has_index = true;
+  return GH_OK;
+}
+
+// Enqueues the plan kernels and the gather kernel and returns.  Device waits on this path:
+// none when the tables exist and the buffers are large enough.  The exceptions: the first
+// gather after a load (gather_setup reads the stream's last words back), a buffer that has
+// to grow (the last gather in flight still uses the old one), and nothing else: the
+// context's own decodes are not waited for, since the gather reads only the loaded stream
+// and writes only its own buffers, status words and d_dst.
+extern "C" int gh_ctx_gather_device(gh_ctx* c, const gh_range* d_ranges, uint32_t nranges, void* d_dst,
+                                    uint64_t dst_len, void* hip_stream) {
+  if (!c) return fail(GH_E_ARG, "null ctx");
+  if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_gather_device before gh_ctx_load");
+  DevGather& dg = c->dgather;
+  if (!dg.has_index) return fail(GH_E_STATE, "gh_ctx_gather_device without a resident index (gh_ctx_set_index)");
+  if (nranges == 0) return GH_OK;
+  if (!d_ranges || !d_dst) return fail(GH_E_ARG, "null argument");
+  if (nranges > GH_GATHER_MAX_RANGES) return fail(GH_E_ARG, "gh_ctx_gather_device: more than 2^24 ranges in one batch");
+  // (the gather kernel counts pieces in 32 bits)
+  const uint64_t cap = std::min<uint64_t>(gh_gather_piece_bound(nranges, dst_len, dg.log2_stride), (1ull << 31) - 1);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream;
+  GH_HIP(hipSetDevice(c->device));
+  Gather& ga = c->gather;
+  // (a stream without segments has N = 0: the plan kernels alone run, and refuse every
+  // range that is not empty)
+  const bool has_segments = c->shard.nseg > 0;
+  if (has_segments && !ga.tab.ready)
+    if (int rc = gather_setup(c)) return rc;
+  const GatherTables& t = ga.tab;
+  if (int rc = dg.ev_a.create()) return rc;
+  if (int rc = dg.ev_b.create()) return rc;
+  if (int rc = dg.ev_c.create()) return rc;
+  if (dg.loc.capacity() < nranges * sizeof(RangeLoc) || dg.pieces.capacity() < cap * sizeof(gh_gather_piece)) {
+    if (dg.enqueued) GH_HIP(hipEventSynchronize(dg.ev_c));
+    if (int rc = dg.loc.reserve(nranges * sizeof(RangeLoc))) return rc;
+    if (int rc = dg.slot.reserve(nranges * 4ull)) return rc;
+    if (int rc = dg.dst0.reserve(nranges * 8ull)) return rc;
+    if (int rc = dg.pieces.reserve(cap * sizeof(gh_gather_piece))) return rc;
+  }
+  GplanParams pp{};
+  pp.ranges = d_ranges;
+  pp.offsets = dg.offsets.get<uint64_t>();
+  pp.rank = dg.rank.get<uint32_t>();
+  pp.loc = dg.loc.get<RangeLoc>();
+  pp.slot = dg.slot.get<uint32_t>();
+  pp.dst0 = dg.dst0.get<unsigned long long>();
+  pp.pieces = dg.pieces.get<gh_gather_piece>();
+  pp.status = c->misc_at(18);
+  pp.npieces = c->misc_at(19);
+  pp.totals = (unsigned long long*)c->misc_at(20);
+  pp.nblocks = dg.nblocks;
+  pp.n = c->shard.n_total;
+  pp.cap = cap;
+  pp.dst_len = dst_len;
+  pp.nranges = nranges;
+  GatherParams gp{};
+  gp.w = shard_params(c);
+  gp.w.lut = t.lut_c.get<uint2>();
+  gp.w.out = (uint8_t*)d_dst;
+  gp.w.status = pp.status;
+  gp.w.kbits = t.kc;
+  gp.w.lut_bytes = (uint32_t)(4u << t.kc);
+  gp.w.last_end = t.last_end;
+  gp.w.fb = t.fb.get<uint32_t>();
+  gp.pieces = pp.pieces;
+  gp.sym_lut = t.lut_s.get<uint32_t>();
+  gp.d_npieces = pp.npieces;
+  gp.log2_stride = dg.log2_stride;
+  gp.sym_bits = t.ks;
+  // the host knows only the bound: every workgroup that could have a piece, at most what
+  // the device holds at once
+  uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(t.wgs, 1), ceil_div(cap, (uint64_t)(GA_TB / 64)));
+  if (const char* eg = getenv("GH_GATHER_GRID"))  // tests: few workgroups, many pieces per wave
+    grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
+  const uint32_t grid_r = (uint32_t)ceil_div((uint64_t)nranges, (uint64_t)GP_TB);
+  const uint32_t grid_e = (uint32_t)std::min<uint64_t>(ceil_div(cap, (uint64_t)GP_TB), 1024);
+  void* pa[1] = {&pp};
+  void* args[1] = {&gp};
+  // A member of the device's decode chain, without holding it: the lock is taken only
+  // while enqueuing.  The gather starts after the device's last tile decode (or chain
+  // member), and its end event becomes the chain's last, so the next tile decode of any
+  // context starts after the gather.
+  DevChain& dc = dev_chain(c->device);
+  std::lock_guard<std::mutex> chain_lock(dc.mu);
+  const bool ordered = dc.owner == c && dc.last_stream == st && st == c->stream;
+  if (dc.has && !ordered) GH_HIP(hipStreamWaitEvent(st, dc.last, 0));
+  // (the context's gathers share the plan's buffers: in turn, whatever their streams)
+  if (dg.enqueued && dg.last_stream != st) GH_HIP(hipStreamWaitEvent(st, dg.ev_c, 0));
+  GH_HIP(hipEventRecord(dg.ev_a, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_gplan_locate_kernel, dim3(grid_r), dim3(GP_TB), pa, 0, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_gplan_scan_kernel, dim3(1), dim3(GP_SCAN_TB), pa, 0, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_gplan_emit_kernel, dim3(grid_e), dim3(GP_TB), pa, 0, st));
+  GH_HIP(hipEventRecord(dg.ev_b, st));
+  if (has_segments) GH_HIP(hipLaunchKernel(t.kern, dim3(grid), dim3(GA_TB), args, t.lds, st));
+  GH_HIP(hipGetLastError());
+  GH_HIP(hipEventRecord(dg.ev_c, st));
+  dg.enqueued = true;
+  dg.last_stream = st;
+  dc.last = dg.ev_c;
+  dc.owner = c;
+  dc.has = true;
+  dc.last_stream = st;
+  return GH_OK;
+}
+
+// Waits for the last device gather and reads its words of misc: [18] status, [19] piece
+// count, [20..21] bytes.
+static int dgather_result(gh_ctx* c, const char* who, unsigned int* status, uint64_t* np, uint64_t* bytes) {
+  if (!c) return fail(GH_E_ARG, "null ctx");
+  if (!c->dgather.enqueued) return fail(GH_E_STATE, std::string(who) + ": no device gather since the load");
+  GH_HIP(hipSetDevice(c->device));
+  GH_HIP(hipEventSynchronize(c->dgather.ev_c));
+  unsigned int m[4] = {};
+  GH_HIP(hipMemcpy(m, c->misc_at(18), sizeof(m), hipMemcpyDeviceToHost));
+  *status = m[0];
+  *np = m[1];
+  std::memcpy(bytes, m + 2, 8);
+  return GH_OK;
+}
+
+// Event times of the last device gather, once it has finished: plan kernels, gather kernel.
+static int dgather_times(const gh_ctx* c, float* plan_ms, float* gather_ms) {
+  GH_HIP(hipEventElapsedTime(plan_ms, c->dgather.ev_a, c->dgather.ev_b));
+  GH_HIP(hipEventElapsedTime(gather_ms, c->dgather.ev_b, c->dgather.ev_c));
+  return GH_OK;
+}
+
+extern "C" int gh_ctx_gather_times(gh_ctx* c, float* plan_ms, float* gather_ms) {
+  unsigned int status;
+  uint64_t np, bytes;
+  if (int rc = dgather_result(c, "gh_ctx_gather_times", &status, &np, &bytes)) return rc;
+  float a = 0, b = 0;
+  if (int rc = dgather_times(c, &a, &b)) return rc;
+  if (plan_ms) *plan_ms = a;
+  if (gather_ms) *gather_ms = b;
+  return GH_OK;
+}
+
+extern "C" int gh_ctx_gather_wait(gh_ctx* c, gh_gather_report* rep) {
+  if (rep) std::memset(rep, 0, sizeof(*rep));
+  unsigned int status;
+  uint64_t np, bytes;
+  if (int rc = dgather_result(c, "gh_ctx_gather_wait", &status, &np, &bytes)) return rc;
+  float a = 0, b = 0;
+  if (int rc = dgather_times(c, &a, &b)) return rc;
+  if (rep) {
+    rep->out_bytes = bytes;
+    rep->npieces = np;
+    rep->status = status;
+    rep->kernel_ms = a + b;
+  }
+  if (status & GH_ST_RANGE) return fail(GH_E_ARG, "device gather: a byte range outside [0, N]");
+  if (status & GH_ST_DSTSMALL) return fail(GH_E_SMALL, "device gather: destination smaller than the ranges' bytes");
+  if (status & GH_ST_PIECES) return fail(GH_E_CORRUPT, "device gather: the plan exceeds the piece bound (the index is no real stream's)");
+  if (status & GH_ST_LAYOUT) return fail(GH_E_HIP, "gather kernel: LDS layout assumption violated");
+  if (status & GH_ST_BADCODE) return fail(GH_E_CORRUPT, "gather: invalid code in stream, or the index is another stream's");
+  return GH_OK;
+}
+
+extern "C" int gh_ctx_gather_pieces(gh_ctx* c, gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces) {
+  if (!npieces || (cap && !pieces)) return fail(GH_E_ARG, "null argument");
+  *npieces = 0;
+  unsigned int status;
+  uint64_t np, bytes;
+  if (int rc = dgather_result(c, "gh_ctx_gather_pieces", &status, &np, &bytes)) return rc;
+  *npieces = np;
+  if (np > cap) return fail(GH_E_SMALL, "piece buffer smaller than the plan");
+  if (np) GH_HIP(hipMemcpy(pieces, c->dgather.pieces.get(), np * sizeof(gh_gather_piece), hipMemcpyDeviceToHost));
   return GH_OK;
 }
 

@@ -25,13 +25,15 @@
 // planner asks for no position at or past N, so the clip at b covers them.
 //
 // gp.w carries the stream, the count table (lut, kbits, lut_bytes) and the fallback
-// tables as IdxParams.w does, and the gather's output buffer in `out`.
+// tables as IdxParams.w does, and the gather's output buffer in `out`.  The piece count is
+// gp.npieces, or *gp.d_npieces when the plan was built on the device (gh_gather_plan.hip).
 
 struct GatherParams {
   WsParams w;
   const gh_gather_piece* pieces;
   const uint32_t* sym_lut;  // 1 << sym_bits entries {len | symbol << 8}; 0: no codeword of <= sym_bits bits
   uint32_t npieces;
+  const uint32_t* d_npieces;  // non-null: the piece count lies in device memory (the device plan's)
   uint32_t log2_stride;     // log2 segments per index block, >= 8
   uint32_t sym_bits;        // 2 .. 12
 };
@@ -59,13 +61,15 @@ __global__ __launch_bounds__(TBK) void gh_gather_kernel(const GatherParams gp) {
   check_lds_base(smem, p.status);
   __syncthreads();
   const uint32_t nw = gridDim.x * (uint32_t)(TBK / 64);
+  // (the grid of a device-planned gather is sized by a bound: a wave may find no piece)
+  const uint32_t npieces = gp.d_npieces ? (uint32_t)__builtin_amdgcn_readfirstlane((int)*gp.d_npieces) : gp.npieces;
   const uint32_t nb = (p.nseg + 64 * U - 1) / (64 * U);  // wave blocks of the stream
   const uint32_t bpi = 1u << (gp.log2_stride - 8u);      // wave blocks per index block
   uint4 w[U];
   uint32_t w4[U], ga[U], gb[U];
   uint32_t have = 0xFFFFFFFFu;  // the wave block whose words w holds (wave-uniform)
   bool cut = false;             // a walk ran out of segments before its b
-  for (unsigned long long i = blockIdx.x * (uint32_t)(TBK / 64) + (uint32_t)(tid >> 6); i < gp.npieces; i += nw) {
+  for (unsigned long long i = blockIdx.x * (uint32_t)(TBK / 64) + (uint32_t)(tid >> 6); i < npieces; i += nw) {
     const gh_gather_piece pc = gp.pieces[i];
     const uint32_t pa = (uint32_t)__builtin_amdgcn_readfirstlane((int)pc.a);
     const uint32_t pb = (uint32_t)__builtin_amdgcn_readfirstlane((int)pc.b);
@@ -73,7 +77,7 @@ __global__ __launch_bounds__(TBK) void gh_gather_kernel(const GatherParams gp) {
     const unsigned long long dst = rfl_u64(pc.dst);
     // the first wave block of the wave's next piece (prefetched behind this piece's last)
     uint32_t nxt = kb;
-    if (i + nw < gp.npieces) nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)gp.pieces[i + nw].block);
+    if (i + nw < npieces) nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)gp.pieces[i + nw].block);
     const uint32_t nxt0 = (uint32_t)min((unsigned long long)nxt * bpi, (unsigned long long)(nb - 1u));
     if ((unsigned long long)kb * bpi >= nb) {  // no such block in this stream
       cut = true;

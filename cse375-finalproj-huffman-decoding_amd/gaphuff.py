@@ -37,6 +37,9 @@ GH_ERRORS = {
 GH_V2_MAGIC = 0x0032465548504147
 GH_ST_BADCODE = 1
 GH_ST_TIMEOUT = 2
+GH_ST_LAYOUT = 4
+GH_ST_RANGE, GH_ST_DSTSMALL, GH_ST_PIECES = 8, 16, 32  # device-planned gather
+GH_GATHER_MAX_RANGES = 1 << 24
 
 # Every symbol include/gaphuff.h declares (checked by tests/test_abi.py).
 EXPORTED = (
@@ -54,6 +57,8 @@ EXPORTED = (
     "gh_encode_plan_from_counts", "gh_encode_bound", "gh_slice_extent", "gh_encode_slice",
     "gh_encode_image_init", "gh_slice_merge", "gh_ectx_counts", "gh_ectx_encode_slice",
     "gh_ectx_download_slice", "gh_encode_sharded",
+    "gh_ctx_set_index", "gh_gather_piece_bound", "gh_ctx_gather_device", "gh_ctx_gather_wait",
+    "gh_ctx_gather_times", "gh_ctx_gather_pieces",
 )
 
 
@@ -122,6 +127,11 @@ class gh_range(ctypes.Structure):
 class gh_gather_piece(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_uint64), ("block", ctypes.c_uint32), ("a", ctypes.c_uint32),
                 ("b", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class gh_gather_report(ctypes.Structure):
+    _fields_ = [("out_bytes", ctypes.c_uint64), ("npieces", ctypes.c_uint64), ("status", ctypes.c_uint32),
+                ("kernel_ms", ctypes.c_float)]
 
 
 class gh_sync_report(ctypes.Structure):
@@ -195,6 +205,12 @@ def lib() -> ctypes.CDLL:
             "gh_ctx_build_index": ([P, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_float)], I),
             "gh_gather_plan": ([ctypes.POINTER(gh_index), P, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(U64)], I),
             "gh_ctx_gather": ([P, ctypes.POINTER(gh_index), P, U32, P, U64, P, ctypes.POINTER(ctypes.c_float)], I),
+            "gh_ctx_set_index": ([P, ctypes.POINTER(gh_index)], I),
+            "gh_gather_piece_bound": ([U32, U64, U32], U64),
+            "gh_ctx_gather_device": ([P, P, U32, P, U64, P], I),
+            "gh_ctx_gather_wait": ([P, ctypes.POINTER(gh_gather_report)], I),
+            "gh_ctx_gather_times": ([P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)], I),
+            "gh_ctx_gather_pieces": ([P, P, U64, ctypes.POINTER(U64)], I),
             "gh_encode_index": ([P, ctypes.POINTER(gh_encode_plan), U32, I, P, U64], I),
             "gh_ectx_index": ([P, U32, P, U64, ctypes.POINTER(ctypes.c_float)], I),
             "gh_encode_plan_from_counts": ([P, I, ctypes.POINTER(gh_encode_plan)], I),
@@ -615,6 +631,50 @@ class Decoder:
                                    ctypes.c_void_p(hip_stream or None), ctypes.byref(ms)))
         return (total if out is None else out), float(ms.value)
 
+    def set_index(self, index) -> None:
+        """Keep the entries of ``index`` (an :class:`Index` or a sidecar image) on the device
+        for :meth:`gather_device` (gh_ctx_set_index); the next load drops them."""
+        ix = index if isinstance(index, Index) else parse_index(index)
+        _check(lib().gh_ctx_set_index(self._h, ctypes.byref(ix.c)))
+
+    def gather_device(self, ranges_ptr: int, nranges: int, dst_ptr: int, dst_len: int, hip_stream: int = 0) -> None:
+        """Enqueue the gather of ``nranges`` (lo, hi) pairs held in device memory at
+        ``ranges_ptr`` (a contiguous int64/uint64 [n, 2] array) into the ``dst_len`` device
+        bytes at ``dst_ptr``, planned on the GPU, and return without waiting
+        (gh_ctx_gather_device).  Addresses are integers (``tensor.data_ptr()``,
+        ``DeviceBuffer.addr``).  What only the device finds is raised by :meth:`gather_wait`."""
+        _check(lib().gh_ctx_gather_device(self._h, ctypes.c_void_p(ranges_ptr or None), nranges,
+                                          ctypes.c_void_p(dst_ptr or None), dst_len,
+                                          ctypes.c_void_p(hip_stream or None)))
+
+    def gather_wait(self) -> gh_gather_report:
+        """Wait for the last :meth:`gather_device` and return its report; raises
+        :class:`GapHuffError` (with the report as ``.report``) on a device-side refusal."""
+        r = gh_gather_report()
+        rc = lib().gh_ctx_gather_wait(self._h, ctypes.byref(r))
+        if rc != GH_OK:
+            e = GapHuffError(rc, lib().gh_last_error().decode(errors="replace"))
+            e.report = r
+            raise e
+        return r
+
+    def gather_times(self):
+        """(plan kernels ms, gather kernel ms) of the last :meth:`gather_device`."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(lib().gh_ctx_gather_times(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return float(a.value), float(b.value)
+
+    def gather_pieces(self) -> np.ndarray:
+        """The pieces of the last :meth:`gather_device` as the record array
+        :meth:`Index.plan` returns (gh_ctx_gather_pieces)."""
+        n = ctypes.c_uint64()
+        rc = lib().gh_ctx_gather_pieces(self._h, None, 0, ctypes.byref(n))
+        if rc not in (GH_OK, -9):
+            _check(rc)
+        pieces = np.zeros(int(n.value), dtype=PIECE_DTYPE)
+        _check(lib().gh_ctx_gather_pieces(self._h, _ptr(pieces), pieces.size, ctypes.byref(n)))
+        return pieces
+
     def reset_timing(self) -> None:
         _check(lib().gh_ctx_reset_timing(self._h))
 
@@ -708,6 +768,11 @@ def _ranges(ranges) -> np.ndarray:
     if r.shape[0] >= 1 << 32:
         raise GapHuffError(-1, "2^32 or more ranges in one batch")
     return r
+
+
+def gather_piece_bound(nranges: int, dst_len: int, log2_stride: int) -> int:
+    """Pieces a device-planned batch can need (gh_gather_piece_bound); 0 on a bad stride."""
+    return int(lib().gh_gather_piece_bound(nranges, dst_len, log2_stride))
 
 
 def parse_index(image) -> Index:

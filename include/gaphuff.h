@@ -395,6 +395,70 @@ int gh_gather_plan(const gh_index* ix, const gh_range* ranges, uint32_t nranges,
 int gh_ctx_gather(gh_ctx* ctx, const gh_index* ix, const gh_range* ranges, uint32_t nranges,
                   void* dst, uint64_t dst_len, void* hip_stream, float* kernel_ms);
 
+/* Device-planned gather: the ranges and the destination are device memory, the index is
+ * resident in the context, the plan (the pieces gh_gather_plan would cut, in the same
+ * order) is built by kernels, and the call only enqueues: for callers that hold their row
+ * ids on the GPU, on a stream that must not stall.  No reference counterpart. */
+/* Keep the index's entries on the context's device.  The checks of gh_ctx_gather: the load
+ * covers [0, G), ix->n / ix->g are the stream's, nentries matches gh_index_bytes (GH_E_ARG
+ * otherwise, also when the entries do not start at 0, end at N and never decrease by
+ * steps of at most 143 * stride); GH_E_STATE before a load.  The next load drops the
+ * index; setting it again replaces it.  Synchronous (two uploads). */
+int gh_ctx_set_index(gh_ctx* ctx, const gh_index* ix);
+/* Status bits of a device-planned gather, beside GH_ST_BADCODE and GH_ST_LAYOUT. */
+#define GH_ST_RANGE 8u       /* some range has lo > hi or hi > N                   */
+#define GH_ST_DSTSMALL 16u   /* the batch's bytes exceed dst_len                   */
+#define GH_ST_PIECES 32u     /* the plan would exceed the piece buffer             */
+typedef struct gh_gather_report {
+  uint64_t out_bytes;  /* sum of hi - lo over the batch (its valid ranges)   */
+  uint64_t npieces;    /* pieces the device plan produced (0: refused)       */
+  uint32_t status;     /* device status bits of the gather (GH_ST_*)         */
+  float kernel_ms;     /* HIP events: plan kernels + gather kernel           */
+} gh_gather_report;
+/* Ranges in one device-planned batch, at most. */
+#define GH_GATHER_MAX_RANGES (1u << 24)
+/* Pieces a batch of nranges ranges that fits dst_len bytes can need: the host cannot know
+ * the piece count of ranges it never sees, so the piece buffer is sized by this bound,
+ *   2 * nranges + dst_len / (8 * stride),   stride = 1 << log2_stride segments.
+ * A piece that is neither the first nor the last of its range covers a whole index block
+ * that is not the stream's last; the block spans 128 * stride bits wholly inside the code
+ * bits; no codeword is longer than 16 bits, so at least 8 * stride codewords start in it,
+ * and the piece gives that many of the batch's bytes.  gh_index_parse enforces no minimum
+ * step, so an index that belongs to no real stream can break the bound: the device plan
+ * checks its piece count against the buffer and refuses (GH_ST_PIECES) instead of
+ * writing.  Monotone in nranges and dst_len; 0 on a stride outside the range.  No device. */
+uint64_t gh_gather_piece_bound(uint32_t nranges, uint64_t dst_len, uint32_t log2_stride);
+/* Enqueue the gather of d_ranges[0 .. nranges) ({u64 lo, u64 hi} in device memory: a
+ * contiguous int64[n, 2] tensor) into d_dst (device memory, dst_len bytes) on hip_stream
+ * (NULL = the context's stream), and return.  Range i's bytes start at
+ * sum_{j<i} (hi_j - lo_j) of d_dst, as gh_ctx_gather's, and the kernels store them there
+ * directly.  d_ranges and d_dst must stay as they are until the gather has finished.
+ * The call waits for the device only when it is the first gather after a load (it builds
+ * the tables) or when a context buffer has to grow (the piece buffer holds
+ * min(gh_gather_piece_bound, 2^31 - 1) pieces); a repeated call with the same or a smaller
+ * nranges and dst_len allocates nothing.  It does not wait for the context's decodes: it
+ * reads only the loaded stream.  Calls on one context run in the order they were made,
+ * whatever their streams.  nranges = 0: GH_OK, nothing is launched.
+ * GH_E_STATE before a load or without a resident index; GH_E_ARG: a null pointer, more
+ * than GH_GATHER_MAX_RANGES ranges.  What only the device can find is returned by
+ * gh_ctx_gather_wait. */
+int gh_ctx_gather_device(gh_ctx* ctx, const gh_range* d_ranges, uint32_t nranges,
+                         void* d_dst, uint64_t dst_len, void* hip_stream);
+/* Wait for the context's last device gather and report it (rep may be NULL; it is filled
+ * before an error is returned).  GH_E_ARG: some range had lo > hi or hi > N; GH_E_SMALL:
+ * the batch's bytes exceed dst_len; GH_E_CORRUPT: GH_ST_BADCODE, or the plan would exceed
+ * the piece buffer; GH_E_HIP: GH_ST_LAYOUT.  After GH_E_ARG, GH_E_SMALL and a piece-buffer
+ * overflow not one byte of d_dst has been written.  GH_E_STATE when no device gather has
+ * been enqueued since the load. */
+int gh_ctx_gather_wait(gh_ctx* ctx, gh_gather_report* rep);
+/* The HIP-event times of the last device gather's plan kernels and of its gather kernel
+ * (their sum is gh_gather_report.kernel_ms); waits like gh_ctx_gather_wait.  Either
+ * pointer may be NULL. */
+int gh_ctx_gather_times(gh_ctx* ctx, float* plan_ms, float* gather_ms);
+/* Pieces of the last device gather, copied to host memory (tests, diagnosis); waits for
+ * it.  *npieces is always written; GH_E_SMALL when cap is smaller. */
+int gh_ctx_gather_pieces(gh_ctx* ctx, gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces);
+
 /* ---- self-synchronising decode of gap-less streams ---- */
 /* Replaces CUHD's decoder for raw Huffman streams without a gap array
  * (gpuhd/src/cuhd_gpu_decoder.cu:145-523, CUHDGPUDecoder::decode declared at
