@@ -651,51 +651,136 @@ size_t gh::index_header(uint32_t log2_stride, uint64_t n, uint64_t g, uint64_t n
   return IDX_HEADER;
 }
 
-// The seek index of the stream gh_encode_write produces, from the input alone: the
-// encoder knows every codeword's first bit, so offsets[k] = the first i with start(i) >=
-// 128 * stride * k falls out of a walk over the code lengths.  Threaded as
-// gh_encode_write: per-thread bit totals, a scan, then thread t resolves the boundaries
-// inside its bit range [tbits[t], tbits[t + 1]); every boundary lies below the stream's
-// bit total (k * stride < G), so each has exactly one such thread.
+// Which index entries a slice owns (gaphuff.h, "the index of a sliced stream"): the
+// boundaries S * k inside its bits [base_bit, base_bit + bits).
+extern "C" int gh_index_slice_extent(uint64_t base_bit, uint64_t bits, uint32_t log2_stride, uint64_t* k0,
+                                     uint64_t* nk) {
+  if (!k0 || !nk) return fail(GH_E_ARG, "null argument");
+  if (log2_stride < GH_INDEX_MIN_LOG2 || log2_stride > GH_INDEX_MAX_LOG2)
+    return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
+  if (base_bit + bits < base_bit) return fail(GH_E_ARG, "slice end overflows 64 bits");
+  const uint32_t sh = 7 + log2_stride;  // S = 1 << sh
+  auto ceil_s = [&](uint64_t x) { return (x >> sh) + ((x & ((1ull << sh) - 1)) != 0); };
+  *k0 = ceil_s(base_bit);
+  *nk = ceil_s(base_bit + bits) - *k0;
+  return GH_OK;
+}
+
+// The host index walk's body: the entries the bytes in[0..n) own as the slice at base_bit /
+// sym_base (gaphuff.h); the whole stream is the slice at bit 0 / symbol 0.  The encoder
+// knows every codeword's first bit, so entry k = sym_base + the first i with start(i) >=
+// S * k falls out of a walk over the code lengths.  Threaded as the encode: per-thread bit
+// totals, a scan, then thread t resolves the boundaries inside its bit range
+// [base_bit + tbits[t], base_bit + tbits[t + 1]); the threads' ranges partition the
+// slice's bits, so every owned boundary has exactly one such thread.  ent: 8 * cap bytes
+// at any alignment, entry k at ent + 8 * (k - *k0).  want_bits (may be NULL): the bit
+// total the input must have, checked before anything is written.
+static int index_slice_body(const uint8_t* in, uint64_t n, const gh_encode_plan* plan, uint64_t base_bit,
+                            uint64_t sym_base, uint32_t log2_stride, int threads, uint8_t* ent, uint64_t cap,
+                            uint64_t* k0, uint64_t* nk, const uint64_t* want_bits) {
+  const uint64_t S = (uint64_t)GH_SEGMENT_BITS << log2_stride;
+  const int nt = (int)std::min<uint64_t>(n_threads(threads), std::max<uint64_t>(1, n >> 20));
+  std::vector<uint64_t> tbits(nt + 1, 0);
+  std::atomic<bool> absent{false};
+  parallel_for(nt, [&](int t) {
+    const uint64_t a = n * t / nt, b = n * (t + 1) / nt;
+    uint64_t s = 0;
+    bool zero = false;
+    for (uint64_t i = a; i < b; ++i) {
+      const uint32_t l = plan->len[in[i]];
+      zero |= l == 0;
+      s += l;
+    }
+    tbits[t + 1] = s;
+    if (zero) absent = true;
+  });
+  if (absent) return fail(GH_E_TABLE, "a byte of the input has no code in the plan");
+  for (int t = 0; t < nt; ++t) tbits[t + 1] += tbits[t];
+  const uint64_t bits = tbits[nt];
+  if (want_bits && bits != *want_bits) return fail(GH_E_ARG, "input does not match the plan");
+  if (base_bit + bits < base_bit || base_bit + bits > plan->bits)
+    return fail(GH_E_ARG, "slice ends past the plan's bit total");
+  if (int rc = gh_index_slice_extent(base_bit, bits, log2_stride, k0, nk)) return rc;
+  if (cap < *nk) return fail(GH_E_SMALL, "entry buffer too small");
+  const uint64_t kbase = *k0;
+  parallel_for(nt, [&](int t) {
+    const uint64_t a = n * t / nt, b = n * (t + 1) / nt;
+    const uint64_t lo = base_bit + tbits[t], hi = base_bit + tbits[t + 1];
+    uint64_t k = ceil_div(lo, S);  // the first boundary at or past this thread's first bit
+    if (k * S >= hi) return;
+    uint64_t pos = lo;
+    for (uint64_t i = a; i < b; ++i) {
+      if (pos >= k * S) {  // (codewords are shorter than a stride: at most one boundary)
+        wr<uint64_t>(ent + 8 * (k - kbase), sym_base + i);
+        if (++k * S >= hi) return;
+      }
+      pos += plan->len[in[i]];
+    }
+    // boundaries inside the thread's last codeword: the next thread's (or slice's) first symbol
+    for (; k * S < hi; ++k) wr<uint64_t>(ent + 8 * (k - kbase), sym_base + b);
+  });
+  return GH_OK;
+}
+
+extern "C" int gh_encode_index_slice(const uint8_t* in, uint64_t n, const gh_encode_plan* plan, uint64_t base_bit,
+                                     uint64_t sym_base, uint32_t log2_stride, int threads, uint64_t* entries,
+                                     uint64_t cap, uint64_t* k0, uint64_t* nk) {
+  if (!plan || !k0 || !nk || (n && !in) || (cap && !entries)) return fail(GH_E_ARG, "null argument");
+  if (log2_stride < GH_INDEX_MIN_LOG2 || log2_stride > GH_INDEX_MAX_LOG2)
+    return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
+  return index_slice_body(in, n, plan, base_bit, sym_base, log2_stride, threads, (uint8_t*)entries, cap, k0, nk,
+                          nullptr);
+}
+
+extern "C" int gh_index_image_init(const gh_encode_plan* plan, uint32_t log2_stride, void* image,
+                                   uint64_t image_len) {
+  if (!plan || !image) return fail(GH_E_ARG, "null argument");
+  const uint64_t bytes = gh_index_bytes(plan->g, log2_stride);
+  if (bytes == 0) return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
+  if (image_len < bytes) return fail(GH_E_SMALL, "index buffer too small");
+  uint8_t* out = (uint8_t*)image;
+  const uint64_t nentries = (bytes - IDX_HEADER) / 8;
+  uint8_t* ent = out + gh::index_header(log2_stride, plan->n, plan->g, nentries, out);
+  std::memset(ent, 0, 8 * (nentries - 1));
+  wr<uint64_t>(ent + 8 * (nentries - 1), plan->n);
+  return GH_OK;
+}
+
+// A bounds-checked store against the image's own header: the owned entries of different
+// slices are disjoint (gaphuff.h), so nothing is combined.
+extern "C" int gh_index_slice_merge(void* image, uint64_t image_len, uint64_t k0, uint64_t nk,
+                                    const uint64_t* entries) {
+  if (!image || (nk && !entries)) return fail(GH_E_ARG, "null argument");
+  uint8_t* p = (uint8_t*)image;
+  if (image_len < IDX_HEADER) return fail(GH_E_SMALL, "index image shorter than its header");
+  if (rd<uint64_t>(p) != GH_INDEX_MAGIC) return fail(GH_E_FORMAT, "not a seek index (magic)");
+  const uint64_t bytes = gh_index_bytes(rd<uint64_t>(p + 24), rd<uint32_t>(p + 8));
+  if (bytes == 0 || rd<uint64_t>(p + 32) != (bytes - IDX_HEADER) / 8)
+    return fail(GH_E_FORMAT, "index: entry count does not match G and the stride");
+  if (image_len < bytes) return fail(GH_E_SMALL, "index image shorter than its entries");
+  const uint64_t nblocks = (bytes - IDX_HEADER) / 8 - 1;  // the terminal entry belongs to no slice
+  if (k0 > nblocks || nk > nblocks - k0) return fail(GH_E_ARG, "slice entries outside the index");
+  if (nk) std::memcpy(p + IDX_HEADER + 8 * k0, entries, 8 * nk);
+  return GH_OK;
+}
+
+// The seek index of the stream gh_encode_write produces, from the input alone: the image
+// of gh_index_image_init with the entries of the slice at bit 0 / symbol 0, which owns
+// every entry k < nblocks (every boundary lies below the stream's bit total: k * stride
+// < G).
 extern "C" int gh_encode_index(const uint8_t* in, const gh_encode_plan* plan, uint32_t log2_stride,
                                int threads, void* out_v, uint64_t out_len) {
   if (!plan || !out_v || (plan->n && !in)) return fail(GH_E_ARG, "null argument");
   const uint64_t bytes = gh_index_bytes(plan->g, log2_stride);
   if (bytes == 0) return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
   if (out_len < bytes) return fail(GH_E_SMALL, "index buffer too small");
-  uint8_t* out = (uint8_t*)out_v;
-  const uint64_t n = plan->n;
-  const uint64_t S = (uint64_t)GH_SEGMENT_BITS << log2_stride;
+  if (ceil_div(plan->bits, GH_SEGMENT_BITS) != plan->g) return fail(GH_E_ARG, "input does not match the plan");
+  if (int rc = gh_index_image_init(plan, log2_stride, out_v, out_len)) return rc;
   const uint64_t nblocks = (bytes - IDX_HEADER) / 8 - 1;
-  const int nt = (int)std::min<uint64_t>(n_threads(threads), std::max<uint64_t>(1, n >> 20));
-  std::vector<uint64_t> tbits(nt + 1, 0);
-  parallel_for(nt, [&](int t) {
-    const uint64_t a = n * t / nt, b = n * (t + 1) / nt;
-    uint64_t s = 0;
-    for (uint64_t i = a; i < b; ++i) s += plan->len[in[i]];
-    tbits[t + 1] = s;
-  });
-  for (int t = 0; t < nt; ++t) tbits[t + 1] += tbits[t];
-  if (tbits[nt] != plan->bits || ceil_div(tbits[nt], GH_SEGMENT_BITS) != plan->g)
-    return fail(GH_E_ARG, "input does not match the plan");
-  uint8_t* ent = out + gh::index_header(log2_stride, n, plan->g, nblocks + 1, out);
-  parallel_for(nt, [&](int t) {
-    const uint64_t a = n * t / nt, b = n * (t + 1) / nt;
-    const uint64_t lo = tbits[t], hi = tbits[t + 1];
-    uint64_t k = ceil_div(lo, S);  // the first boundary at or past this thread's first bit
-    if (k >= nblocks || k * S >= hi) return;
-    uint64_t pos = lo;
-    for (uint64_t i = a; i < b; ++i) {
-      if (pos >= k * S) {  // (codewords are shorter than a stride: at most one boundary)
-        wr<uint64_t>(ent + 8 * k, i);
-        if (++k >= nblocks || k * S >= hi) return;
-      }
-      pos += plan->len[in[i]];
-    }
-    // boundaries inside the thread's last codeword: the next thread's first symbol
-    for (; k < nblocks && k * S < hi; ++k) wr<uint64_t>(ent + 8 * k, b);
-  });
-  wr<uint64_t>(ent + 8 * nblocks, n);
+  uint64_t k0 = 0, nk = 0;
+  const int rc = index_slice_body(in, plan->n, plan, 0, 0, log2_stride, threads, (uint8_t*)out_v + IDX_HEADER,
+                                  nblocks, &k0, &nk, &plan->bits);
+  if (rc) return fail(GH_E_ARG, "input does not match the plan");
   return GH_OK;
 }
 

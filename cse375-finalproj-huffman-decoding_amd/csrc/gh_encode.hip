@@ -28,9 +28,12 @@
 //                        atomicOr-ed into the zeroed gap array, the rest stored.
 //   gh_enc_index_kernel  (gh_ectx_index, after an encode) the seek index from the chunk
 //                        offsets: see the kernel.
+//   gh_enc_merge_kernel  (gh_ectx_merge_device) ORs an encode's words and gap words into
+//                        the stream's device-resident arrays: see enc_merge_span.
 // Sliced encode (gh_ectx_encode_slice): the same kernels on an input that is one slice of
 // a longer stream; the block scan starts at the slice's first stream bit and the write
-// kernel's SLICE variant indexes its outputs from the slice's origin.
+// kernel's SLICE variant indexes its outputs from the slice's origin; the index kernel's
+// SLICE variant (gh_ectx_index_slice) emits the entries the slice owns.
 // Traffic: N (histogram, plan step) + 2N + C + gaps (encode) bytes.  A single pass
 // with a decoupled look-back (one 4 KiB chunk per workgroup) measured 2.85 ms on
 // cfg4, slower than these three kernels: its workgroups waited on their nearest
@@ -44,6 +47,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "gaphuff.h"
@@ -548,6 +552,17 @@ __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW
 // thread covers at most 256 bits and S >= 32768, so it owns at most one boundary; the
 // threads' ranges partition the stream's bits and every boundary lies below their total
 // (k * stride < G), so each entry has exactly one writer: no atomics, no zero-fill.
+// SLICE (gh_ectx_index_slice, after a slice encode): the block scan started at the slice's
+// base_bit, so every o0 is a stream bit position and the early-out, q0 / q1, k and B are
+// the stream's own already.  What differs is the store: entry k goes to offsets[k - k0],
+// its value is sym_base + ib + cnt (the stream offset of the slice's first byte added, in
+// 64 bits), and the bound is the slice's k0 + nk (p.nblocks holds it).  The one-writer
+// argument carries over by the ownership rule (gaphuff.h, "the index of a sliced stream"):
+// the threads' ranges partition the slice's bits [base_bit, base_bit + bits), the slice
+// owns exactly the boundaries inside them, k0 <= k < k0 + nk, so each of the nk entries
+// has exactly one writer and none is left unwritten: d_index holds 8 * nk bytes, never
+// zeroed.  SLICE = false keeps the parameter block and the code it had before the
+// template (the slice's two fields live in a derived block).
 struct EncIndexParams {
   const uint8_t* in;
   const uint32_t* lut;                 // 256 x {code << 8 | len}
@@ -558,8 +573,13 @@ struct EncIndexParams {
   uint64_t n, nblocks;
   uint32_t nchunks, log2_bits;         // S = 1 << log2_bits
 };
+struct EncIndexSliceParams : EncIndexParams {  // nblocks: the slice's k0 + nk
+  unsigned long long k0, sym_base;
+};
 
-__global__ __launch_bounds__(ETB) void gh_enc_index_kernel(const EncIndexParams p) {
+template <bool SLICE>
+__global__ __launch_bounds__(ETB) void gh_enc_index_kernel(
+    const std::conditional_t<SLICE, EncIndexSliceParams, EncIndexParams> p) {
   __shared__ uint32_t s_lenr[256 * EBREP];
   __shared__ uint32_t s_red[2][ETB / 64];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -604,9 +624,60 @@ __global__ __launch_bounds__(ETB) void gh_enc_index_kernel(const EncIndexParams 
         cnt += pos < rel ? 1u : 0u;
         pos += l[j];
       }
-      p.offsets[k] = ib + cnt;
+      if constexpr (SLICE) p.offsets[k - p.k0] = p.sym_base + ib + cnt;
+      else p.offsets[k] = ib + cnt;
     }
   }
+}
+
+// gh_ectx_merge_device: OR a slice's words into the stream's arrays.  One span is n source
+// words s[0 .. n) for destination words d[0 .. n) of a zeroed (or partly merged) array.
+// Only the span's first and last word can hold a neighbouring slice's bits (slices
+// partition the stream's bits; a word or gap word strictly inside a slice's extent lies
+// wholly inside its bits), so those two are ORed with device-scope atomics and the rest is
+// stored plainly: a span of at most two words is all-atomic.  Interior, when source and
+// destination agree modulo 16 bytes: a scalar head up to 16-byte alignment, a uint4
+// grid-stride body, a scalar tail; otherwise dwords.  The payload always agrees: the slice
+// buffer starts at stream bit org = base_bit & ~1023, so source word lead + i and
+// destination word word0 + i sit at the same offset from 128-byte-aligned bases (the
+// caller's arrays are 16-byte aligned at least).  The gap words agree when gapw0 is a
+// multiple of 4; they are 1 / 32 of the payload's bytes.  Bandwidth-bound: one read and
+// one write of the slice.
+__device__ __forceinline__ void enc_merge_span(const uint32_t* __restrict__ s, uint32_t* __restrict__ d, uint64_t n,
+                                               uint64_t tid, uint64_t nth) {
+  if (n == 0) return;
+  if (tid == 0) {
+    __hip_atomic_fetch_or(&d[0], s[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (n > 1) __hip_atomic_fetch_or(&d[n - 1], s[n - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (n <= 2) return;
+  const uint64_t lo = 1, hi = n - 1;  // the interior [lo, hi)
+  if ((((uintptr_t)s ^ (uintptr_t)d) & 15u) != 0) {
+    for (uint64_t i = lo + tid; i < hi; i += nth) d[i] = s[i];
+    return;
+  }
+  const uint64_t a = min(hi, lo + ((4u - (uint32_t)(((uintptr_t)(d + lo) >> 2) & 3u)) & 3u));  // head [lo, a)
+  const uint64_t b = a + ((hi - a) & ~3ull);                                                    // body [a, b)
+  if (lo + tid < a) d[lo + tid] = s[lo + tid];
+  const uint4* s4 = (const uint4*)(s + a);
+  uint4* d4 = (uint4*)(d + a);
+  for (uint64_t i = tid; i < (b - a) / 4; i += nth) d4[i] = s4[i];
+  if (b + tid < hi) d[b + tid] = s[b + tid];
+}
+
+struct EncMergeParams {
+  const uint32_t* sw;  // the slice's payload words: source word i is stream word word0 + i
+  uint32_t* dw;        // &d_payload[word0]
+  uint64_t nw;
+  const uint32_t* sg;  // the slice's gap words
+  uint32_t* dg;        // &d_gap_words[gapw0]
+  uint64_t ng;
+};
+constexpr int MERGE_TB = 256;
+__global__ __launch_bounds__(MERGE_TB) void gh_enc_merge_kernel(const EncMergeParams p) {
+  const uint64_t tid = (uint64_t)blockIdx.x * MERGE_TB + threadIdx.x, nth = (uint64_t)gridDim.x * MERGE_TB;
+  enc_merge_span(p.sw, p.dw, p.nw, tid, nth);
+  enc_merge_span(p.sg, p.dg, p.ng, tid, nth);
 }
 
 }  // namespace gh
@@ -634,6 +705,7 @@ struct gh_ectx {
   bool sliced = false;                         // the last encode was a slice encode: `slice`
   gh_slice slice{};
   EventPair ev;
+  Event ev_in;                                 // gh_ectx_load_device: the producer stream's position
   ~gh_ectx() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
@@ -677,6 +749,24 @@ extern "C" int gh_ectx_load(gh_ectx* e, const uint8_t* in, uint64_t n) {
   GH_HIP(hipStreamSynchronize(e->stream));
   e->n = n;
   e->planned = e->encoded = e->counted = e->sliced = false;
+  return GH_OK;
+}
+
+extern "C" int gh_ectx_load_device(gh_ectx* e, const void* d_in, uint64_t n, void* hip_stream) {
+  if (!e || (n && !d_in)) return fail(GH_E_ARG, "null argument");
+  GH_HIP(hipSetDevice(e->device));
+  e->planned = e->encoded = e->counted = e->sliced = false;  // (the input buffer changes from here on)
+  e->n = 0;
+  if (int rc = e->d_in.reserve(n + ECHUNK + 64)) return rc;
+  if (n) {
+    // after what the producer's stream holds now, then device to device on the context's stream
+    if (int rc = e->ev_in.create(hipEventDisableTiming)) return rc;
+    GH_HIP(hipEventRecord(e->ev_in, (hipStream_t)hip_stream));
+    GH_HIP(hipStreamWaitEvent(e->stream, e->ev_in, 0));
+    GH_HIP(hipMemcpyAsync(e->d_in.get(), d_in, n, hipMemcpyDefault, e->stream));
+  }
+  GH_HIP(hipStreamSynchronize(e->stream));
+  e->n = n;
   return GH_OK;
 }
 
@@ -884,14 +974,14 @@ extern "C" int gh_ectx_index(gh_ectx* e, uint32_t log2_stride, void* out, uint64
   GH_HIP(hipEventRecord(e->ev.a, e->stream));
   if (nblocks) {  // (then N > 0: the encode ran its kernels)
     int pc = 0;
-    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, (const void*)gh_enc_index_kernel, ETB, 0));
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, (const void*)gh_enc_index_kernel<false>, ETB, 0));
     uint32_t grid = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pc, 1) * e->num_cu);
     if (const char* eg = getenv("GH_ENC_INDEX_GRID"))  // tests: few workgroups, many chunks each
       grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
     const EncIndexParams p{e->d_in.get<uint8_t>(), e->d_lut.get<uint32_t>(), e->d_chunk_bits.get<uint32_t>(),
                            e->d_loc, e->d_blk, e->d_index.get<unsigned long long>(), e->n, nblocks,
                            (uint32_t)nchunks, 7u + log2_stride};
-    hipLaunchKernelGGL(gh_enc_index_kernel, dim3(grid), dim3(ETB), 0, e->stream, p);
+    hipLaunchKernelGGL(gh_enc_index_kernel<false>, dim3(grid), dim3(ETB), 0, e->stream, p);
     GH_HIP(hipGetLastError());
   }
   GH_HIP(hipEventRecord(e->ev.b, e->stream));
@@ -904,16 +994,96 @@ extern "C" int gh_ectx_index(gh_ectx* e, uint32_t log2_stride, void* out, uint64
   return GH_OK;
 }
 
+// The entries the last slice encode owns: the index kernel's SLICE variant over the same
+// leftovers (the chunk offsets are stream bit positions: the block scan started at
+// base_bit), then one copy of the nk entries.
+extern "C" int gh_ectx_index_slice(gh_ectx* e, uint64_t sym_base, uint32_t log2_stride, uint64_t* entries,
+                                   uint64_t cap, uint64_t* k0, uint64_t* nk, float* kernel_ms) {
+  if (!e || !k0 || !nk || (cap && !entries)) return fail(GH_E_ARG, "null argument");
+  if (!e->sliced) return fail(GH_E_STATE, "gh_ectx_index_slice: the last encode was not a slice encode");
+  if (int rc = gh_index_slice_extent(e->slice.base_bit, e->slice.bits, log2_stride, k0, nk)) return rc;
+  if (cap < *nk) return fail(GH_E_SMALL, "entry buffer too small");
+  GH_HIP(hipSetDevice(e->device));
+  const uint64_t nchunks = ceil_div(e->n, ECHUNK), n_own = *nk;
+  if (n_own)
+    if (int rc = e->d_index.reserve(8 * n_own)) return rc;
+  GH_HIP(hipEventRecord(e->ev.a, e->stream));
+  if (n_own) {  // (then the slice holds bits: the encode ran its kernels)
+    int pc = 0;
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, (const void*)gh_enc_index_kernel<true>, ETB, 0));
+    uint32_t grid = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pc, 1) * e->num_cu);
+    if (const char* eg = getenv("GH_ENC_INDEX_GRID"))  // tests: few workgroups, many chunks each
+      grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
+    EncIndexSliceParams p{};
+    static_cast<EncIndexParams&>(p) = EncIndexParams{e->d_in.get<uint8_t>(), e->d_lut.get<uint32_t>(),
+                                                     e->d_chunk_bits.get<uint32_t>(), e->d_loc, e->d_blk,
+                                                     e->d_index.get<unsigned long long>(), e->n, *k0 + n_own,
+                                                     (uint32_t)nchunks, 7u + log2_stride};
+    p.k0 = *k0;
+    p.sym_base = sym_base;
+    hipLaunchKernelGGL(gh_enc_index_kernel<true>, dim3(grid), dim3(ETB), 0, e->stream, p);
+    GH_HIP(hipGetLastError());
+  }
+  GH_HIP(hipEventRecord(e->ev.b, e->stream));
+  if (n_own) GH_HIP(hipMemcpyAsync(entries, e->d_index.get(), 8 * n_own, hipMemcpyDeviceToHost, e->stream));
+  GH_HIP(hipStreamSynchronize(e->stream));
+  if (kernel_ms)
+    if (int rc = e->ev.elapsed(kernel_ms)) return rc;
+  return GH_OK;
+}
+
+extern "C" int gh_ectx_merge_device(gh_ectx* e, uint32_t* d_payload, uint64_t payload_words, uint32_t* d_gap_words,
+                                    uint64_t gap_words, void* hip_stream) {
+  if (!e) return fail(GH_E_ARG, "null ctx");
+  if (!e->sliced && !e->encoded) return fail(GH_E_STATE, "gh_ectx_merge_device before an encode");
+  gh_slice sl = e->slice;
+  if (!e->sliced)  // a whole encode is the slice at bit 0
+    if (gh_slice_extent(0, e->plan.bits, &sl)) return GH_E_ARG;
+  if ((sl.nwords && !d_payload) || (sl.ngapw && !d_gap_words)) return fail(GH_E_ARG, "null argument");
+  if (sl.word0 > payload_words || sl.nwords > payload_words - sl.word0 || sl.gapw0 > gap_words ||
+      sl.ngapw > gap_words - sl.gapw0)
+    return fail(GH_E_ARG, "slice extents outside the destination arrays");
+  if (((uintptr_t)d_payload | (uintptr_t)d_gap_words) & 15u)
+    return fail(GH_E_ARG, "destination arrays must be 16-byte aligned");
+  GH_HIP(hipSetDevice(e->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)e->stream;
+  if (sl.nwords || sl.ngapw) {
+    // the device buffers start at the gap word holding base_bit: up to 31 words before word0
+    const uint64_t lead = sl.word0 - ((sl.base_bit & ~1023ull) >> 5);
+    const EncMergeParams p{e->d_words.get<uint32_t>() + lead, d_payload + sl.word0, sl.nwords,
+                           e->d_gaps.get<uint32_t>(), d_gap_words + sl.gapw0, sl.ngapw};
+    // a uint4 per thread, not a persistent grid: the copy yardstick's finding (gh_bw.hip: 6.1
+    // against 4.4-4.9 TB/s for grid-stride loops; this kernel at 8 workgroups per CU: 4.2)
+    const uint64_t want = ceil_div(std::max<uint64_t>(sl.nwords / 4 + 2, 1), MERGE_TB);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(want, 0x7fffffffull);
+    hipLaunchKernelGGL(gh_enc_merge_kernel, dim3(grid), dim3(MERGE_TB), 0, st, p);
+    GH_HIP(hipGetLastError());
+  }
+  GH_HIP(hipStreamSynchronize(st));
+  return GH_OK;
+}
+
 // One-shot sliced encode (gaphuff.h).  Slice i: bytes [n i / K, n (i + 1) / K) on device
 // devs[i % ng], in a gh_ectx of its own; a host thread per distinct device takes that
 // device's slices in turn.  Two passes with the stream-wide plan between them: the first
 // loads the slices and takes their histograms, the second encodes every slice at its
 // scanned bit offset and downloads it.  The merge runs on the calling thread, in slice
 // order (neighbouring slices share their edge words).
-extern "C" int gh_encode_sharded(const uint8_t* in, uint64_t n, const gh_opts* o, uint32_t nslices,
-                                 int force_version, void* out, uint64_t out_len, gh_encode_plan* plan_out,
-                                 float* kernel_ms) {
+// ix (gh_encode_sharded_index; NULL: no index): every slice's context also emits the index
+// entries the slice owns, right after its encode, and the calling thread stores them into
+// the image of gh_index_image_init.
+struct ShardedIndex {
+  uint32_t log2_stride;
+  void* out;
+  uint64_t len;
+  float* ms;
+};
+static int encode_sharded_run(const uint8_t* in, uint64_t n, const gh_opts* o, uint32_t nslices, int force_version,
+                              void* out, uint64_t out_len, gh_encode_plan* plan_out, float* kernel_ms,
+                              const ShardedIndex* ix) {
   if ((n && !in) || !out || nslices == 0) return fail(GH_E_ARG, "null argument or no slices");
+  if (ix && !ix->out) return fail(GH_E_ARG, "null argument");
+  if (ix && gh_index_bytes(0, ix->log2_stride) == 0) return fail(GH_E_ARG, "index stride outside 2^8 .. 2^20 segments");
   const int ng = (o && o->ngpus > 1) ? o->ngpus : 1;
   const uint32_t K = nslices;
   std::vector<int> dev(K);
@@ -970,10 +1140,14 @@ extern "C" int gh_encode_sharded(const uint8_t* in, uint64_t n, const gh_opts* o
   if (!rc) {
     if (plan_out) *plan_out = *plan;
     if (out_len < plan->file_bytes) rc = fail(GH_E_SMALL, "output buffer too small");
+    else if (ix && ix->len < gh_index_bytes(plan->g, ix->log2_stride)) rc = fail(GH_E_SMALL, "index buffer too small");
   }
   std::vector<gh_slice> sl(K);
   std::vector<std::vector<uint32_t>> words(K), gapw(K);
   std::vector<float> ms(K, 0.f);
+  std::vector<std::vector<uint64_t>> ent(K);  // slice i's entries [ek0[i], ek0[i] + ent[i].size())
+  std::vector<uint64_t> ek0(K, 0);
+  std::vector<float> ims(K, 0.f);
   if (!rc) {
     for (uint32_t i = 0; i < K; ++i) {  // the slices' bit totals, scanned
       uint64_t b = 0;
@@ -986,6 +1160,14 @@ extern "C" int gh_encode_sharded(const uint8_t* in, uint64_t n, const gh_opts* o
         words[i].resize(sl[i].nwords);
         gapw[i].resize(sl[i].ngapw);
         r = gh_ectx_download_slice(ctx[i], words[i].data(), words[i].size(), gapw[i].data(), gapw[i].size());
+      }
+      if (!r && ix) {
+        uint64_t nk = 0;
+        r = gh_index_slice_extent(sl[i].base_bit, sl[i].bits, ix->log2_stride, &ek0[i], &nk);
+        if (!r) {
+          ent[i].resize(nk);
+          r = gh_ectx_index_slice(ctx[i], cut(i), ix->log2_stride, ent[i].data(), nk, &ek0[i], &nk, &ims[i]);
+        }
       }
       gh_ectx_destroy(ctx[i]);  // (this device's memory goes back before its next slice)
       ctx[i] = nullptr;
@@ -1001,6 +1183,30 @@ extern "C" int gh_encode_sharded(const uint8_t* in, uint64_t n, const gh_opts* o
     *kernel_ms = 0.f;
     for (auto& d : per_dev) *kernel_ms = std::max(*kernel_ms, d.second);
   }
+  if (!rc && ix) {
+    rc = gh_index_image_init(plan, ix->log2_stride, ix->out, ix->len);
+    for (uint32_t i = 0; i < K && !rc; ++i) rc = gh_index_slice_merge(ix->out, ix->len, ek0[i], ent[i].size(), ent[i].data());
+    if (!rc && ix->ms) {
+      std::map<int, float> per_dev;
+      for (uint32_t i = 0; i < K; ++i) per_dev[dev[i]] += ims[i];
+      *ix->ms = 0.f;
+      for (auto& d : per_dev) *ix->ms = std::max(*ix->ms, d.second);
+    }
+  }
   delete plan;
   return rc;
+}
+
+extern "C" int gh_encode_sharded(const uint8_t* in, uint64_t n, const gh_opts* o, uint32_t nslices,
+                                 int force_version, void* out, uint64_t out_len, gh_encode_plan* plan_out,
+                                 float* kernel_ms) {
+  return encode_sharded_run(in, n, o, nslices, force_version, out, out_len, plan_out, kernel_ms, nullptr);
+}
+
+extern "C" int gh_encode_sharded_index(const uint8_t* in, uint64_t n, const gh_opts* o, uint32_t nslices,
+                                       int force_version, void* out, uint64_t out_len, gh_encode_plan* plan_out,
+                                       float* kernel_ms, uint32_t log2_stride, void* index_out, uint64_t index_len,
+                                       float* index_ms) {
+  const ShardedIndex ix{log2_stride, index_out, index_len, index_ms};
+  return encode_sharded_run(in, n, o, nslices, force_version, out, out_len, plan_out, kernel_ms, &ix);
 }

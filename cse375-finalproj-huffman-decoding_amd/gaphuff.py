@@ -59,6 +59,8 @@ EXPORTED = (
     "gh_ectx_download_slice", "gh_encode_sharded",
     "gh_ctx_set_index", "gh_gather_piece_bound", "gh_ctx_gather_device", "gh_ctx_gather_wait",
     "gh_ctx_gather_times", "gh_ctx_gather_pieces",
+    "gh_index_slice_extent", "gh_encode_index_slice", "gh_index_image_init", "gh_index_slice_merge",
+    "gh_ectx_index_slice", "gh_ectx_load_device", "gh_ectx_merge_device", "gh_encode_sharded_index",
 )
 
 
@@ -226,6 +228,18 @@ def lib() -> ctypes.CDLL:
             "gh_ectx_download_slice": ([P, P, U64, P, U64], I),
             "gh_encode_sharded": ([P, U64, ctypes.POINTER(gh_opts), U32, I, P, U64, ctypes.POINTER(gh_encode_plan),
                                    ctypes.POINTER(ctypes.c_float)], I),
+            "gh_index_slice_extent": ([U64, U64, U32, ctypes.POINTER(U64), ctypes.POINTER(U64)], I),
+            "gh_encode_index_slice": ([P, U64, ctypes.POINTER(gh_encode_plan), U64, U64, U32, I, P, U64,
+                                       ctypes.POINTER(U64), ctypes.POINTER(U64)], I),
+            "gh_index_image_init": ([ctypes.POINTER(gh_encode_plan), U32, P, U64], I),
+            "gh_index_slice_merge": ([P, U64, U64, U64, P], I),
+            "gh_ectx_index_slice": ([P, U64, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(U64),
+                                     ctypes.POINTER(ctypes.c_float)], I),
+            "gh_ectx_load_device": ([P, P, U64, P], I),
+            "gh_ectx_merge_device": ([P, P, U64, P, U64, P], I),
+            "gh_encode_sharded_index": ([P, U64, ctypes.POINTER(gh_opts), U32, I, P, U64,
+                                         ctypes.POINTER(gh_encode_plan), ctypes.POINTER(ctypes.c_float), U32, P, U64,
+                                         ctypes.POINTER(ctypes.c_float)], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -280,6 +294,20 @@ class Stream:
     @property
     def symbols(self) -> list:
         return [(self.c.syms[i].symbol, self.c.syms[i].length) for i in range(self.c.nsyms)]
+
+    @classmethod
+    def from_plan(cls, plan: "gh_encode_plan") -> "Stream":
+        """A header-only stream of the plan's sizes and code, for :meth:`Decoder.load_device`:
+        ``syms`` point into (a kept copy of) the plan, the word pointers are null."""
+        keep = gh_encode_plan.from_buffer_copy(plan)
+        s = gh_stream()
+        s.syms = ctypes.cast(ctypes.byref(keep, gh_encode_plan.syms.offset), ctypes.POINTER(gh_sym))
+        s.nsyms, s.version = keep.nsyms, keep.version
+        s.n, s.w, s.g = keep.n, keep.w, keep.g
+        s.gap_words = s.payload = None
+        st = cls(np.zeros(0, dtype=np.uint8), s)
+        st._plan = keep  # (syms point into it)
+        return st
 
 
 def parse(file_bytes) -> Stream:
@@ -367,6 +395,47 @@ def merge_slices(plan: gh_encode_plan, parts) -> np.ndarray:
     return img
 
 
+# ---- the index of a sliced stream (include/gaphuff.h) ----
+def index_slice_extent(base_bit: int, bits: int, log2_stride: int = 8):
+    """(k0, nk): the index entries the slice holding code bits [base_bit, base_bit + bits)
+    owns (gh_index_slice_extent)."""
+    k0, nk = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().gh_index_slice_extent(base_bit, bits, log2_stride, ctypes.byref(k0), ctypes.byref(nk)))
+    return int(k0.value), int(nk.value)
+
+
+def encode_index_slice(data, plan: gh_encode_plan, base_bit: int, sym_base: int, log2_stride: int = 8,
+                       threads: int = 0):
+    """Host: (entries as np.uint64, k0) of ``data`` as the slice at ``base_bit`` /
+    ``sym_base`` of the stream planned by ``plan`` (gh_encode_index_slice); the buffer
+    holds exactly the slice's nk entries."""
+    d = _u8(data)
+    k0, nk = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = lib().gh_encode_index_slice(_ptr(d), d.size, ctypes.byref(plan), base_bit, sym_base, log2_stride, threads,
+                                     None, 0, ctypes.byref(k0), ctypes.byref(nk))
+    if rc not in (GH_OK, -9):
+        _check(rc)
+    ent = np.zeros(int(nk.value), dtype=np.uint64)
+    _check(lib().gh_encode_index_slice(_ptr(d), d.size, ctypes.byref(plan), base_bit, sym_base, log2_stride, threads,
+                                       _ptr(ent), ent.size, ctypes.byref(k0), ctypes.byref(nk)))
+    return ent, int(k0.value)
+
+
+def merge_index_slices(plan: gh_encode_plan, log2_stride: int, parts) -> np.ndarray:
+    """The seek index image (np.uint8) of the (entries, k0) ``parts``, in any order
+    (gh_index_image_init + gh_index_slice_merge).  With a slice missing the image does not
+    parse."""
+    nbytes = int(lib().gh_index_bytes(plan.g, log2_stride))
+    if nbytes == 0:
+        raise GapHuffError(-1, "index stride outside 2^8 .. 2^20 segments")
+    img = np.empty(nbytes, dtype=np.uint8)
+    _check(lib().gh_index_image_init(ctypes.byref(plan), log2_stride, _ptr(img), img.size))
+    for part in parts:
+        ent = np.ascontiguousarray(part[0], dtype=np.uint64)
+        _check(lib().gh_index_slice_merge(_ptr(img), img.size, int(part[1]), ent.size, _ptr(ent)))
+    return img
+
+
 class Encoder:
     """One gh_ectx: the GPU encoder on one gfx950 device.
 
@@ -400,6 +469,11 @@ class Encoder:
     def load(self, data) -> None:
         d = _u8(data)
         _check(lib().gh_ectx_load(self._h, _ptr(d), d.size))
+
+    def load_device(self, ptr: int, n: int, hip_stream: int = 0) -> None:
+        """Load ``n`` input bytes from device memory at address ``ptr`` (gh_ectx_load_device):
+        copied on the device after what ``hip_stream`` (0: the default stream) holds now."""
+        _check(lib().gh_ectx_load_device(self._h, ctypes.c_void_p(ptr or None), n, ctypes.c_void_p(hip_stream or None)))
 
     def make_plan(self, force_version: int = 0) -> gh_encode_plan:
         p = gh_encode_plan()
@@ -444,6 +518,28 @@ class Encoder:
         _check(lib().gh_ectx_download_slice(self._h, _ptr(words), words.size, _ptr(gapw), gapw.size))
         return words, gapw
 
+    def index_slice(self, sym_base: int, log2_stride: int = 8):
+        """The index entries the last slice encode owns, built on the device
+        (gh_ectx_index_slice): (entries as np.uint64, k0, kernel ms).  ``sym_base``: the
+        stream offset of the slice's first byte."""
+        k0, nk, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_float()
+        rc = lib().gh_ectx_index_slice(self._h, sym_base, log2_stride, None, 0, ctypes.byref(k0), ctypes.byref(nk), None)
+        if rc not in (GH_OK, -9):
+            _check(rc)
+        ent = np.zeros(int(nk.value), dtype=np.uint64)
+        _check(lib().gh_ectx_index_slice(self._h, sym_base, log2_stride, _ptr(ent), ent.size, ctypes.byref(k0),
+                                         ctypes.byref(nk), ctypes.byref(ms)))
+        return ent, int(k0.value), float(ms.value)
+
+    def merge_device(self, payload_ptr: int, payload_words: int, gap_ptr: int, gap_words: int,
+                     hip_stream: int = 0) -> None:
+        """OR the last encode (a slice, or a whole encode) into the stream's zeroed device
+        arrays: ``payload_words`` u32 at ``payload_ptr``, ``gap_words`` u32 at ``gap_ptr``,
+        both 16-byte aligned (gh_ectx_merge_device)."""
+        _check(lib().gh_ectx_merge_device(self._h, ctypes.c_void_p(payload_ptr or None), payload_words,
+                                          ctypes.c_void_p(gap_ptr or None), gap_words,
+                                          ctypes.c_void_p(hip_stream or None)))
+
     def index(self, log2_stride: int = 8):
         """Seek index of the encoded stream, built on the device from what the encode left
         there (gh_ectx_index): (sidecar image as np.uint8, kernel ms)."""
@@ -467,11 +563,13 @@ def encode_gpu(data, device: int = 0, force_version: int = 0) -> np.ndarray:
 
 
 def encode_sharded(data, nslices: int, devices: Optional[Sequence[int]] = None, force_version: int = 0,
-                   return_ms: bool = False):
+                   return_ms: bool = False, index_log2_stride: Optional[int] = None):
     """Compress bytes on the GPU(s) slice by slice (gh_encode_sharded): ``nslices`` even
     cuts, slice i on ``devices[i % len(devices)]`` (default: device 0).  The image equals
     ``encode(data)``; with ``return_ms`` also the encode kernels' time (the slowest
-    device's sum)."""
+    device's sum).  With ``index_log2_stride`` (gh_encode_sharded_index) the stream's seek
+    index image, from the slices' own entries, is added to the tuple: (image, index) or
+    (image, ms, index)."""
     d = _u8(data)
     o = gh_opts()
     o.ngpus, o.reps = 1, 1
@@ -482,10 +580,18 @@ def encode_sharded(data, nslices: int, devices: Optional[Sequence[int]] = None, 
     out = np.empty(int(lib().gh_encode_bound(d.size)), dtype=np.uint8)
     plan = gh_encode_plan()
     ms = ctypes.c_float()
-    _check(lib().gh_encode_sharded(_ptr(d), d.size, ctypes.byref(o), nslices, force_version, _ptr(out), out.size,
-                                   ctypes.byref(plan), ctypes.byref(ms)))
-    img = out[: plan.file_bytes]
-    return (img, float(ms.value)) if return_ms else img
+    if index_log2_stride is None:
+        _check(lib().gh_encode_sharded(_ptr(d), d.size, ctypes.byref(o), nslices, force_version, _ptr(out), out.size,
+                                       ctypes.byref(plan), ctypes.byref(ms)))
+        img = out[: plan.file_bytes]
+        return (img, float(ms.value)) if return_ms else img
+    # (G <= ceil(n / 8); a bad stride: one byte, and the library's refusal)
+    idx = np.zeros(max(1, int(lib().gh_index_bytes((d.size + 7) // 8, index_log2_stride))), dtype=np.uint8)
+    _check(lib().gh_encode_sharded_index(_ptr(d), d.size, ctypes.byref(o), nslices, force_version, _ptr(out), out.size,
+                                         ctypes.byref(plan), ctypes.byref(ms), index_log2_stride, _ptr(idx), idx.size,
+                                         None))
+    img, idx = out[: plan.file_bytes], idx[: int(lib().gh_index_bytes(plan.g, index_log2_stride))]
+    return (img, float(ms.value), idx) if return_ms else (img, idx)
 
 
 def package_merge(sorted_counts: Sequence[int]) -> list:
@@ -551,6 +657,17 @@ class Decoder:
         seg_end = stream.g if seg_end is None else seg_end
         self._stream = stream
         _check(lib().gh_ctx_load(self._h, ctypes.byref(stream.c), seg_begin, seg_end, out_cap))
+
+    def load_device(self, stream: Stream, payload_ptr: int, payload_words: int, gap_ptr: int, seg_begin: int = 0,
+                    seg_end: Optional[int] = None, out_cap: int = 0) -> None:
+        """Load from device-resident words (gh_ctx_load_device): ``stream`` supplies the sizes
+        and the code (e.g. :meth:`Stream.from_plan`); ``payload_words`` u32 at ``payload_ptr``
+        and the whole gap array at ``gap_ptr`` stay owned by the caller."""
+        seg_end = stream.g if seg_end is None else seg_end
+        self._stream = stream
+        _check(lib().gh_ctx_load_device(self._h, ctypes.byref(stream.c), seg_begin, seg_end,
+                                        ctypes.c_void_p(payload_ptr or None), payload_words,
+                                        ctypes.c_void_p(gap_ptr or None), out_cap))
 
     def load_file(self, path: str, seg_begin: int = 0, seg_end: Optional[int] = None,
                   out_cap: int = 0) -> gh_file_info:

@@ -11,7 +11,8 @@
 // default 8) from the encoder itself: gh_encode_index on the host, gh_ectx_index with
 // --gpu; the same index with --raw (G is the same).  --gpu --slices K encodes the input
 // in K slices (gh_encode_sharded), slice i on the i-th of --devices (round robin; default:
-// the --gpu device); the same file, and the index then from gh_encode_index.
+// the --gpu device); the same file, and the index then from the slices' own entries
+// (gh_encode_sharded_index: gh_ectx_index_slice per slice, no host pass over the input).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -88,14 +89,19 @@ int main(int argc, char** argv) {
     float ms = 0.f;
     out.resize(gh_encode_bound(in.size()));
     t0 = now_ms();
-    rc = gh_encode_sharded(in.data(), in.size(), &opts, slices, force, out.data(), out.size(), plan, &ms);
-    t2 = now_ms();
+    if (index_path) {  // the index of a sliced stream: every slice's entries, from its GPU
+      // (G <= ceil(n / 8): 16-bit codes; a bad stride: size 0, and the library's refusal)
+      index.resize(std::max<uint64_t>(gh_index_bytes((in.size() + 7) / 8, index_k), 1));
+      rc = gh_encode_sharded_index(in.data(), in.size(), &opts, slices, force, out.data(), out.size(), plan, &ms,
+                                   index_k, index.data(), index.size(), nullptr);
+      t2 = now_ms();
+      if (!rc) index.resize(gh_index_bytes(plan->g, index_k));
+    } else {
+      rc = gh_encode_sharded(in.data(), in.size(), &opts, slices, force, out.data(), out.size(), plan, &ms);
+      t2 = now_ms();
+    }
     t1 = t2 - ms;
     if (!rc) out.resize(plan->file_bytes);
-    if (!rc && index_path) {  // the index of a sliced stream: from the host encoder
-      index.resize(std::max<uint64_t>(gh_index_bytes(plan->g, index_k), 1));
-      rc = gh_encode_index(in.data(), plan, index_k, threads, index.data(), index.size());
-    }
     if (rc) {
       std::fprintf(stderr, "encoder: %s\n", gh_last_error());
       return 1;

@@ -200,9 +200,34 @@ int gh_ectx_encode_slice(gh_ectx* ctx, const gh_encode_plan* stream_plan, uint64
  * out.  GH_E_STATE unless the context's last encode was a slice encode; GH_E_SMALL: a cap
  * (in u32) is too small.  After a slice encode gh_ectx_download and gh_ectx_index return
  * GH_E_STATE: the context holds no whole image, and the seek index of a sliced stream is
- * gh_encode_index's. */
+ * made of its slices' entries (gh_ectx_index_slice below) or is gh_encode_index's. */
 int gh_ectx_download_slice(gh_ectx* ctx, uint32_t* words, uint64_t words_cap, uint32_t* gapw,
                            uint64_t gaps_cap);
+/* Slices from and to device memory: with gh_ectx_index_slice, a stream is encoded slice by
+ * slice, merged, loaded into a gh_ctx (gh_ctx_load_device) and gathered from with no byte
+ * of input, payload or gap array crossing to the host.
+ * gh_ectx_load_device: gh_ectx_load with a device source (any address the context's device
+ * can read).  The n bytes are copied into the context's own padded input buffer (the
+ * kernels load unconditionally past n, so a borrowed pointer would need the caller to
+ * pad): device to device on the context's stream, after an event recorded on hip_stream
+ * (NULL: the default stream), so a producer kernel enqueued there has finished first.
+ * Synchronous; the same state reset as gh_ectx_load. */
+int gh_ectx_load_device(gh_ectx* ctx, const void* d_in, uint64_t n, void* hip_stream);
+/* OR the context's last encode (a slice, or a whole encode: the slice at bit 0) into
+ * caller-owned arrays on the context's device, laid out as gh_ctx_load_device takes them:
+ * payload word w of the stream at d_payload[w] (payload_words in all), gap word j at
+ * d_gap_words[j] (gap_words in all).  The caller zeroes both before the first merge.
+ * gh_enc_merge_kernel stores the slice's interior words plainly and ORs its first and last
+ * payload word and first and last gap word, the only words a neighbour can share, with
+ * device-scope atomics: merges of different contexts of ONE device into one destination
+ * may overlap on different streams, in any order.  Merges issued from DIFFERENT devices
+ * into one destination must be ordered by the caller (each finished before the next
+ * starts): atomicity across devices is not relied on and was not measured.  Waits for the
+ * context's encode, runs on hip_stream (NULL: the context's stream) and returns when done.
+ * GH_E_STATE before an encode; GH_E_ARG: a null array with a non-empty extent, the slice's
+ * extents past payload_words / gap_words, d_payload or d_gap_words not 16-byte aligned. */
+int gh_ectx_merge_device(gh_ectx* ctx, uint32_t* d_payload, uint64_t payload_words,
+                         uint32_t* d_gap_words, uint64_t gap_words, void* hip_stream);
 
 /* ---- GPU decoder -------------------------------------------------------------- */
 typedef struct gh_ctx gh_ctx;
@@ -366,6 +391,66 @@ int gh_encode_index(const uint8_t* in, const gh_encode_plan* plan, uint32_t log2
  * GH_E_STATE before gh_ectx_encode or after a later gh_ectx_load / gh_ectx_plan;
  * GH_E_ARG: null pointers, a stride outside the range; GH_E_SMALL: out_len too small. */
 int gh_ectx_index(gh_ectx* ctx, uint32_t log2_stride, void* out, uint64_t out_len, float* kernel_ms);
+
+/* ---- the index of a sliced stream: every slice emits the entries it owns --------------- */
+/* With S = 128 << log2_stride bits, entry k is the number of codewords that start before
+ * stream bit S * k.  A slice ("sliced encode" above) holds code bits [base_bit, base_bit +
+ * bits) and input bytes [sym_base, sym_base + n) of the stream, and it OWNS entry k when
+ *   base_bit <= S * k < base_bit + bits:
+ * entries [k0, k0 + nk) with k0 = ceil(base_bit / S), k1 = ceil((base_bit + bits) / S), nk =
+ * k1 - k0.  The value is sym_base + the number of the slice's bytes whose first bit is
+ * < S * k: every byte before the slice starts before the boundary, none after it does.  A
+ * boundary exactly on a seam belongs to the later slice, with count 0; a boundary inside a
+ * slice's last codeword gives sym_base + n; an empty slice owns nothing (k0 = k1).
+ * Coverage: the slices' bit ranges partition [0, plan->bits), so k0 of one slice is k1 of
+ * the one before (the k0 values chain from 0) and every boundary below plan->bits has
+ * exactly one owner.  S * k < bits implies k * stride < G = ceil(bits / 128), and k * stride
+ * < G implies S * k <= 128 * (G - 1) < bits, so the owned entries over all slices are
+ * exactly k < nblocks = ceil(G / stride): the nk values sum to nblocks, no owned k reaches
+ * nblocks, and the terminal entry N belongs to nobody (gh_index_image_init writes it).
+ * No reference counterpart. */
+/* [k0, k0 + nk) for bits [base_bit, base_bit + bits).  GH_E_ARG: nulls, a stride outside
+ * the range, a sum that overflows 64 bits.  No device. */
+int gh_index_slice_extent(uint64_t base_bit, uint64_t bits, uint32_t log2_stride,
+                          uint64_t* k0, uint64_t* nk);
+/* Host: entries [k0, k0 + nk) of the n bytes at `in` as the slice at base_bit / sym_base of
+ * the stream planned by stream_plan; entries[j] is entry *k0 + j.  gh_encode_index's
+ * two-pass walk with the bit origin and the symbol origin moved (gh_encode_index is the
+ * slice at bit 0 / symbol 0 into gh_index_image_init's image).  The entries do not depend
+ * on `threads`.  Errors as gh_encode_slice's: GH_E_TABLE: a byte of the slice has length 0
+ * in the plan; GH_E_ARG: null pointers, a stride outside the range, base_bit + bits >
+ * plan->bits; GH_E_SMALL: cap < nk -- *k0 and *nk are filled all the same, so a call with
+ * cap = 0 sizes the buffer (entries may then be NULL). */
+int gh_encode_index_slice(const uint8_t* in, uint64_t n, const gh_encode_plan* stream_plan,
+                          uint64_t base_bit, uint64_t sym_base, uint32_t log2_stride, int threads,
+                          uint64_t* entries, uint64_t cap, uint64_t* k0, uint64_t* nk);
+/* Header, zeroed entries and the terminal entry N (gh_index_bytes(plan->g, log2_stride)
+ * bytes): the image every slice's entries go into.  GH_E_ARG: nulls, a stride outside the
+ * range; GH_E_SMALL: image_len too small. */
+int gh_index_image_init(const gh_encode_plan* plan, uint32_t log2_stride, void* image, uint64_t image_len);
+/* Store a slice's entries [k0, k0 + nk) into the image (any alignment), checked against
+ * the image's own header: k0 + nk <= nentries - 1.  Slices own disjoint entries, so merges
+ * may come in any order (and, unlike gh_slice_merge, share nothing).  An image with a
+ * slice missing keeps that slice's zeros and fails gh_index_parse ("entries decrease": a
+ * zero after a non-zero entry; only entry 0 is 0 in a stream whose every block holds a
+ * codeword start): that is the intended tripwire, there is no separate completeness
+ * check.  It does not cover the slice that owns entry 0: zeros after entry 0 never
+ * decrease, and the parse then refuses only when the step up to the next slice's first
+ * entry exceeds 143 * stride.  GH_E_ARG: nulls, entries past nentries - 1; GH_E_FORMAT: not an index image's
+ * header; GH_E_SMALL: image_len shorter than the header says. */
+int gh_index_slice_merge(void* image, uint64_t image_len, uint64_t k0, uint64_t nk, const uint64_t* entries);
+/* GPU: the entries the context's last gh_ectx_encode_slice owns, from what that encode left
+ * on the device (gh_enc_index_kernel<SLICE = true>; the slice's chunk offsets are stream
+ * bit positions already), copied to entries[0 .. nk); sym_base: the stream offset of the
+ * slice's first byte.  *k0, *nk as gh_encode_index_slice's, filled before cap is checked
+ * (GH_E_SMALL).  nk = 0 launches nothing.  Repeatable with different strides; the slice's
+ * words (gh_ectx_download_slice, gh_ectx_merge_device) are untouched.  Synchronous, on the
+ * context's stream.  kernel_ms (may be NULL): HIP-event time of the index kernel alone.
+ * GH_E_STATE unless the context's last encode was a slice encode (and after a later
+ * load, counts, plan or encode); GH_E_ARG: nulls, a stride outside the range.
+ * gh_ectx_index keeps returning GH_E_STATE after a slice encode. */
+int gh_ectx_index_slice(gh_ectx* ctx, uint64_t sym_base, uint32_t log2_stride,
+                        uint64_t* entries, uint64_t cap, uint64_t* k0, uint64_t* nk, float* kernel_ms);
 /* Batched range gather: many byte ranges of a resident stream in one launch.  offsets[k]
  * is the output position of index block k's first symbol, so a block decodes on its own;
  * a batch is cut into pieces "decode index block k, keep the symbols at positions [a, b)
@@ -532,6 +617,19 @@ int gh_decode(const gh_stream* s, uint8_t* out, uint64_t out_len, const gh_opts*
 int gh_encode_sharded(const uint8_t* in, uint64_t n, const gh_opts* opts, uint32_t nslices,
                       int force_version, void* out, uint64_t out_len, gh_encode_plan* plan,
                       float* kernel_ms);
+/* gh_encode_sharded plus the stream's seek index (gh_index_bytes(plan->g, log2_stride)
+ * bytes into index_out; byte-identical to gh_encode_index's): the same two passes, each
+ * slice's context also running gh_ectx_index_slice (sym_base = the slice's first byte)
+ * right after its slice encode, and the calling thread gh_index_image_init and the
+ * gh_index_slice_merge calls.  No host pass over the input.  index_ms (may be NULL): the
+ * index kernels' time, by kernel_ms's convention (per device the sum over its slices, the
+ * maximum over devices).  GH_E_ARG also for a stride outside the range (before any device
+ * work); GH_E_SMALL also when index_len is too small (checked once the plan is known:
+ * gh_index_bytes(ceil(n / 8), log2_stride) always suffices). */
+int gh_encode_sharded_index(const uint8_t* in, uint64_t n, const gh_opts* opts, uint32_t nslices,
+                            int force_version, void* out, uint64_t out_len, gh_encode_plan* plan,
+                            float* kernel_ms, uint32_t log2_stride, void* index_out, uint64_t index_len,
+                            float* index_ms);
 
 /* Evenly split G segments into `nshards` contiguous ranges: bounds[0..nshards]. */
 int gh_plan_shards(uint64_t g, uint32_t nshards, uint64_t* bounds);
