@@ -704,14 +704,6 @@ extern "C" int gh_ctx_create(int device, gh_ctx** out) {
   return GH_OK;
 }
 
-// Copies s and its terminating NUL into buf[0..cap).
-static int copy_name(const std::string& s, char* buf, size_t cap) {
-  if (!buf) return fail(GH_E_ARG, "null argument");
-  if (s.size() + 1 > cap) return fail(GH_E_SMALL, "name buffer too small");
-  std::memcpy(buf, s.c_str(), s.size() + 1);
-  return GH_OK;
-}
-
 extern "C" int gh_ctx_kernel_shape(gh_ctx* c, char* buf, size_t cap) {
   if (!c) return fail(GH_E_ARG, "null ctx");
   if (!c->loaded) return fail(GH_E_STATE, "gh_ctx_kernel_shape before gh_ctx_load");

@@ -703,6 +703,7 @@ struct gh_ectx {
   uint64_t counts[256] = {};                   // histogram of the loaded input, when `counted`
   bool counted = false;
   bool sliced = false;                         // the last encode was a slice encode: `slice`
+  std::string shape;                           // the last encode's write kernel (gh_ectx_kernel_shape)
   gh_slice slice{};
   EventPair ev;
   Event ev_in;                                 // gh_ectx_load_device: the producer stream's position
@@ -770,12 +771,20 @@ extern "C" int gh_ectx_load_device(gh_ectx* e, const void* d_in, uint64_t n, voi
   return GH_OK;
 }
 
+// GH_ENC_GRID=k (tests): at most k workgroups for the encoder's persistent kernels
+// (histogram, bits, write), so a short input gives each workgroup many chunks.  It only
+// lowers a grid; read at each launch.
+static uint32_t enc_grid_cap(uint32_t grid) {
+  if (const char* eg = getenv("GH_ENC_GRID")) grid = (uint32_t)std::clamp<long>(atol(eg), 1, (long)grid);
+  return grid;
+}
+
 // Byte histogram of the loaded input into e->counts (synchronous).
 static int ectx_hist(gh_ectx* e) {
   GH_HIP(hipMemsetAsync(e->d_count.get(), 0, 256 * 8, e->stream));
   const uint64_t nchunks = ceil_div(e->n, ECHUNK);
   if (nchunks) {
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(nchunks, 4ull * e->num_cu);
+    const uint32_t grid = enc_grid_cap((uint32_t)std::min<uint64_t>(nchunks, 4ull * e->num_cu));
     hipLaunchKernelGGL(gh_enc_hist_kernel, dim3(grid), dim3(ETB), 0, e->stream, e->d_in.get<uint8_t>(), e->n,
                        e->d_count.get<unsigned long long>());
     GH_HIP(hipGetLastError());
@@ -813,15 +822,51 @@ extern "C" int gh_ectx_counts(gh_ectx* e, uint64_t counts[256]) {
   return GH_OK;
 }
 
+// A picked write kernel: its launch pointer and the name of its template instantiation
+// (gh_ectx_kernel_shape, gh_enc_kernel_shapes, gh_enc_kernel_shape_for), both from the one
+// template argument list, as the decoder's pickers (gh_decode.hip).
+struct EncKern {
+  const void* fn;
+  const char* name;
+};
+template <int NSW, bool SLICE>
+static EncKern enc_write_kern() {
+  static const std::string n = "enc_write<" + std::to_string(NSW) + ",slice=" + (SLICE ? "1" : "0") + ">";
+  return {(const void*)gh_enc_write_kernel<NSW, SLICE>, n.c_str()};
+}
 template <bool SLICE>
-static const void* enc_write_kernel(int need) {
-  return need <= 1   ? (const void*)gh_enc_write_kernel<1, SLICE>
-         : need <= 2 ? (const void*)gh_enc_write_kernel<2, SLICE>
-         : need <= 3 ? (const void*)gh_enc_write_kernel<3, SLICE>
-         : need <= 4 ? (const void*)gh_enc_write_kernel<4, SLICE>
-         : need <= 5 ? (const void*)gh_enc_write_kernel<5, SLICE>
-         : need <= 6 ? (const void*)gh_enc_write_kernel<6, SLICE>
-                     : (const void*)gh_enc_write_kernel<9, SLICE>;
+static EncKern enc_write_kernel(int need) {
+  return need <= 1   ? enc_write_kern<1, SLICE>()
+         : need <= 2 ? enc_write_kern<2, SLICE>()
+         : need <= 3 ? enc_write_kern<3, SLICE>()
+         : need <= 4 ? enc_write_kern<4, SLICE>()
+         : need <= 5 ? enc_write_kern<5, SLICE>()
+         : need <= 6 ? enc_write_kern<6, SLICE>()
+                     : enc_write_kern<9, SLICE>();
+}
+constexpr int ENC_NEED_MAX = 9;  // the largest NSW: 9 x ETB words hold a chunk at 16 bits per byte
+
+// The write kernel of an input of n bytes and `bits` code bits (a whole stream or a slice).
+// Payload words per chunk ~ ECHUNK * W / n: NSW = store instructions per thread.
+static EncKern enc_write_kernel_for(uint64_t n, uint64_t bits, bool slice) {
+  const double wpc = (double)ECHUNK * (double)ceil_div(bits, 32) / (double)std::max<uint64_t>(n, 1) + 2.0;
+  const int need = (int)std::ceil(wpc * 1.05 / ETB);
+  return slice ? enc_write_kernel<true>(need) : enc_write_kernel<false>(need);
+}
+
+// Every name enc_write_kernel_for can return, one per line: the picker enumerated over its
+// argument domain.  No device.
+static std::string all_enc_kernel_shapes() {
+  std::string s;
+  for (int slice = 0; slice <= 1; ++slice) {
+    const char* last = nullptr;
+    for (int need = 1; need <= ENC_NEED_MAX; ++need) {
+      const char* n = slice ? enc_write_kernel<true>(need).name : enc_write_kernel<false>(need).name;
+      if (n != last) s += std::string(n) + "\n";
+      last = n;
+    }
+  }
+  return s;
 }
 
 // The device encode of the loaded input under pl, as code bits [base_bit, base_bit + bits)
@@ -846,11 +891,11 @@ static int ectx_encode_run(gh_ectx* e, const gh_encode_plan& pl, bool slice, uin
   GH_HIP(hipMemcpyAsync(e->d_lut.get(), lut, sizeof(lut), hipMemcpyHostToDevice, e->stream));
   GH_HIP(hipEventRecord(e->ev.a, e->stream));
   GH_HIP(hipMemsetAsync(e->d_gaps.get(), 0, 4 * (GW + 4), e->stream));
+  e->shape.clear();  // (an empty input launches no kernel)
   if (nchunks) {
-    // payload words per chunk ~ 4096 * W / n: NSW = store instructions per thread
-    const double wpc = (double)ECHUNK * (double)ceil_div(bits, 32) / (double)std::max<uint64_t>(e->n, 1) + 2.0;
-    const int need = (int)std::ceil(wpc * 1.05 / ETB);
-    const void* wk = slice ? enc_write_kernel<true>(need) : enc_write_kernel<false>(need);
+    const EncKern kern = enc_write_kernel_for(e->n, bits, slice);
+    const void* wk = kern.fn;
+    e->shape = kern.name;
     // the LDS image holds a chunk at the code's longest codeword
     uint32_t maxlen = 1;
     for (int v = 0; v < 256; ++v) maxlen = std::max<uint32_t>(maxlen, pl.len[v]);
@@ -860,7 +905,7 @@ static int ectx_encode_run(gh_ectx* e, const gh_encode_plan& pl, bool slice, uin
     int pb = 0, pw = 0;  // persistent grids: what is resident at once
     GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)gh_enc_bits_kernel, ETB, 0));
     GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pw, wk, ETB, dyn));
-    const uint32_t gb = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pb, 1) * e->num_cu);
+    const uint32_t gb = enc_grid_cap((uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pb, 1) * e->num_cu));
     const uint8_t* d_in = e->d_in.get<uint8_t>();
     const uint32_t* d_lut = e->d_lut.get<uint32_t>();
     uint32_t* d_chunk_bits = e->d_chunk_bits.get<uint32_t>();
@@ -874,7 +919,7 @@ static int ectx_encode_run(gh_ectx* e, const gh_encode_plan& pl, bool slice, uin
                        (uint32_t)nchunks, loc, blk);
     hipLaunchKernelGGL(gh_enc_blkscan_kernel, dim3(1), dim3(SCAN_TB), 0, e->stream, blk, nblk,
                        (unsigned long long)base_bit);
-    const uint32_t gw = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pw, 1) * e->num_cu);
+    const uint32_t gw = enc_grid_cap((uint32_t)std::min<uint64_t>(nchunks, (uint64_t)std::max(pw, 1) * e->num_cu));
     if (int rc = e->d_junk.reserve(4ull * gw * ETB)) return rc;
     e->d_loc = loc;
     e->d_blk = blk;
@@ -924,6 +969,21 @@ extern "C" int gh_ectx_encode_slice(gh_ectx* e, const gh_encode_plan* sp, uint64
   e->sliced = true;
   if (out) *out = sl;
   return GH_OK;
+}
+
+extern "C" int gh_ectx_kernel_shape(gh_ectx* e, char* buf, size_t cap) {
+  if (!e) return fail(GH_E_ARG, "null ctx");
+  if (!e->encoded && !e->sliced) return fail(GH_E_STATE, "gh_ectx_kernel_shape before an encode");
+  return copy_name(e->shape, buf, cap);
+}
+
+extern "C" int gh_enc_kernel_shapes(char* buf, size_t cap) { return copy_name(all_enc_kernel_shapes(), buf, cap); }
+
+extern "C" int gh_enc_kernel_shape_for(uint64_t n, uint64_t bits, int slice, char* buf, size_t cap) {
+  if (slice != 0 && slice != 1) return fail(GH_E_ARG, "slice is 0 or 1");
+  if (bits / GH_MAX_CODE_LEN > n || (bits / GH_MAX_CODE_LEN == n && bits % GH_MAX_CODE_LEN))
+    return fail(GH_E_ARG, "more than 16 code bits per input byte");
+  return copy_name(n ? enc_write_kernel_for(n, bits, slice != 0).name : "", buf, cap);
 }
 
 extern "C" int gh_ectx_download_slice(gh_ectx* e, uint32_t* words, uint64_t words_cap, uint32_t* gapw,

@@ -3,6 +3,7 @@
 // device memory, streams and events) are in gh_hip.hpp.  Not part of the C ABI.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 #include "gaphuff.h"
@@ -48,6 +49,15 @@ inline uint32_t canon_decode16(const Canon& c, uint32_t w16, uint32_t* index) {
 }
 
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+
+// Copies s and its terminating NUL into buf[0..cap): the kernel-name queries of the
+// decoder and the encoder.
+inline int copy_name(const std::string& s, char* buf, size_t cap) {
+  if (!buf) return fail(GH_E_ARG, "null argument");
+  if (s.size() + 1 > cap) return fail(GH_E_SMALL, "name buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return GH_OK;
+}
 
 // Encoder plan from plan->n and plan->count[] (symbol order, package-merge lengths,
 // canonical codes, sizes, header version); shared by the host and GPU encoders.

@@ -591,6 +591,8 @@ int grid_for(const void* k, uint64_t items) {
 
 using namespace gh;
 
+extern "C" int gh_sync_lut_bits(void) { return SK; }
+
 extern "C" int gh_sync_gaps(int device, const gh_sym* syms, uint32_t nsyms, const uint32_t* d_words,
                             uint64_t w, uint32_t* d_gap_words, void* hip_stream, gh_sync_report* rep) {
   if (rep) std::memset(rep, 0, sizeof(*rep));

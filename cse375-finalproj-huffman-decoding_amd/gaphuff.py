@@ -61,6 +61,7 @@ EXPORTED = (
     "gh_ctx_gather_times", "gh_ctx_gather_pieces",
     "gh_index_slice_extent", "gh_encode_index_slice", "gh_index_image_init", "gh_index_slice_merge",
     "gh_ectx_index_slice", "gh_ectx_load_device", "gh_ectx_merge_device", "gh_encode_sharded_index",
+    "gh_ectx_kernel_shape", "gh_enc_kernel_shapes", "gh_enc_kernel_shape_for", "gh_sync_lut_bits",
 )
 
 
@@ -240,6 +241,10 @@ def lib() -> ctypes.CDLL:
             "gh_encode_sharded_index": ([P, U64, ctypes.POINTER(gh_opts), U32, I, P, U64,
                                          ctypes.POINTER(gh_encode_plan), ctypes.POINTER(ctypes.c_float), U32, P, U64,
                                          ctypes.POINTER(ctypes.c_float)], I),
+            "gh_ectx_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_enc_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_enc_kernel_shape_for": ([U64, U64, I, ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_sync_lut_bits": ([], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -494,6 +499,13 @@ class Encoder:
         _check(lib().gh_ectx_download(self._h, _ptr(out), out.size))
         return out
 
+    def kernel_shape(self) -> str:
+        """Name of the write kernel instantiation the last encode or slice encode picked
+        (gh_ectx_kernel_shape)."""
+        buf = ctypes.create_string_buffer(64)
+        _check(lib().gh_ectx_kernel_shape(self._h, buf, len(buf)))
+        return buf.value.decode()
+
     def counts(self) -> np.ndarray:
         """GPU histogram of the loaded input (256 x np.uint64); makes no plan."""
         c = np.zeros(256, dtype=np.uint64)
@@ -618,6 +630,26 @@ def kernel_shapes() -> list:
     buf = ctypes.create_string_buffer(1 << 14)
     _check(lib().gh_kernel_shapes(buf, len(buf)))
     return buf.value.decode().split()
+
+
+def enc_kernel_shapes() -> list:
+    """Every write kernel name an encode can pick (gh_enc_kernel_shapes); needs no device."""
+    buf = ctypes.create_string_buffer(1 << 10)
+    _check(lib().gh_enc_kernel_shapes(buf, len(buf)))
+    return buf.value.decode().split()
+
+
+def enc_kernel_shape_for(n: int, bits: int, slice: bool = False) -> str:
+    """The write kernel an encode picks for ``n`` input bytes of ``bits`` code bits
+    (gh_enc_kernel_shape_for); needs no device."""
+    buf = ctypes.create_string_buffer(64)
+    _check(lib().gh_enc_kernel_shape_for(n, bits, int(slice), buf, len(buf)))
+    return buf.value.decode()
+
+
+def sync_lut_bits() -> int:
+    """Prefix bits of the self-synchronising decode's length table (gh_sync_lut_bits)."""
+    return int(lib().gh_sync_lut_bits())
 
 
 def device_count() -> int:

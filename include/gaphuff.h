@@ -228,6 +228,19 @@ int gh_ectx_load_device(gh_ectx* ctx, const void* d_in, uint64_t n, void* hip_st
  * extents past payload_words / gap_words, d_payload or d_gap_words not 16-byte aligned. */
 int gh_ectx_merge_device(gh_ectx* ctx, uint32_t* d_payload, uint64_t payload_words,
                          uint32_t* d_gap_words, uint64_t gap_words, void* hip_stream);
+/* The encode's write kernel is one of 14 template instantiations, named
+ * "enc_write<NSW,slice=0|1>": NSW in {1, 2, 3, 4, 5, 6, 9} payload stores per thread and
+ * chunk, picked from the input's code bits per byte; slice=1 for gh_ectx_encode_slice.
+ * gh_ectx_kernel_shape: the name the context's last gh_ectx_encode / gh_ectx_encode_slice
+ * picked, NUL-terminated into buf[0..cap); empty for an empty input.  GH_E_SMALL when cap
+ * is too small, GH_E_STATE before an encode (or after a later load or plan). */
+int gh_ectx_kernel_shape(gh_ectx* ctx, char* buf, size_t cap);
+/* Every name an encode can pick, one per line.  Needs no device. */
+int gh_enc_kernel_shapes(char* buf, size_t cap);
+/* The name the picker returns for an input of n bytes and `bits` code bits, a whole stream
+ * (slice = 0) or a slice (slice = 1); empty for n = 0.  Host arithmetic only, no device.
+ * GH_E_ARG: slice not 0 or 1, bits > 16 n; GH_E_SMALL when cap is too small. */
+int gh_enc_kernel_shape_for(uint64_t n, uint64_t bits, int slice, char* buf, size_t cap);
 
 /* ---- GPU decoder -------------------------------------------------------------- */
 typedef struct gh_ctx gh_ctx;
@@ -570,6 +583,9 @@ typedef struct gh_sync_report {
  * counter back).  rep may be NULL. */
 int gh_sync_gaps(int device, const gh_sym* syms, uint32_t nsyms, const uint32_t* d_words,
                  uint64_t w, uint32_t* d_gap_words, void* hip_stream, gh_sync_report* rep);
+/* Prefix bits of gh_sync_gaps's length table: a code whose longest codeword has more bits
+ * runs the kernels' long-codeword path.  Needs no device. */
+int gh_sync_lut_bits(void);
 /* Raw-stream file container (this repo's; gpuhd keeps its streams in memory,
  * demo.cc:100-160): u64 GH_RAW_MAGIC ("GHRAW1\0\0"), u64 nsyms, nsyms x {u8 symbol,
  * u8 length} in code order, u64 N, u64 W, W x u32 units (codewords MSB-first). */

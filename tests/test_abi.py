@@ -25,6 +25,17 @@ def test_library_exports_all(gh):
         assert hasattr(lib, name), name
 
 
+def test_shape_and_sync_queries_declared_and_exported(gh):
+    """The encoder's kernel-shape queries and the sync LUT width: in the header, in
+    gh.EXPORTED, in the library and in the ctypes table (no device needed)."""
+    lib = ctypes.CDLL(gh.LIB_PATH)
+    for name in ("gh_ectx_kernel_shape", "gh_enc_kernel_shapes", "gh_enc_kernel_shape_for", "gh_sync_lut_bits"):
+        assert name in declared() and name in gh.EXPORTED and hasattr(lib, name), name
+        assert getattr(gh.lib(), name).argtypes is not None, name
+    assert len(gh.enc_kernel_shapes()) == 14
+    assert 1 <= gh.sync_lut_bits() <= 16
+
+
 def test_version_and_error_strings(gh):
     assert b"gfx950" in gh.lib().gh_version()
     assert isinstance(gh.lib().gh_last_error(), bytes)

@@ -123,7 +123,7 @@ WS_ROWS = {
 
 ENV_KNOBS = ("GH_MODE", "GH_TILE_GRID", "GH_TILE_SCAP", "GH_TILE_SCAPF", "GH_WS_K", "GH_WS_KC", "GH_WS_NS",
              "GH_WS_GRID", "GH_WS_STAGE", "GH_WS_LGC", "GH_MT_KC", "GH_MT_CLGR", "GH_LUT_BITS", "GH_LGR",
-             "GH_TILE_IDLE")
+             "GH_TILE_IDLE", "GH_ENC_GRID", "GH_ENC_INDEX_GRID")
 
 
 # ---- streams ------------------------------------------------------------------------

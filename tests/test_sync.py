@@ -105,8 +105,17 @@ def test_desync_table_oracle(orc):
 
 def test_sync_abi_exports(gh):
     L = gh.lib()
-    for name in ("gh_sync_gaps", "gh_ctx_load_raw", "gh_ctx_device"):
+    for name in ("gh_sync_gaps", "gh_ctx_load_raw", "gh_ctx_device", "gh_sync_lut_bits"):
         assert hasattr(L, name)
+
+
+def test_sync_lut_bits_is_the_librarys(gh):
+    """SK as the library reports it (gh_sync_lut_bits: host code, no device) is the value
+    the boundary tests below were collected with, and their codes stay within the format's
+    16-bit codewords."""
+    assert gh.sync_lut_bits() == SYNC_LUT_BITS
+    assert LUT_BOUNDARY_MAXLENS == sorted({13, SYNC_LUT_BITS - 1, SYNC_LUT_BITS, SYNC_LUT_BITS + 1})
+    assert 13 in LUT_BOUNDARY_MAXLENS and max(LUT_BOUNDARY_MAXLENS) <= 16
 
 
 # ------------------------------------------------------------------------- GPU
@@ -154,26 +163,40 @@ def test_gpu_sync_block_and_wave_edges(gpu, orc, n):
 
 @pytest.mark.gpu
 def test_gpu_sync_long_codes(gpu, orc):
-    """Codes longer than the 13-bit sync LUT (SK = 13, gh_sync.hip: the LONG kernels'
+    """Codes longer than the sync LUT (SK bits, gh_sync.hip: the LONG kernels'
     canonical-threshold path), up to 16 bits, from the geometric fixture."""
     d = _bin("geometric_long_codes")
     syms = orc.symbols_of(d)
-    assert max(l for _, l in syms) > SYNC_LUT_BITS
+    assert max(l for _, l in syms) > gpu.sync_lut_bits() == SYNC_LUT_BITS
+    assert max(l for _, l in syms) == 16
     units = orc.raw_encode(d, syms)
     gaps, _ = _sync_on_gpu(gpu, units, syms)
     assert np.array_equal(gaps, orc.raw_gaps(d, syms))
     assert np.array_equal(gpu.decode_raw(units, syms, d.size), d)
 
 
-SYNC_LUT_BITS = 13  # SK in csrc/gh_sync.hip
+def _sync_lut_bits():
+    """SK of csrc/gh_sync.hip for the parametrisation below, read from the source: loading
+    the library while tests are collected would put its HIP runtime ahead of torch's
+    (conftest.py).  Every test that uses it first asserts gh_sync_lut_bits() returns it."""
+    import re
+    src = os.path.join(os.path.dirname(GOLD), os.pardir, "cse375-finalproj-huffman-decoding_amd", "csrc", "gh_sync.hip")
+    return int(re.search(r"^#define GH_SYNC_SK (\d+)", open(src).read(), re.M).group(1))
+
+
+SYNC_LUT_BITS = _sync_lut_bits()
+# SK - 1 and SK fit the LUT (plain kernel), SK + 1 is the first LONG length; 13 was the
+# boundary's lower side until SK became 14 and stays
+LUT_BOUNDARY_MAXLENS = sorted({13, SYNC_LUT_BITS - 1, SYNC_LUT_BITS, SYNC_LUT_BITS + 1})
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("maxlen", [SYNC_LUT_BITS, SYNC_LUT_BITS + 1])
+@pytest.mark.parametrize("maxlen", LUT_BOUNDARY_MAXLENS)
 def test_gpu_sync_lut_boundary_codes(gpu, orc, maxlen):
-    """Complete codes whose longest codeword is exactly SK bits (fits the LUT: plain
-    kernel) and exactly SK + 1 bits (the LONG kernel): lengths 1, 2, ..., maxlen-1,
+    """Complete codes whose longest codeword is SK - 1 and exactly SK bits (fit the LUT:
+    plain kernel) and exactly SK + 1 bits (the LONG kernel): lengths 1, 2, ..., maxlen-1,
     maxlen, maxlen (Kraft sum 1), symbols drawn with probability 2^-length."""
+    assert gpu.sync_lut_bits() == SYNC_LUT_BITS
     lens = list(range(1, maxlen)) + [maxlen, maxlen]
     syms = [(40 + i, l) for i, l in enumerate(lens)]
     p = np.array([2.0 ** -l for l in lens])
