@@ -32,9 +32,13 @@
 // Issue priority by arrival rank: the waves that arrived last at their previous tile gate
 // the next aggregate, so they take priority 3, the first arrivals 0.
 //
-// Every alternative of the round-3/4 build knobs (copy-out interleaving, batched reads,
-// early loads, ticket schedules, priority rotations, ...) measured slower and was removed
-// (tile-kernel section).  Diagnostic builds only: GH_TILE_STAMPS, GH_TILE_ABLATE.
+// The alternatives of the round-3/4 build knobs (copy-out interleaving, batched reads,
+// early loads, priority rotations, ...) measured slower and were removed.  The round-5/6
+// alternatives are still compiled in behind the knobs below, all at their measured-best
+// defaults (DYN, HOLD, PF2, W2, LATEP, CLDS, POLLDIV, LMAJ, ALRD: DESIGN.md, tile-kernel
+// section, records each measurement); the C-coded borrow count (CSUB) and the per-codeword
+// placement barrier (EPERM) are gone.
+// Diagnostic builds only: GH_TILE_STAMPS, GH_TILE_ABLATE.
 
 #ifndef GH_TILE_TB
 #define GH_TILE_TB 1024
@@ -62,9 +66,6 @@ constexpr int TILE_SLOTS = 16;  // per-tile wave totals / offsets / arrival coun
 #else
 #define TSTAMP(i) ((void)0)
 #endif
-#ifndef GH_TILE_CSUB
-#define GH_TILE_CSUB 0  // the decode step's borrow count in C (the compiler's own hazard padding)
-#endif
 #ifndef GH_TILE_CLDS
 #define GH_TILE_CLDS 0  // the decode's LUT reads as plain LDS loads (the compiler's own lgkmcnt waits)
 #endif
@@ -80,9 +81,6 @@ constexpr int TILE_SLOTS = 16;  // per-tile wave totals / offsets / arrival coun
 constexpr int TILE_TAHEAD = 5;  // (GH_TILE_DYN) a tile index is posted this many iterations ahead
 #ifndef GH_TILE_LATEP
 #define GH_TILE_LATEP 0  // a third prefix load right before the prefetch (see the loop)
-#endif
-#ifndef GH_TILE_EPERM
-#define GH_TILE_EPERM 0  // symbols placed into the output words as they are decoded (register peak)
 #endif
 #ifndef GH_TILE_HOLD
 #define GH_TILE_HOLD 0  // a decoded tile is held in registers one iteration and staged the next:
@@ -142,10 +140,12 @@ inline size_t tile_lds_bytes(size_t lut_bytes, size_t stage_bytes) {
          TILE_SLOTS * 12 + 4 * (TILE_TB / 64) + 4 * TILE_SLOTS + 32;
 }
 
-// v_perm selector placing byte 1 of S0 (the symbol) at byte j, keeping S1's others.
-__device__ __forceinline__ constexpr uint32_t perm_sel(int j) {
-  return j == 0 ? 0x03020105u : j == 1 ? 0x03020500u : j == 2 ? 0x03050100u : 0x05020100u;
-}
+// v_perm selectors of the symbol placement (a LUT entry carries its symbol in byte 1;
+// v_perm_b32 D, S0, S1, sel: selector bytes 0-3 take S1's bytes, 4-7 S0's).  Four
+// consecutive symbols make one output dword in three ops: two pairs, then the dword.
+constexpr uint32_t PERM_PAIR = 0x07060501u;   // (S0 = later entry, S1 = earlier): bytes 0, 1 = their symbols
+constexpr uint32_t PERM_QUAD = 0x05040100u;   // (S0 = pair 2-3, S1 = pair 0-1): the dword
+constexpr uint32_t PERM_THIRD = 0x07050100u;  // (S0 = entry 2, S1 = pair 0-1): a dword cut short after three symbols
 
 // e-window of a segment starting at bit `start` (0..15): e-stream bit 0 is segment
 // bit start - S (bits before the segment read as 0); requires 16 <= S <= 31.  The
@@ -191,9 +191,9 @@ __device__ __forceinline__ void lds_wait_n(uint32_t& v) {
 
 // Decode of U segments per lane on e-windows.  Each group decodes G codewords per chain
 // from e0:e1 and then shifts the windows (G * maxlen <= 32, so the group's consumed bits
-// fit Q's low byte).  Codeword j of a segment goes to byte j of ow (v_perm, static
-// index); dead codewords go there too and are never staged.  `mid()` runs once, after
-// group TILE_MIDG (NG > TILE_MIDG).  Returns the groups run (wave-uniform: the loop stops
+// fit Q's low byte).  Codeword j of a segment goes to byte j of ow (v_perm with static
+// selectors, two symbols at a time: PERM_PAIR above); dead codewords go there too and are
+// never staged.  `mid()` runs once, after group TILE_MIDG (NG > TILE_MIDG).  Returns the groups run (wave-uniform: the loop stops
 // once no chain of the wave is live).  The chains' lookups roll: each chain waits only
 // for its own read (a counted lgkmcnt: LDS reads of a wave complete in order) and issues
 // its next one at once, so U reads stay in flight and a chain's step costs one LDS round
@@ -206,16 +206,34 @@ __device__ __forceinline__ void lds_wait_n(uint32_t& v) {
 // K bits: nothing at e-position >= 157 - lgr - start is read for a kept codeword, so a
 // word lying wholly at or above 157 is no longer shifted (its stale bits reach only such
 // positions; dead codewords decode garbage, never counted).
+// Never-borrow prefix: a segment starts at bit <= 15 (a gap nibble; first_start is the
+// nibble before the shard's first segment, 0 at a stream's start) and the host picks
+// G = min(4, 32 / maxlen) (tile_kernel_for's second argument), so a code decoded with
+// G = 4, 3, 2 has no codeword longer than LMAX = 8, 10, 12 bits (tile codes stop at 12).  The first NB = 112 / LMAX
+// codewords of a segment then end at or before bit 15 + 112 = 127: none of them reaches
+// the segment end, so none borrows, whatever the payload bits are (the lengths come from
+// the LUT, not from the stream).  For them Q takes a plain subtract and cnt is left alone.
+// For the same reason every active segment is still live after NB codewords: the
+// liveness minimum and the exit test start at the first group that holds codeword NB
+// (0-based).  A wave without a tile (the drain iterations: every chain inactive) leaves
+// after group TILE_MIDG as before, on the wave-uniform `have_tile`.
 template <int G, int U, int OW, int MINL, class Mid>
 __device__ __forceinline__ int decode_tile_rolling(uint32_t (&e)[U][5], const int (&start)[U], const bool (&act)[U],
                                                    uint32_t (&ow)[U][OW], uint32_t (&cnt)[U], uint32_t amask,
-                                                   uint32_t laneoff, Mid&& mid) {
+                                                   uint32_t laneoff, bool have_tile, Mid&& mid) {
   constexpr int S = 4 * OW;
   constexpr int NG = (S + G - 1) / G;
+  static_assert(G >= 2 && G <= 4, "G = min(4, 32 / maxlen) with maxlen <= 12");
+  constexpr int LMAX = G >= 4 ? 8 : G == 3 ? 10 : 12;  // the longest codeword of a code decoded with this G
+  static_assert(G * LMAX <= 32 && (G == 4 || (G + 1) * LMAX > 32), "LMAX is the longest maxlen with 32 / maxlen == G");
+  constexpr int NB = 112 / LMAX;  // 15 (the gap nibble's range) + NB * LMAX <= 127: codewords 0 .. NB - 1 never borrow
+  static_assert(15 + NB * LMAX <= 127 && NB < S, "the never-borrow prefix");
+  constexpr int GLIVE = NB / G;   // the first group whose last codeword is >= NB
+  static_assert(GLIVE >= TILE_MIDG && GLIVE < NG, "mid() runs before any exit");
   // (four codewords per window shift: the deferred symbol placement kept too many entries
   // live and spilled; placed per group instead)
-  constexpr int PLACE = GH_TILE_EPERM ? GH_TILE_EPERM : (G >= 4 ? 2 : 0);
-  uint32_t q[U], ent[U];
+  constexpr bool PLACE = G >= 4;
+  uint32_t q[U], ent[U], hold[U], pair[U];
 #if GH_TILE_CLDS
   const __attribute__((address_space(3))) uint8_t* const lds0 = (const __attribute__((address_space(3))) uint8_t*)nullptr;
   auto lut_rd = [&](uint32_t a) -> uint32_t { return *(const __attribute__((address_space(3))) uint32_t*)(lds0 + a); };
@@ -259,22 +277,21 @@ __device__ __forceinline__ int decode_tile_rolling(uint32_t (&e)[U][5], const in
           } else {
             lds_wait_n<U - 1>(ent[u]);
           }
-#if GH_TILE_CSUB
-          {
-            uint32_t nq;
-            const bool br = __builtin_sub_overflow(q[u], ent[u], &nq);
-            q[u] = nq;
-            cnt[u] = br ? (uint32_t)(pos + 1) : cnt[u];
+          if (pos < NB) {
+            q[u] -= ent[u];  // cannot borrow (above)
+          } else {
+            asm("v_sub_co_u32 %0, vcc, %0, %2\n\t"
+                "v_cndmask_b32_e64 %1, %1, %3, vcc"
+                : "+v"(q[u]), "+v"(cnt[u]) : "v"(ent[u]), "i"(pos + 1) : "vcc");
           }
-#else
-          asm("v_sub_co_u32 %0, vcc, %0, %2\n\t"
-              "v_cndmask_b32_e64 %1, %1, %3, vcc"
-              : "+v"(q[u]), "+v"(cnt[u]) : "v"(ent[u]), "i"(pos + 1) : "vcc");
-#endif
-          ow[u][pos >> 2] = __builtin_amdgcn_perm(ent[u], ow[u][pos >> 2], perm_sel(pos & 3));
-          // (GH_TILE_EPERM) place the symbol now: the compiler otherwise keeps every entry
-          // live until the staging, ~60 VGPRs at the decode's peak
-          if (PLACE == 1) asm volatile("" : "+v"(ow[u][pos >> 2]));
+          // symbol placement: entries 0 and 2 of a dword wait for their neighbour
+          if ((pos & 1) == 0) {
+            hold[u] = ent[u];
+          } else if ((pos & 3) == 1) {
+            pair[u] = __builtin_amdgcn_perm(ent[u], hold[u], PERM_PAIR);
+          } else {
+            ow[u][pos >> 2] = __builtin_amdgcn_perm(__builtin_amdgcn_perm(ent[u], hold[u], PERM_PAIR), pair[u], PERM_QUAD);
+          }
           if (!gend) {
             const uint32_t x = __builtin_amdgcn_alignbit(e[u][0], e[u][1], q[u]);
             ent[u] = lut_rd((x & amask) | laneoff);
@@ -286,13 +303,13 @@ __device__ __forceinline__ int decode_tile_rolling(uint32_t (&e)[U][5], const in
             if (CMIN + 96 < 157) e[u][3] = __builtin_amdgcn_alignbit(e[u][3], e[u][4], q[u]);
             if (CMIN + 128 < 157) e[u][4] = __builtin_amdgcn_alignbit(e[u][4], 0u, q[u]);
             q[u] = (q[u] & 0xFFFFFF00u) | 32u;
-            qmin = min(qmin, q[u]);
+            if (gi >= GLIVE) qmin = min(qmin, q[u]);
             if (!last) ent[u] = lut_rd((e[u][0] & amask) | laneoff);
           }
         }
       }
     }
-    if (PLACE == 2) {  // this group's symbols placed by its end
+    if (PLACE) {  // this group's symbols placed by its end
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int w0 = (gi * G) >> 2, w1 = min(OW - 1, (gi * G + G - 1) >> 2);
@@ -301,10 +318,19 @@ __device__ __forceinline__ int decode_tile_rolling(uint32_t (&e)[U][5], const in
       }
     }
     if (gi == TILE_MIDG) mid();
-    if (gi >= TILE_MIDG && gi + 1 < NG && !__any(qmin < Q_LIVE)) {
+    // no segment can end before group GLIVE; a wave without a tile leaves after mid()
+    if (gi + 1 < NG && (gi >= GLIVE ? !__any(qmin < Q_LIVE) : (gi == TILE_MIDG && !have_tile))) {
       // the next group's reads are in flight: drain them
 #pragma unroll
       for (int u = 0; u < U; ++u) lds_wait_n<0>(ent[u]);
+      // the dword this group ends in, if it is not whole: from the symbols it has
+      const int pe = gi * G + G - 1;  // the last codeword decoded
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if ((pe & 3) == 0) ow[u][pe >> 2] = hold[u] >> 8;
+        else if ((pe & 3) == 1) ow[u][pe >> 2] = pair[u];
+        else if ((pe & 3) == 2) ow[u][pe >> 2] = __builtin_amdgcn_perm(hold[u], pair[u], PERM_THIRD);
+      }
       gdone = gi + 1;
       break;
     }
@@ -994,9 +1020,9 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     };
     // ---- decode this tile (its words were loaded during the previous iteration) --------
     // Decoded unconditionally: in the last iterations (no tile) every chain is inactive
-    // and the loop stops after one group (the loads were issued, clamped to the last
-    // tile).  A branch around the decode made the compiler zero the output words before
-    // it every iteration and wait vmcnt(0) after it.
+    // and the loop stops after group TILE_MIDG, on have_cur (the loads were issued,
+    // clamped to the last tile).  A branch around the decode made the compiler zero the
+    // output words before it every iteration and wait vmcnt(0) after it.
     const uint32_t seg0 = cur * (uint32_t)(U * TB) + lseg;
     uint32_t ow[U][OW], cnt[U];
     int gdone;
@@ -1022,7 +1048,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         mid();
         gdone = (16 + GRP - 1) / GRP;
       } else {
-        gdone = decode_tile_rolling<GRP, U, OW, MINL>(e, start, act, ow, cnt, amask, laneoff, mid);
+        gdone = decode_tile_rolling<GRP, U, OW, MINL>(e, start, act, ow, cnt, amask, laneoff, have_cur, mid);
       }
     }
     // The next tile's words, right after the decode (its windows are dead, so the
