@@ -384,6 +384,60 @@ extern "C" uint64_t gh_gather_piece_bound(uint32_t nranges, uint64_t dst_len, ui
 }
 
 // ---------------------------------------------------------------------------
+// Batched decode: the host plan (gaphuff.h, "batched decode").  No device.
+// ---------------------------------------------------------------------------
+// a + b into *r; false when the sum overflows 64 bits
+static bool add_u64(uint64_t a, uint64_t b, uint64_t* r) { return !__builtin_add_overflow(a, b, r); }
+
+extern "C" int gh_batch_layout(const uint64_t* n, uint32_t nstreams, uint64_t* out_off) {
+  if (!out_off || (nstreams && !n)) return fail(GH_E_ARG, "null argument");
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    out_off[i] = at;
+    uint64_t padded;
+    if (!add_u64(n[i], 15, &padded) || !add_u64(at, padded & ~15ull, &at))
+      return fail(GH_E_ARG, "batch output arena overflows 64 bits at stream " + std::to_string(i));
+  }
+  out_off[nstreams] = at;
+  return GH_OK;
+}
+
+int gh::batch_plan(const uint64_t* n, const uint64_t* w, const uint64_t* g, uint32_t nstreams, BatchPlan& out) {
+  out = BatchPlan();
+  if (nstreams && (!n || !w || !g)) return fail(GH_E_ARG, "null argument");
+  if (nstreams > BATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  out.ext.resize(nstreams);
+  uint64_t pay = 0, gap = 0, units = 0, bytes = 0;
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    const std::string who = "stream " + std::to_string(i) + ": ";
+    if (g[i] >= BATCH_MAX_G) return fail(GH_E_ARG, who + "2^32 - 256 or more segments");
+    if (g[i] == 0 ? w[i] != 0 : (w[i] > 4 * g[i] || w[i] + 3 < 4 * g[i]))
+      return fail(GH_E_ARG, who + "W inconsistent with G (need 4G-3 <= W <= 4G)");
+    BatchExtent& e = out.ext[i];
+    e.pay_off = pay;
+    // words [4 (G - 1), 4 G) of the last segment and the look-ahead word 4 G are loaded
+    // unconditionally: 4 G + 1 words, rounded up to 16 bytes
+    e.pay_words = g[i] ? 4 * g[i] + 4 : 0;
+    e.gap_off = gap;
+    e.gap_words = ceil_div(g[i], GH_GAPS_PER_WORD);
+    e.unit0 = units;
+    e.out_off = bytes;
+    pay += e.pay_words;  // (< 2^24 * 2^34)
+    gap += e.gap_words;
+    units += ceil_div(g[i], BATCH_UNIT_SEGS);
+    if (units >= BATCH_MAX_UNITS) return fail(GH_E_ARG, who + "the batch reaches 2^31 work units");
+    uint64_t padded;
+    if (!add_u64(n[i], 15, &padded) || !add_u64(bytes, padded & ~15ull, &bytes))
+      return fail(GH_E_ARG, who + "the output arena overflows 64 bits");
+  }
+  out.pay_words = pay;
+  out.gap_words = gap;
+  out.nunits = units;
+  out.out_bytes = bytes;
+  return GH_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Encoder
 // ---------------------------------------------------------------------------
 extern "C" int gh_encode_plan_make(const uint8_t* in, uint64_t n, int threads,

@@ -47,6 +47,7 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 #include "gh_index.hip"
 #include "gh_gather.hip"
 #include "gh_gather_plan.hip"
+#include "gh_batch.hip"
 #include "gh_mtile.hip"
 
 }  // namespace gh
@@ -1544,6 +1545,336 @@ extern "C" int gh_ctx_gather_pieces(gh_ctx* c, gh_gather_piece* pieces, uint64_t
   if (np > cap) return fail(GH_E_SMALL, "piece buffer smaller than the plan");
   if (np) GH_HIP(hipMemcpy(pieces, c->dgather.pieces.get(), np * sizeof(gh_gather_piece), hipMemcpyDeviceToHost));
   return GH_OK;
+}
+
+// ---- batched decode (gaphuff.h; kernels: gh_batch.hip; host plan: gh::batch_plan) ------
+// The count and write kernels of a batch share one template argument list, as the *_kern
+// functions above: FB, whether a lookup can miss.
+struct BatchKernels {
+  const void* count;
+  const void* write;
+  const char* name;
+};
+template <bool FB>
+static BatchKernels batch_kernels() {
+  static const std::string n = kern_name("batch<fb=%d>", (int)FB);
+  return {(const void*)gh_batch_count_kernel<FB>, (const void*)gh_batch_write_kernel<FB>, n.c_str()};
+}
+static BatchKernels batch_kernels_for(bool fb) { return fb ? batch_kernels<true>() : batch_kernels<false>(); }
+constexpr uint32_t BATCH_LAUNCHES = 3;  // count, scan, write
+
+struct gh_batch {
+  int device = 0, num_cu = 0;
+  Stream stream;
+  Event done;   // end of the last decode, on whatever stream it ran
+  Event ev_in;  // gh_batch_load_device: the producer stream's position
+  EventPair ev;
+  DevBuf payload, gaps, tables, desc, unit0, syms, items;  // the loaded batch
+  DevBuf seg_cnt, unit_tot, unit_off, symbols;             // decode scratch
+  DevBuf flags;                                            // 4 summary words, then a status word per stream
+  DevBuf out;                                              // the batch's own output arena (on demand)
+  BatchPlan plan;
+  std::vector<uint64_t> n;
+  uint32_t nstreams = 0;
+  bool loaded = false, enqueued = false, timed = false, fb = false, own_out = false;
+  ~gh_batch() {
+    (void)hipSetDevice(device);
+    if (enqueued) (void)hipEventSynchronize(done);  // (it may run on a caller's stream)
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
+
+extern "C" int gh_batch_create(int device, gh_batch** out) {
+  if (!out) return fail(GH_E_ARG, "null batch pointer");
+  *out = nullptr;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+    return fail(GH_E_NODEV, "no HIP device visible (the decoder has no CPU fallback)");
+  if (device < 0 || device >= n) return fail(GH_E_ARG, "device ordinal out of range");
+  hipDeviceProp_t prop;
+  GH_HIP(hipGetDeviceProperties(&prop, device));
+  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
+    return fail(GH_E_NODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
+  std::unique_ptr<gh_batch> b(new gh_batch());
+  b->device = device;
+  b->num_cu = prop.multiProcessorCount;
+  GH_HIP(hipSetDevice(device));
+  if (int rc = b->stream.create()) return rc;
+  if (int rc = b->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = b->ev_in.create(hipEventDisableTiming)) return rc;
+  if (int rc = b->ev.create()) return rc;
+  *out = b.release();
+  return GH_OK;
+}
+
+extern "C" int gh_batch_destroy(gh_batch* b) {
+  delete b;
+  return GH_OK;
+}
+
+// At least `bytes` (and never an empty allocation), then a copy of host memory.
+static int batch_upload(DevBuf& d, const void* src, uint64_t bytes) {
+  if (int rc = d.reserve(std::max<uint64_t>(bytes, 16))) return rc;
+  if (bytes) GH_HIP(hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
+  return GH_OK;
+}
+
+// ss[i]: stream i's header; its word pointers are host memory (any alignment), or device
+// memory when `device`.
+static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device, void* hip_stream) {
+  const uint32_t ns = (uint32_t)ss.size();
+  GH_HIP(hipSetDevice(b->device));
+  if (b->enqueued) GH_HIP(hipEventSynchronize(b->done));  // the previous batch's decode reads what is replaced
+  GH_HIP(hipStreamSynchronize(b->stream));
+  b->loaded = b->enqueued = b->own_out = false;
+  std::vector<uint64_t> n(ns), w(ns), g(ns);
+  std::vector<BatchDesc> desc(ns);
+  std::vector<gh_sym> syms;
+  uint64_t tab_words = 0;
+  bool fb = false;
+  for (uint32_t i = 0; i < ns; ++i) {
+    const gh_stream& s = ss[i];
+    const std::string who = "stream " + std::to_string(i) + ": ";
+    if (int rc = gh_stream_validate(&s)) return fail(rc, who + gh_last_error());
+    Canon cn;
+    if (int rc = build_canon(s.syms, s.nsyms, cn)) return fail(rc, who + gh_last_error());
+    if (s.g > 0 && cn.nsyms == 0) return fail(GH_E_TABLE, who + "segments but an empty code");
+    if ((s.w && !s.payload) || (s.g && !s.gap_words)) return fail(GH_E_ARG, who + "null word pointer");
+    if (device && ((((uintptr_t)s.payload) | ((uintptr_t)s.gap_words)) & 3u))
+      return fail(GH_E_ARG, who + "device words not 4-byte aligned");
+    n[i] = s.n;
+    w[i] = s.w;
+    g[i] = s.g;
+    BatchDesc& d = desc[i];
+    d = BatchDesc{};
+    d.n = s.n;
+    d.minlen = std::max<uint32_t>(cn.minlen, 1);
+    d.maxlen = std::max<uint32_t>(cn.maxlen, d.minlen);
+    d.sym_off = (uint32_t)syms.size();
+    d.nsyms = s.nsyms;
+    d.tab_off = tab_words;
+    if (s.g) {
+      d.kbits = std::min<uint32_t>(cn.maxlen, BA_KMAX);
+      tab_words += BA_FBW + std::max<uint32_t>(1u << d.kbits, 4u);
+      fb |= cn.maxlen > BA_KMAX || kraft16(cn) != 65536;
+      syms.insert(syms.end(), s.syms, s.syms + s.nsyms);
+    }
+  }
+  BatchPlan plan;
+  if (int rc = batch_plan(n.data(), w.data(), g.data(), ns, plan)) return rc;
+  std::vector<uint32_t> unit0(ns + 1);
+  for (uint32_t i = 0; i < ns; ++i) {
+    const BatchExtent& e = plan.ext[i];
+    desc[i].pay_off = e.pay_off;
+    desc[i].gap_off = e.gap_off;
+    desc[i].out_off = e.out_off;
+    desc[i].nseg = (uint32_t)g[i];
+    unit0[i] = (uint32_t)e.unit0;
+  }
+  unit0[ns] = (uint32_t)plan.nunits;
+  if (int rc = batch_upload(b->desc, desc.data(), sizeof(BatchDesc) * (uint64_t)ns)) return rc;
+  if (int rc = batch_upload(b->unit0, unit0.data(), 4ull * (ns + 1))) return rc;
+  if (int rc = batch_upload(b->syms, syms.data(), sizeof(gh_sym) * (uint64_t)syms.size())) return rc;
+  if (int rc = b->tables.reserve(std::max<uint64_t>(4 * tab_words, 16))) return rc;
+  if (int rc = b->payload.reserve(std::max<uint64_t>(4 * plan.pay_words, 16))) return rc;
+  if (int rc = b->gaps.reserve(std::max<uint64_t>(4 * plan.gap_words, 16))) return rc;
+  if (int rc = b->seg_cnt.reserve(std::max<uint64_t>(plan.nunits * BATCH_UNIT_SEGS, 16))) return rc;
+  if (int rc = b->unit_tot.reserve(std::max<uint64_t>(4 * plan.nunits, 16))) return rc;
+  if (int rc = b->unit_off.reserve(8 * (plan.nunits + 1))) return rc;
+  if (int rc = b->symbols.reserve(std::max<uint64_t>(8ull * ns, 16))) return rc;
+  if (int rc = b->flags.reserve(16 + 4ull * ns)) return rc;
+  if (!device) {
+    // the arenas are assembled in host memory, padding included, and go up in two copies
+    std::vector<uint32_t> pay(plan.pay_words, 0u), gap(plan.gap_words, 0u);
+    for (uint32_t i = 0; i < ns; ++i) {
+      if (w[i]) std::memcpy(pay.data() + plan.ext[i].pay_off, ss[i].payload, 4 * w[i]);
+      if (g[i]) std::memcpy(gap.data() + plan.ext[i].gap_off, ss[i].gap_words, 4 * plan.ext[i].gap_words);
+    }
+    if (!pay.empty()) {
+      if (use_staged(4 * pay.size())) {
+        if (int rc = h2d_staged(b->device, pay.data(), 4 * pay.size(), b->payload.get())) return rc;
+      } else {
+        GH_HIP(hipMemcpy(b->payload.get(), pay.data(), 4 * pay.size(), hipMemcpyHostToDevice));
+      }
+    }
+    if (!gap.empty()) GH_HIP(hipMemcpy(b->gaps.get(), gap.data(), 4 * gap.size(), hipMemcpyHostToDevice));
+  } else {
+    std::vector<BatchCopyItem> items(ns);
+    for (uint32_t i = 0; i < ns; ++i) {
+      const BatchExtent& e = plan.ext[i];
+      items[i] = BatchCopyItem{ss[i].payload, ss[i].gap_words, w[i], e.pay_off, e.pay_words, e.gap_off, e.gap_words};
+    }
+    if (int rc = batch_upload(b->items, items.data(), sizeof(BatchCopyItem) * (uint64_t)ns)) return rc;
+    // after what the producer's stream holds now, then one copy kernel on the batch's stream
+    GH_HIP(hipEventRecord(b->ev_in, (hipStream_t)hip_stream));
+    GH_HIP(hipStreamWaitEvent(b->stream, b->ev_in, 0));
+    if (plan.pay_words) {
+      hipLaunchKernelGGL(gh_batch_copy_kernel, dim3(std::min<uint32_t>(ns, 4096u), BA_COPY_Y), dim3(256), 0, b->stream,
+                         b->items.get<BatchCopyItem>(), ns, b->payload.get<uint32_t>(), b->gaps.get<uint32_t>());
+      GH_HIP(hipGetLastError());
+    }
+  }
+  if (tab_words) {  // every stream's tables: one launch
+    hipLaunchKernelGGL(gh_batch_table_kernel, dim3(std::min<uint32_t>(ns, 16u * (uint32_t)b->num_cu)), dim3(256), 0,
+                       b->stream, b->desc.get<BatchDesc>(), b->syms.get<gh_sym>(), b->tables.get<uint32_t>(), ns);
+    GH_HIP(hipGetLastError());
+  }
+  GH_HIP(hipStreamSynchronize(b->stream));
+  b->plan = std::move(plan);
+  b->n = std::move(n);
+  b->nstreams = ns;
+  b->fb = fb;
+  b->loaded = true;
+  return GH_OK;
+}
+
+extern "C" int gh_batch_load(gh_batch* b, const gh_stream* streams, uint32_t nstreams) {
+  if (!b || (nstreams && !streams)) return fail(GH_E_ARG, "null argument");
+  if (nstreams > BATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  return batch_load(b, std::vector<gh_stream>(streams, streams + nstreams), false, nullptr);
+}
+
+extern "C" int gh_batch_load_device(gh_batch* b, const gh_batch_item* items, uint32_t nstreams, void* hip_stream) {
+  if (!b || (nstreams && !items)) return fail(GH_E_ARG, "null argument");
+  if (nstreams > BATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  std::vector<gh_stream> ss(nstreams);
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    const gh_batch_item& it = items[i];
+    ss[i] = gh_stream{it.syms, it.nsyms, 2u, it.n, it.w, it.g, it.d_gap_words, it.d_payload};
+  }
+  return batch_load(b, ss, true, hip_stream);
+}
+
+// GH_BATCH_GRID=k (tests): k workgroups for the count and write kernels, so that one wave
+// walks many units and streams.  Read at each decode.
+static uint32_t batch_grid(const gh_batch* b) {
+  if (const char* eg = getenv("GH_BATCH_GRID")) return (uint32_t)std::clamp<long>(atol(eg), 1, 1l << 20);
+  const uint64_t want = ceil_div(b->plan.nunits, BA_TB / 64);
+  return (uint32_t)std::clamp<uint64_t>(want, 1, 8ull * (uint64_t)b->num_cu);
+}
+
+extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void* hip_stream, int timed) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_batch_decode before a load");
+  GH_HIP(hipSetDevice(b->device));
+  const bool own = d_dst == nullptr;
+  if (own) {
+    if (int rc = b->out.reserve(std::max<uint64_t>(b->plan.out_bytes, 16))) return rc;
+    d_dst = b->out.get();
+  } else {
+    if ((uintptr_t)d_dst & 15u) return fail(GH_E_ARG, "destination not 16-byte aligned");
+    if (dst_len < b->plan.out_bytes) return fail(GH_E_SMALL, "destination smaller than the batch's arena");
+  }
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)b->stream;
+  // decodes of one batch share its scratch: they run in the order they were made
+  if (b->enqueued) GH_HIP(hipStreamWaitEvent(st, b->done, 0));
+  BatchParams bp{};
+  bp.desc = b->desc.get<BatchDesc>();
+  bp.unit0 = b->unit0.get<uint32_t>();
+  bp.payload = b->payload.get<uint32_t>();
+  bp.gaps = b->gaps.get<uint32_t>();
+  bp.tables = b->tables.get<uint32_t>();
+  bp.seg_cnt = b->seg_cnt.get<uint8_t>();
+  bp.unit_tot = b->unit_tot.get<uint32_t>();
+  bp.unit_off = b->unit_off.get<unsigned long long>();
+  bp.summary = b->flags.get<unsigned int>();
+  bp.status = bp.summary + 4;
+  bp.symbols = b->symbols.get<unsigned long long>();
+  bp.out = (uint8_t*)d_dst;
+  bp.nstreams = b->nstreams;
+  bp.nunits = (uint32_t)b->plan.nunits;
+  if (timed) GH_HIP(hipEventRecord(b->ev.a, st));
+  GH_HIP(hipMemsetAsync(b->flags.get(), 0, 16 + 4ull * b->nstreams, st));
+  if (b->nstreams) {
+    const BatchKernels k = batch_kernels_for(b->fb);
+    const uint32_t grid = batch_grid(b);
+    void* args[] = {&bp};
+    if (bp.nunits) GH_HIP(hipLaunchKernel(k.count, dim3(grid), dim3(BA_TB), args, 0, st));
+    GH_HIP(hipLaunchKernel((const void*)gh_batch_scan_kernel, dim3(1), dim3(BA_SCAN_TB), args, 0, st));
+    if (bp.nunits) GH_HIP(hipLaunchKernel(k.write, dim3(grid), dim3(BA_TB), args, 0, st));
+  }
+  if (timed) GH_HIP(hipEventRecord(b->ev.b, st));
+  GH_HIP(hipEventRecord(b->done, st));
+  b->enqueued = true;
+  b->timed = timed != 0;
+  b->own_out = own;
+  return GH_OK;
+}
+
+extern "C" int gh_batch_wait(gh_batch* b, gh_batch_report* rep) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (rep) *rep = gh_batch_report{};
+  if (!b->loaded || !b->enqueued) return fail(GH_E_STATE, "gh_batch_wait without a decode since the load");
+  GH_HIP(hipSetDevice(b->device));
+  GH_HIP(hipEventSynchronize(b->done));
+  unsigned int sum[2] = {0, 0};
+  GH_HIP(hipMemcpy(sum, b->flags.get(), sizeof(sum), hipMemcpyDeviceToHost));
+  float ms = 0;
+  if (b->timed)
+    if (int rc = b->ev.elapsed(&ms)) return rc;
+  if (rep) {
+    for (uint64_t v : b->n) rep->out_bytes += v;
+    rep->nstreams = b->nstreams;
+    rep->bad_streams = sum[0];
+    rep->status = sum[1];
+    rep->kernel_ms = ms;
+    rep->launches = BATCH_LAUNCHES;
+  }
+  if (sum[0])
+    return fail(GH_E_CORRUPT, std::to_string(sum[0]) + " stream(s) of the batch decoded to fewer than N symbols or met "
+                                                        "a pattern outside their code (gh_batch_status names them)");
+  return GH_OK;
+}
+
+extern "C" int gh_batch_status(gh_batch* b, uint32_t* status, uint64_t* symbols, uint32_t cap) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded || !b->enqueued) return fail(GH_E_STATE, "gh_batch_status without a decode since the load");
+  if (cap < b->nstreams) return fail(GH_E_SMALL, "status arrays smaller than the batch");
+  GH_HIP(hipSetDevice(b->device));
+  GH_HIP(hipEventSynchronize(b->done));
+  if (status && b->nstreams)
+    GH_HIP(hipMemcpy(status, b->flags.get<unsigned int>() + 4, 4ull * b->nstreams, hipMemcpyDeviceToHost));
+  if (symbols && b->nstreams) GH_HIP(hipMemcpy(symbols, b->symbols.get(), 8ull * b->nstreams, hipMemcpyDeviceToHost));
+  return GH_OK;
+}
+
+extern "C" int gh_batch_output(gh_batch* b, void** d_out, uint64_t* cap) {
+  if (!b || !d_out) return fail(GH_E_ARG, "null argument");
+  *d_out = b->out.get();
+  if (cap) *cap = b->out.capacity();
+  return GH_OK;
+}
+
+extern "C" int gh_batch_offsets(gh_batch* b, uint64_t* out_off, uint32_t cap) {
+  if (!b || !out_off) return fail(GH_E_ARG, "null argument");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_batch_offsets before a load");
+  if ((uint64_t)cap < (uint64_t)b->nstreams + 1) return fail(GH_E_SMALL, "offset array smaller than nstreams + 1");
+  for (uint32_t i = 0; i < b->nstreams; ++i) out_off[i] = b->plan.ext[i].out_off;
+  out_off[b->nstreams] = b->plan.out_bytes;
+  return GH_OK;
+}
+
+extern "C" int gh_batch_download(gh_batch* b, uint32_t stream, uint8_t* dst, uint64_t nbytes) {
+  if (!b || (nbytes && !dst)) return fail(GH_E_ARG, "null argument");
+  if (!b->loaded || !b->enqueued || !b->own_out)
+    return fail(GH_E_STATE, "gh_batch_download without a decode into the batch's own arena");
+  if (stream >= b->nstreams) return fail(GH_E_ARG, "no such stream in the batch");
+  if (nbytes > b->n[stream]) return fail(GH_E_ARG, "more bytes than the stream holds");
+  GH_HIP(hipSetDevice(b->device));
+  GH_HIP(hipEventSynchronize(b->done));
+  if (nbytes)
+    GH_HIP(hipMemcpy(dst, b->out.get<uint8_t>() + b->plan.ext[stream].out_off, nbytes, hipMemcpyDeviceToHost));
+  return GH_OK;
+}
+
+extern "C" int gh_batch_kernel_shape(gh_batch* b, char* buf, size_t cap) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_batch_kernel_shape before a load");
+  return copy_name(b->plan.nunits ? batch_kernels_for(b->fb).name : "", buf, cap);
+}
+
+extern "C" int gh_batch_kernel_shapes(char* buf, size_t cap) {
+  return copy_name(std::string(batch_kernels_for(false).name) + "\n" + batch_kernels_for(true).name + "\n", buf, cap);
 }
 
 // Decode time of a set of shards: decodes on one device run in turn (DevChain), so a

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "gaphuff.h"
 
@@ -58,6 +59,29 @@ inline int copy_name(const std::string& s, char* buf, size_t cap) {
   std::memcpy(buf, s.c_str(), s.size() + 1);
   return GH_OK;
 }
+
+// Host plan of a batched decode (gaphuff.h, "batched decode"): where every stream's words,
+// gap words, work units and output bytes lie.  Host arithmetic only (gh_core.cpp), shared
+// by gh_batch_load / gh_batch_load_device (gh_decode.hip) and tests/sanitize/batch_fuzz.cpp.
+constexpr uint32_t BATCH_UNIT_SEGS = 256;              // segments per work unit (one wave block)
+constexpr uint32_t BATCH_MAX_STREAMS = 1u << 24;
+constexpr uint64_t BATCH_MAX_G = (1ull << 32) - 256;   // per-stream segments, exclusive
+constexpr uint64_t BATCH_MAX_UNITS = 1ull << 31;       // work units of a batch, exclusive
+struct BatchExtent {
+  uint64_t pay_off;    // first payload word in the payload arena (a multiple of 4: 16 bytes)
+  uint64_t pay_words;  // words the stream owns there: 4 G + 4 (0 when G = 0), W copied, the rest zero
+  uint64_t gap_off;    // first gap word in the gap arena
+  uint64_t gap_words;  // ceil(G / 8)
+  uint64_t unit0;      // first work unit; the stream has ceil(G / 256) of them
+  uint64_t out_off;    // first output byte (gh_batch_layout)
+};
+struct BatchPlan {
+  std::vector<BatchExtent> ext;  // nstreams entries
+  uint64_t pay_words = 0, gap_words = 0, nunits = 0, out_bytes = 0;  // arena sizes, units, output arena
+};
+// GH_E_ARG beyond the limits above, on W outside [4G - 3, 4G] (W = 0 when G = 0) and on
+// sums that overflow; the message names the stream's index.
+int batch_plan(const uint64_t* n, const uint64_t* w, const uint64_t* g, uint32_t nstreams, BatchPlan& out);
 
 // Encoder plan from plan->n and plan->count[] (symbol order, package-merge lengths,
 // canonical codes, sizes, header version); shared by the host and GPU encoders.

@@ -62,6 +62,9 @@ EXPORTED = (
     "gh_index_slice_extent", "gh_encode_index_slice", "gh_index_image_init", "gh_index_slice_merge",
     "gh_ectx_index_slice", "gh_ectx_load_device", "gh_ectx_merge_device", "gh_encode_sharded_index",
     "gh_ectx_kernel_shape", "gh_enc_kernel_shapes", "gh_enc_kernel_shape_for", "gh_sync_lut_bits",
+    "gh_batch_create", "gh_batch_destroy", "gh_batch_layout", "gh_batch_load", "gh_batch_load_device",
+    "gh_batch_decode", "gh_batch_wait", "gh_batch_status", "gh_batch_output", "gh_batch_offsets",
+    "gh_batch_download", "gh_batch_kernel_shape", "gh_batch_kernel_shapes",
 )
 
 
@@ -135,6 +138,17 @@ class gh_gather_piece(ctypes.Structure):
 class gh_gather_report(ctypes.Structure):
     _fields_ = [("out_bytes", ctypes.c_uint64), ("npieces", ctypes.c_uint64), ("status", ctypes.c_uint32),
                 ("kernel_ms", ctypes.c_float)]
+
+
+class gh_batch_item(ctypes.Structure):
+    _fields_ = [("syms", ctypes.POINTER(gh_sym)), ("nsyms", ctypes.c_uint32), ("n", ctypes.c_uint64),
+                ("w", ctypes.c_uint64), ("g", ctypes.c_uint64), ("d_payload", ctypes.c_void_p),
+                ("d_gap_words", ctypes.c_void_p)]
+
+
+class gh_batch_report(ctypes.Structure):
+    _fields_ = [("out_bytes", ctypes.c_uint64), ("nstreams", ctypes.c_uint32), ("bad_streams", ctypes.c_uint32),
+                ("status", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
 
 
 class gh_sync_report(ctypes.Structure):
@@ -245,6 +259,19 @@ def lib() -> ctypes.CDLL:
             "gh_enc_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_enc_kernel_shape_for": ([U64, U64, I, ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_sync_lut_bits": ([], I),
+            "gh_batch_create": ([I, ctypes.POINTER(P)], I),
+            "gh_batch_destroy": ([P], I),
+            "gh_batch_layout": ([P, U32, P], I),
+            "gh_batch_load": ([P, ctypes.POINTER(gh_stream), U32], I),
+            "gh_batch_load_device": ([P, ctypes.POINTER(gh_batch_item), U32, P], I),
+            "gh_batch_decode": ([P, P, U64, P, I], I),
+            "gh_batch_wait": ([P, ctypes.POINTER(gh_batch_report)], I),
+            "gh_batch_status": ([P, P, P, U32], I),
+            "gh_batch_output": ([P, ctypes.POINTER(P), ctypes.POINTER(U64)], I),
+            "gh_batch_offsets": ([P, P, U32], I),
+            "gh_batch_download": ([P, U32, P, U64], I),
+            "gh_batch_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_batch_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -858,6 +885,135 @@ def decode(file_bytes, ngpus: int = 1, devices: Optional[Sequence[int]] = None,
     r = gh_report()
     _check(lib().gh_decode(ctypes.byref(s.c), _ptr(out), out.size, ctypes.byref(o), ctypes.byref(r)))
     return out[: s.n]
+
+
+# --------------------------------------------------------------------------- batched decode
+def batch_layout(ns) -> np.ndarray:
+    """Output offsets of a batch of streams of ``ns`` bytes (gh_batch_layout): ``len(ns) + 1``
+    uint64, every stream 16-byte aligned, the last entry the arena size.  Needs no device."""
+    n = np.ascontiguousarray(ns, dtype=np.uint64)
+    off = np.zeros(n.size + 1, dtype=np.uint64)
+    _check(lib().gh_batch_layout(_ptr(n) if n.size else None, n.size, _ptr(off)))
+    return off
+
+
+def batch_kernel_shapes() -> list:
+    """Every kernel name a batch load can pick (gh_batch_kernel_shapes); needs no device."""
+    buf = ctypes.create_string_buffer(1 << 10)
+    _check(lib().gh_batch_kernel_shapes(buf, len(buf)))
+    return buf.value.decode().split()
+
+
+class BatchDecoder:
+    """One gh_batch: many independent streams resident on one GPU, decoded by one fixed set
+    of kernel launches per batch."""
+
+    def __init__(self, device: int = 0):
+        self._h = ctypes.c_void_p()
+        _check(lib().gh_batch_create(device, ctypes.byref(self._h)))
+        self.device = device
+        self.ns: list = []  # output bytes of every loaded stream
+
+    def close(self) -> None:
+        if self._h:
+            lib().gh_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def load(self, images_or_streams) -> None:
+        """Load a batch from host memory: compressed.huff images (bytes / np.uint8) or parsed
+        :class:`Stream` objects, in batch order (gh_batch_load)."""
+        streams = [s if isinstance(s, Stream) else parse(s) for s in images_or_streams]
+        arr = (gh_stream * max(1, len(streams)))()
+        for i, s in enumerate(streams):
+            arr[i] = s.c
+        _check(lib().gh_batch_load(self._h, arr, len(streams)))
+        self.ns = [s.n for s in streams]
+
+    def load_device(self, items, hip_stream: int = 0) -> None:
+        """Load a batch whose words are device memory (gh_batch_load_device): ``items`` are
+        ``(stream, payload_ptr, gap_ptr)`` with a :class:`Stream` for the sizes and the code
+        (e.g. a parsed image or :meth:`Stream.from_plan`) and two 4-byte-aligned device
+        addresses as integers."""
+        items = list(items)
+        arr = (gh_batch_item * max(1, len(items)))()
+        for i, (s, pay, gap) in enumerate(items):
+            arr[i].syms, arr[i].nsyms = s.c.syms, s.c.nsyms
+            arr[i].n, arr[i].w, arr[i].g = s.c.n, s.c.w, s.c.g
+            arr[i].d_payload, arr[i].d_gap_words = pay or None, gap or None
+        _check(lib().gh_batch_load_device(self._h, arr, len(items), ctypes.c_void_p(hip_stream or None)))
+        self.ns = [s.n for s, _, _ in items]
+
+    def decode(self, dst_ptr: int = 0, dst_len: int = 0, hip_stream: int = 0, timed: bool = True) -> None:
+        """Enqueue one decode of the batch into the device memory at ``dst_ptr`` (16-byte
+        aligned, ``dst_len`` bytes), or into the batch's own arena, and return."""
+        _check(lib().gh_batch_decode(self._h, ctypes.c_void_p(dst_ptr or None), dst_len,
+                                     ctypes.c_void_p(hip_stream or None), int(timed)))
+
+    def wait(self) -> gh_batch_report:
+        """Wait for the last :meth:`decode` and return its report; raises
+        :class:`GapHuffError` (with the report as ``.report``) when a stream was bad."""
+        r = gh_batch_report()
+        rc = lib().gh_batch_wait(self._h, ctypes.byref(r))
+        if rc != GH_OK:
+            e = GapHuffError(rc, lib().gh_last_error().decode(errors="replace"))
+            e.report = r
+            raise e
+        return r
+
+    def status(self):
+        """(GH_ST_* bits, codewords counted) per stream, as uint32 / uint64 arrays."""
+        st = np.zeros(len(self.ns), dtype=np.uint32)
+        sy = np.zeros(len(self.ns), dtype=np.uint64)
+        _check(lib().gh_batch_status(self._h, _ptr(st) if st.size else None, _ptr(sy) if sy.size else None, st.size))
+        return st, sy
+
+    def offsets(self) -> np.ndarray:
+        off = np.zeros(len(self.ns) + 1, dtype=np.uint64)
+        _check(lib().gh_batch_offsets(self._h, _ptr(off), off.size))
+        return off
+
+    def output(self):
+        """(device address, capacity) of the batch's own output arena."""
+        p = ctypes.c_void_p()
+        cap = ctypes.c_uint64()
+        _check(lib().gh_batch_output(self._h, ctypes.byref(p), ctypes.byref(cap)))
+        return int(p.value or 0), int(cap.value)
+
+    def download(self, i: int) -> np.ndarray:
+        """Stream ``i``'s bytes from the batch's own arena."""
+        out = np.empty(self.ns[i], dtype=np.uint8)
+        _check(lib().gh_batch_download(self._h, i, _ptr(out) if out.size else None, out.size))
+        return out
+
+    def download_all(self) -> list:
+        return [self.download(i) for i in range(len(self.ns))]
+
+    def kernel_shape(self) -> str:
+        """Name of the kernel instantiations the last load picked (gh_batch_kernel_shape)."""
+        buf = ctypes.create_string_buffer(64)
+        _check(lib().gh_batch_kernel_shape(self._h, buf, len(buf)))
+        return buf.value.decode()
+
+
+def decode_batch(images, device: int = 0) -> list:
+    """Decode many compressed.huff images as one batch; returns their bytes in order."""
+    with BatchDecoder(device) as b:
+        b.load(images)
+        b.decode()
+        b.wait()
+        return b.download_all()
 
 
 # --------------------------------------------------------------------------- random access

@@ -1,6 +1,9 @@
 // bin/decoder <compressed.huff | raw container> <output> [--gpus N] [--shards S] [--reps R] [--json]
 //             [--verify FILE] [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]
 //             [--index FILE --ranges FILE]
+// bin/decoder --batch LIST
+// --batch LIST (a text file, one input<TAB>output per line) decodes all inputs as one batch
+// (gh_batch_*: one fixed set of launches however many streams) and writes every output.
 // --shards S (default: one per GPU) splits the gap segments into S shards, shard k on
 // device k mod N, each streaming its own payload range and writing at its offset.
 // A raw-stream container (bin/encoder --raw, GH_RAW_MAGIC) is decoded by the
@@ -139,12 +142,94 @@ static int gather_main(const char* input, const char* output, const char* index_
   return 0;
 }
 
+// --batch LIST: every line of the text file is `input<TAB>output`; all inputs are decoded as
+// one batch (gh_batch_*) and every output file is written.  A corrupt stream: exit code 1,
+// its line named, no output written for it.
+static int batch_main(const char* list_file) {
+  std::vector<uint8_t> text;
+  if (!read_file(list_file, text)) { std::fprintf(stderr, "decoder: Could not open batch list %s\n", list_file); return 1; }
+  std::vector<std::string> in, out;
+  std::vector<size_t> line_of;
+  {
+    const std::string t(text.begin(), text.end());
+    size_t at = 0, line = 0;
+    while (at < t.size()) {
+      size_t nl = t.find('\n', at);
+      if (nl == std::string::npos) nl = t.size();
+      std::string ln = t.substr(at, nl - at);
+      at = nl + 1;
+      ++line;
+      if (!ln.empty() && ln.back() == '\r') ln.pop_back();
+      if (ln.empty()) continue;
+      const size_t tab = ln.find('\t');
+      if (tab == std::string::npos || tab == 0 || tab + 1 == ln.size()) {
+        std::fprintf(stderr, "decoder: %s: line %zu: expected input<TAB>output\n", list_file, line);
+        return 1;
+      }
+      in.push_back(ln.substr(0, tab));
+      out.push_back(ln.substr(tab + 1));
+      line_of.push_back(line);
+    }
+  }
+  const size_t ns = in.size();
+  std::vector<std::vector<uint8_t>> img(ns);
+  std::vector<gh_stream> streams(ns);
+  int rc;
+  for (size_t i = 0; i < ns; ++i) {
+    if (!read_file(in[i].c_str(), img[i])) {
+      std::fprintf(stderr, "decoder: %s: line %zu: Could not open input file %s\n", list_file, line_of[i], in[i].c_str());
+      return 1;
+    }
+    if ((rc = gh_stream_parse(img[i].data(), img[i].size(), &streams[i]))) {
+      std::fprintf(stderr, "decoder: %s: line %zu: %s: ", list_file, line_of[i], in[i].c_str());
+      return die("bad compressed stream", rc);
+    }
+  }
+  if (gh_device_count() < 1) return die("no HIP device", GH_E_NODEV);
+  gh_batch* b = nullptr;
+  if ((rc = gh_batch_create(0, &b))) return die("device init", rc);
+  const double t0 = now_ms();
+  if ((rc = gh_batch_load(b, streams.data(), (uint32_t)ns))) { gh_batch_destroy(b); return die("batch load", rc); }
+  const double t1 = now_ms();
+  gh_batch_report rep{};
+  if ((rc = gh_batch_decode(b, nullptr, 0, nullptr, 1))) { gh_batch_destroy(b); return die("batch decode", rc); }
+  rc = gh_batch_wait(b, &rep);
+  const double t2 = now_ms();
+  std::vector<uint32_t> status(ns, 0);
+  if (rc == GH_E_CORRUPT && gh_batch_status(b, status.data(), nullptr, (uint32_t)ns) == GH_OK) {
+    for (size_t i = 0; i < ns; ++i)
+      if (status[i])
+        std::fprintf(stderr, "decoder: %s: line %zu: %s: corrupt stream (status 0x%x)\n", list_file, line_of[i],
+                     in[i].c_str(), status[i]);
+  } else if (rc) {
+    gh_batch_destroy(b);
+    return die("batch decode", rc);
+  }
+  std::vector<uint8_t> bytes;
+  for (size_t i = 0; i < ns; ++i) {
+    if (status[i]) continue;
+    bytes.resize((size_t)streams[i].n);
+    int r = gh_batch_download(b, (uint32_t)i, bytes.data(), bytes.size());
+    if (r) { gh_batch_destroy(b); return die("download", r); }
+    FILE* f = std::fopen(out[i].c_str(), "wb");
+    bool okw = f && std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (f) okw = std::fclose(f) == 0 && okw;
+    if (!okw) { gh_batch_destroy(b); std::fprintf(stderr, "decoder: cannot write %s\n", out[i].c_str()); return 1; }
+  }
+  gh_batch_destroy(b);
+  std::printf("Batch: %u streams, %llu bytes; load %.3f ms, kernel %.3f ms, call %.3f ms, %u bad\n", rep.nstreams,
+              (unsigned long long)rep.out_bytes, t1 - t0, rep.kernel_ms, t2 - t1, rep.bad_streams);
+  return rc ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc == 3 && !std::strcmp(argv[1], "--batch")) return batch_main(argv[2]);
   if (argc < 3) {
     std::fprintf(stderr,
                  "Usage: bin/decoder input output [--gpus N] [--shards S] [--reps R] [--json] [--verify FILE]\n"
                  "       [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]\n"
-                 "       [--index FILE --ranges FILE]\n");
+                 "       [--index FILE --ranges FILE]\n"
+                 "       bin/decoder --batch LIST   (LIST: one input<TAB>output per line)\n");
     return 2;
   }
   int ngpus = 1, reps = 1, nshards = 0;

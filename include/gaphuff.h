@@ -557,6 +557,91 @@ int gh_ctx_gather_times(gh_ctx* ctx, float* plan_ms, float* gather_ms);
  * it.  *npieces is always written; GH_E_SMALL when cap is smaller. */
 int gh_ctx_gather_pieces(gh_ctx* ctx, gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces);
 
+/* ---- batched decode: many independent streams, one launch per batch ------------------ */
+/* Many small streams, each a complete compressed.huff with its own code (a page, a column
+ * chunk, a tensor, a message), decoded by one fixed set of kernel launches however many
+ * they are.  No reference counterpart (the reference decodes one stream per call).  A
+ * gh_batch is bound to one device and used from one host thread at a time.
+ *
+ * Output layout: stream i's bytes start at out_off[i] = sum_{j<i} round_up(n_j, 16) of the
+ * destination arena, so every stream is 16-byte aligned; out_off[nstreams] is the arena
+ * size.  Bytes in [out_off[i] + n_i, out_off[i+1]) are never written.
+ *
+ * Load: every stream is validated on the host (gh_stream_validate's checks, O(nsyms)); a bad
+ * stream fails the whole load with that check's code, the message naming the stream's
+ * index.  Payloads and gap words are packed into one library-owned device arena by a few
+ * large copies (each payload 16-byte aligned and zero padded up to 4 G + 4 words, each gap
+ * array 4-byte aligned), and the decode tables of ALL streams are built on the device by one
+ * kernel from the uploaded (symbol, length) lists: per stream the canonical fallback tables
+ * and a single-codeword lookup table {len | sym << 8} of min(maxlen, 10) bits.
+ * Limits (GH_E_ARG beyond them): nstreams <= 2^24; per-stream G < 2^32 - 256; fewer than
+ * 2^31 work units (a unit is 256 segments of one stream) in a batch.  Empty streams (N = 0,
+ * G = 0, no symbols) decode to nothing; a stream with segments needs a code (GH_E_TABLE).
+ * nstreams = 0 is GH_OK.  A load replaces the previous batch; buffers are reused when
+ * large enough. */
+typedef struct gh_batch gh_batch;
+typedef struct gh_batch_item {
+  const gh_sym* syms;           /* host memory: nsyms entries, file order                   */
+  uint32_t nsyms;
+  uint64_t n, w, g;             /* as gh_stream                                              */
+  const uint32_t* d_payload;    /* device memory, 4-byte aligned: w words                   */
+  const uint32_t* d_gap_words;  /* device memory, 4-byte aligned: ceil(g / 8) words         */
+} gh_batch_item;
+typedef struct gh_batch_report {
+  uint64_t out_bytes;    /* sum of n_i                                                      */
+  uint32_t nstreams;
+  uint32_t bad_streams;  /* streams with a status bit set                                   */
+  uint32_t status;       /* OR of the streams' GH_ST_* bits                                 */
+  float kernel_ms;       /* HIP-event time of the last timed decode (all its kernels)       */
+  uint32_t launches;     /* kernels one decode launches: a constant, whatever nstreams      */
+} gh_batch_report;
+/* GH_E_NODEV without a usable gfx950 device, as gh_ctx_create. */
+int gh_batch_create(int device, gh_batch** out);
+int gh_batch_destroy(gh_batch* b);
+/* out_off[0 .. nstreams] for streams of n[i] bytes.  Host arithmetic only, no device.
+ * GH_E_ARG: null pointers (n may be NULL when nstreams = 0), a sum that overflows 64 bits. */
+int gh_batch_layout(const uint64_t* n, uint32_t nstreams, uint64_t* out_off);
+/* Load parsed streams from host memory (gh_stream_parse output; the words may sit at any
+ * alignment).  Synchronous. */
+int gh_batch_load(gh_batch* b, const gh_stream* streams, uint32_t nstreams);
+/* Load streams whose words are device memory (any address the batch's device can read): one
+ * copy kernel reads the pointer table and copies every stream's words into the padded arena,
+ * on the batch's stream, after an event recorded on hip_stream (NULL: the default stream),
+ * so a producer enqueued there has finished first.  Synchronous; the caller's arrays are
+ * not needed after the call.  Everything downstream is as after gh_batch_load. */
+int gh_batch_load_device(gh_batch* b, const gh_batch_item* items, uint32_t nstreams, void* hip_stream);
+/* Enqueue one decode of the loaded batch on hip_stream (NULL = the batch's own stream) and
+ * return.  d_dst: device memory, 16-byte aligned, dst_len >= out_off[nstreams]; NULL selects
+ * the batch's own output arena (allocated on demand; dst_len is ignored).  timed != 0
+ * brackets the kernels with HIP events.  GH_E_STATE before a load, GH_E_SMALL when dst_len
+ * is too small, GH_E_ARG on a misaligned d_dst. */
+int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void* hip_stream, int timed);
+/* Wait for the last decode and report it (rep may be NULL; it is filled before an error is
+ * returned).  GH_E_CORRUPT when any stream holds fewer than its N codewords or met a bit
+ * pattern outside its code; GH_E_STATE when no decode has been enqueued since the load. */
+int gh_batch_wait(gh_batch* b, gh_batch_report* rep);
+/* Per stream, after gh_batch_wait: the GH_ST_* bits and the codewords counted over its
+ * segments, the last segment's padding included (as gh_report.symbols); either array may be
+ * NULL.  A bad stream never changes another stream's bytes and touches nothing outside its
+ * own extents: its walk is bounded by its G segments, its stores are clipped at its N.
+ * GH_E_SMALL when cap < nstreams. */
+int gh_batch_status(gh_batch* b, uint32_t* status, uint64_t* symbols, uint32_t cap);
+/* The batch's own output arena (NULL / 0 before a decode used it). */
+int gh_batch_output(gh_batch* b, void** d_out, uint64_t* cap);
+/* out_off[0 .. nstreams] of the loaded batch; GH_E_SMALL when cap < nstreams + 1. */
+int gh_batch_offsets(gh_batch* b, uint64_t* out_off, uint32_t cap);
+/* The first nbytes (<= n_i) of stream `stream` from the batch's own arena to host memory;
+ * waits for the last decode. */
+int gh_batch_download(gh_batch* b, uint32_t stream, uint8_t* dst, uint64_t nbytes);
+/* The batch decode's count and write kernels are one of two instantiation pairs, named
+ * "batch<fb=0>" (every stream's code is complete and no longer than the lookup table) and
+ * "batch<fb=1>" (some lookup can miss: the canonical fallback is compiled in).
+ * gh_batch_kernel_shape: the name the last load picked (empty for a batch without
+ * segments); GH_E_STATE before a load.  gh_batch_kernel_shapes: every name, one per line;
+ * needs no device.  Neither is part of gh_kernel_shapes. */
+int gh_batch_kernel_shape(gh_batch* b, char* buf, size_t cap);
+int gh_batch_kernel_shapes(char* buf, size_t cap);
+
 /* ---- self-synchronising decode of gap-less streams ---- */
 /* Replaces CUHD's decoder for raw Huffman streams without a gap array
  * (gpuhd/src/cuhd_gpu_decoder.cu:145-523, CUHDGPUDecoder::decode declared at
