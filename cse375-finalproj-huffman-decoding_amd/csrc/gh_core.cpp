@@ -438,6 +438,61 @@ int gh::batch_plan(const uint64_t* n, const uint64_t* w, const uint64_t* g, uint
 }
 
 // ---------------------------------------------------------------------------
+// Batched encode: the host layout (gaphuff.h, "batched encode").  No device.
+// ---------------------------------------------------------------------------
+int gh::ebatch_in_plan(const uint64_t* n, uint32_t nstreams, EBatchInPlan& out) {
+  out = EBatchInPlan();
+  if (nstreams && !n) return fail(GH_E_ARG, "null argument");
+  if (nstreams > EBATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  out.ext.resize(nstreams);
+  uint64_t at = 0, units = 0, sum = 0;
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    const std::string who = "stream " + std::to_string(i) + ": ";
+    const uint64_t nu = n[i] / EBATCH_UNIT_BYTES + (n[i] % EBATCH_UNIT_BYTES ? 1 : 0);
+    if (nu >= EBATCH_MAX_UNITS || (units += nu) >= EBATCH_MAX_UNITS)
+      return fail(GH_E_ARG, who + "the batch reaches 2^31 work units");
+    EBatchInExtent& e = out.ext[i];
+    e.in_off = at;
+    // every lane's 16-byte load of every unit, and the at most 32 bytes after a unit that
+    // complete its last word, lie inside the stream's own extent
+    e.in_bytes = nu ? nu * EBATCH_UNIT_BYTES + EBATCH_TAIL_BYTES : 0;
+    e.unit0 = units - nu;
+    at += e.in_bytes;  // (< 2^31 * 1024 + 2^24 * 32)
+    sum += n[i];       // (< 2^41)
+  }
+  out.in_bytes = at;
+  out.nunits = units;
+  out.sum_n = sum;
+  return GH_OK;
+}
+
+int gh::ebatch_out_plan(const uint64_t* w, const uint64_t* g, uint32_t nstreams, EBatchOutPlan& out) {
+  out = EBatchOutPlan();
+  if (nstreams && (!w || !g)) return fail(GH_E_ARG, "null argument");
+  if (nstreams > EBATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  out.ext.resize(nstreams);
+  uint64_t pay = 0, gap = 0;
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    const std::string who = "stream " + std::to_string(i) + ": ";
+    if (g[i] != w[i] / 4 + (w[i] % 4 ? 1 : 0)) return fail(GH_E_ARG, who + "G is not ceil(W / 4)");
+    EBatchOutExtent& e = out.ext[i];
+    uint64_t pw, gw;
+    if (!add_u64(w[i], 3, &pw)) return fail(GH_E_ARG, who + "the payload arena overflows 64 bits");
+    pw &= ~3ull;
+    gw = (ceil_div(g[i], GH_GAPS_PER_WORD) + 3) & ~3ull;  // (G <= 2^62)
+    e.pay_off = pay;
+    e.pay_words = pw;
+    e.gap_off = gap;
+    e.gap_words = gw;
+    if (!add_u64(pay, pw, &pay) || pay > (~0ull >> 2)) return fail(GH_E_ARG, who + "the payload arena overflows 64 bits");
+    gap += gw;  // (<= pay)
+  }
+  out.pay_words = pay;
+  out.gap_words = gap;
+  return GH_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Encoder
 // ---------------------------------------------------------------------------
 extern "C" int gh_encode_plan_make(const uint8_t* in, uint64_t n, int threads,

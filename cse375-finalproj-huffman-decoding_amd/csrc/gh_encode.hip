@@ -30,6 +30,8 @@
 //                        offsets: see the kernel.
 //   gh_enc_merge_kernel  (gh_ectx_merge_device) ORs an encode's words and gap words into
 //                        the stream's device-resident arrays: see enc_merge_span.
+// Batched encode (gh_ebatch_*): many inputs with their own codes, wave-sized units; its
+// kernels are in gh_ebatch.hip, its host side at the end of this file.
 // Sliced encode (gh_ectx_encode_slice): the same kernels on an input that is one slice of
 // a longer stream; the block scan starts at the slice's first stream bit and the write
 // kernel's SLICE variant indexes its outputs from the slice's origin; the index kernel's
@@ -41,6 +43,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -680,6 +685,8 @@ __global__ __launch_bounds__(MERGE_TB) void gh_enc_merge_kernel(const EncMergePa
   enc_merge_span(p.sg, p.dg, p.ng, tid, nth);
 }
 
+#include "gh_ebatch.hip"
+
 }  // namespace gh
 
 using namespace gh;
@@ -1270,3 +1277,375 @@ extern "C" int gh_encode_sharded_index(const uint8_t* in, uint64_t n, const gh_o
   const ShardedIndex ix{log2_stride, index_out, index_len, index_ms};
   return encode_sharded_run(in, n, o, nslices, force_version, out, out_len, plan_out, kernel_ms, &ix);
 }
+
+// ---- batched encode (gaphuff.h; kernels: gh_ebatch.hip; host layout: gh::ebatch_*_plan) ---
+constexpr uint32_t EBATCH_LAUNCHES = 5;  // two arena memsets, then bits, scan, write
+static const char* const EBATCH_SHAPE = "ebatch<lut=1>";
+
+struct gh_ebatch {
+  int device = 0, num_cu = 0;
+  Stream stream;
+  Event done;   // end of the last encode, on whatever stream it ran
+  Event ev_in;  // gh_ebatch_load_device: the producer stream's position
+  EventPair ev, ev_hist;
+  DevBuf in, unit0, items;                 // the loaded batch
+  DevBuf code;                             // one EBatchDesc per stream, then 256 table entries per stream
+  DevBuf counts;                           // 256 u64 per stream
+  DevBuf unit_bits, unit_off, flags;       // encode scratch; flags: 4 summary words, then a status word per stream
+  DevBuf payload, gaps;                    // the output arenas
+  EBatchInPlan inp;
+  EBatchOutPlan outp;
+  std::vector<uint64_t> n;
+  std::vector<gh_encode_plan> plans;
+  uint32_t nstreams = 0;
+  uint64_t out_bytes = 0;
+  float hist_ms = 0, plan_host_ms = 0;
+  bool loaded = false, planned = false, enqueued = false, timed = false;
+  ~gh_ebatch() {
+    (void)hipSetDevice(device);
+    if (enqueued) (void)hipEventSynchronize(done);  // (it may run on a caller's stream)
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
+
+extern "C" int gh_ebatch_create(int device, gh_ebatch** out) {
+  if (!out) return fail(GH_E_ARG, "null batch pointer");
+  *out = nullptr;
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0)
+    return fail(GH_E_NODEV, "no HIP device visible (the GPU encoder has no CPU fallback)");
+  if (device < 0 || device >= nd) return fail(GH_E_ARG, "device ordinal out of range");
+  hipDeviceProp_t prop;
+  GH_HIP(hipGetDeviceProperties(&prop, device));
+  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
+    return fail(GH_E_NODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
+  std::unique_ptr<gh_ebatch> b(new gh_ebatch());
+  b->device = device;
+  b->num_cu = prop.multiProcessorCount;
+  GH_HIP(hipSetDevice(device));
+  if (int rc = b->stream.create()) return rc;
+  if (int rc = b->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = b->ev_in.create(hipEventDisableTiming)) return rc;
+  if (int rc = b->ev.create()) return rc;
+  if (int rc = b->ev_hist.create()) return rc;
+  *out = b.release();
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_destroy(gh_ebatch* b) {
+  delete b;
+  return GH_OK;
+}
+
+// The descriptors' load-time half: where every stream's bytes are.
+static std::vector<EBatchDesc> ebatch_descs(const gh_ebatch* b) {
+  std::vector<EBatchDesc> d(b->nstreams);
+  for (uint32_t i = 0; i < b->nstreams; ++i) {
+    d[i] = EBatchDesc{};
+    d[i].in_off = b->inp.ext[i].in_off;
+    d[i].n = b->n[i];
+  }
+  return d;
+}
+
+// src[i]: stream i's bytes, host memory or (device) device memory.
+static int ebatch_load(gh_ebatch* b, const std::vector<const uint8_t*>& src, const uint64_t* n, bool device,
+                       void* hip_stream) {
+  const uint32_t ns = (uint32_t)src.size();
+  GH_HIP(hipSetDevice(b->device));
+  if (b->enqueued) GH_HIP(hipEventSynchronize(b->done));  // the previous batch's encode reads what is replaced
+  GH_HIP(hipStreamSynchronize(b->stream));
+  b->loaded = b->planned = b->enqueued = false;
+  EBatchInPlan inp;
+  if (int rc = ebatch_in_plan(n, ns, inp)) return rc;
+  for (uint32_t i = 0; i < ns; ++i)
+    if (n[i] && !src[i]) return fail(GH_E_ARG, "stream " + std::to_string(i) + ": null input pointer");
+  b->n.assign(n, n + ns);
+  b->nstreams = ns;
+  b->inp = std::move(inp);
+  const EBatchInPlan& ip = b->inp;
+  std::vector<uint32_t> unit0(ns + 1);
+  for (uint32_t i = 0; i < ns; ++i) unit0[i] = (uint32_t)ip.ext[i].unit0;
+  unit0[ns] = (uint32_t)ip.nunits;
+  if (int rc = b->unit0.reserve(4ull * (ns + 1))) return rc;
+  GH_HIP(hipMemcpy(b->unit0.get(), unit0.data(), 4ull * (ns + 1), hipMemcpyHostToDevice));
+  if (int rc = b->code.reserve(std::max<uint64_t>((sizeof(EBatchDesc) + 1024ull) * ns, 16))) return rc;
+  if (ns) {
+    const std::vector<EBatchDesc> d = ebatch_descs(b);
+    GH_HIP(hipMemcpy(b->code.get(), d.data(), sizeof(EBatchDesc) * (uint64_t)ns, hipMemcpyHostToDevice));
+  }
+  if (int rc = b->in.reserve(std::max<uint64_t>(ip.in_bytes, 16))) return rc;
+  if (!device) {
+    // the arena is assembled in host memory, padding included, and goes up in one copy
+    std::vector<uint8_t> stage(ip.in_bytes, 0);
+    for (uint32_t i = 0; i < ns; ++i)
+      if (n[i]) std::memcpy(stage.data() + ip.ext[i].in_off, src[i], n[i]);
+    if (!stage.empty()) {
+      if (use_staged(stage.size())) {
+        if (int rc = h2d_staged(b->device, stage.data(), stage.size(), b->in.get())) return rc;
+      } else {
+        GH_HIP(hipMemcpy(b->in.get(), stage.data(), stage.size(), hipMemcpyHostToDevice));
+      }
+    }
+  } else if (ip.in_bytes) {
+    std::vector<EBatchCopyItem> items(ns);
+    for (uint32_t i = 0; i < ns; ++i) items[i] = EBatchCopyItem{src[i], n[i], ip.ext[i].in_off, ip.ext[i].in_bytes};
+    if (int rc = b->items.reserve(sizeof(EBatchCopyItem) * (uint64_t)ns)) return rc;
+    GH_HIP(hipMemcpy(b->items.get(), items.data(), sizeof(EBatchCopyItem) * (uint64_t)ns, hipMemcpyHostToDevice));
+    // after what the producer's stream holds now, then one copy kernel on the batch's stream
+    GH_HIP(hipEventRecord(b->ev_in, (hipStream_t)hip_stream));
+    GH_HIP(hipStreamWaitEvent(b->stream, b->ev_in, 0));
+    hipLaunchKernelGGL(gh_ebatch_copy_kernel, dim3(std::min<uint32_t>(ns, 4096u), EB_COPY_Y), dim3(256), 0, b->stream,
+                       b->items.get<EBatchCopyItem>(), ns, b->in.get<uint8_t>());
+    GH_HIP(hipGetLastError());
+    GH_HIP(hipStreamSynchronize(b->stream));
+  }
+  b->loaded = true;
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_load(gh_ebatch* b, const uint8_t* const* in, const uint64_t* n, uint32_t nstreams) {
+  if (!b || (nstreams && (!in || !n))) return fail(GH_E_ARG, "null argument");
+  if (nstreams > EBATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  return ebatch_load(b, std::vector<const uint8_t*>(in, in + nstreams), n, false, nullptr);
+}
+
+extern "C" int gh_ebatch_load_device(gh_ebatch* b, const gh_ebatch_item* items, uint32_t nstreams, void* hip_stream) {
+  if (!b || (nstreams && !items)) return fail(GH_E_ARG, "null argument");
+  if (nstreams > EBATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  std::vector<const uint8_t*> src(nstreams);
+  std::vector<uint64_t> n(nstreams);
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    src[i] = (const uint8_t*)items[i].d_in;
+    n[i] = items[i].n;
+  }
+  return ebatch_load(b, src, n.data(), true, hip_stream);
+}
+
+// GH_EBATCH_GRID=k (tests): k workgroups for the per-unit kernels (histogram at plan time;
+// bits and write at encode time), so that one wave walks many units and streams.
+static uint32_t ebatch_grid(const gh_ebatch* b) {
+  if (const char* eg = getenv("GH_EBATCH_GRID")) return (uint32_t)std::clamp<long>(atol(eg), 1, 1l << 20);
+  const uint64_t want = ceil_div(b->inp.nunits, EB_WAVES);
+  return (uint32_t)std::clamp<uint64_t>(want, 1, 8ull * (uint64_t)b->num_cu);
+}
+
+static EBatchParams ebatch_params(const gh_ebatch* b) {
+  EBatchParams p{};
+  p.desc = b->code.get<EBatchDesc>();
+  p.tables = (const uint32_t*)(b->code.get<uint8_t>() + sizeof(EBatchDesc) * (uint64_t)b->nstreams);
+  p.unit0 = b->unit0.get<uint32_t>();
+  p.in = b->in.get<uint8_t>();
+  p.counts = b->counts.get<unsigned long long>();
+  p.unit_bits = b->unit_bits.get<uint32_t>();
+  p.unit_off = b->unit_off.get<unsigned long long>();
+  p.payload = b->payload.get<uint32_t>();
+  p.gaps = b->gaps.get<uint32_t>();
+  p.summary = b->flags.get<unsigned int>();
+  p.status = p.summary ? p.summary + 4 : nullptr;
+  p.nstreams = b->nstreams;
+  p.nunits = (uint32_t)b->inp.nunits;
+  return p;
+}
+
+extern "C" int gh_ebatch_plan(gh_ebatch* b, int force_version, int threads) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_ebatch_plan before a load");
+  GH_HIP(hipSetDevice(b->device));
+  if (b->enqueued) GH_HIP(hipEventSynchronize(b->done));  // (the tables of the last encode are replaced)
+  b->planned = b->enqueued = false;
+  const uint32_t ns = b->nstreams;
+  const uint64_t nunits = b->inp.nunits;
+  // 1. every stream's histogram: one launch, 2. one read-back
+  std::vector<uint64_t> counts(256ull * ns, 0);
+  b->hist_ms = 0;
+  if (ns) {
+    if (int rc = b->counts.reserve(2048ull * ns)) return rc;
+    GH_HIP(hipMemsetAsync(b->counts.get(), 0, 2048ull * ns, b->stream));
+    GH_HIP(hipEventRecord(b->ev_hist.a, b->stream));
+    if (nunits) {
+      const EBatchParams p = ebatch_params(b);
+      hipLaunchKernelGGL(gh_ebatch_hist_kernel, dim3(ebatch_grid(b)), dim3(EB_TB), 0, b->stream, p);
+      GH_HIP(hipGetLastError());
+    }
+    GH_HIP(hipEventRecord(b->ev_hist.b, b->stream));
+    GH_HIP(hipMemcpyAsync(counts.data(), b->counts.get(), 2048ull * ns, hipMemcpyDeviceToHost, b->stream));
+    GH_HIP(hipStreamSynchronize(b->stream));
+    if (int rc = b->ev_hist.elapsed(&b->hist_ms)) return rc;
+  }
+  // 3. the host plans, threaded over streams (streams are handed out by a shared counter)
+  const auto t0 = std::chrono::steady_clock::now();
+  b->plans.assign(ns, gh_encode_plan{});
+  int nt = threads > 0 ? threads : (int)std::min(std::max(std::thread::hardware_concurrency(), 1u), 32u);
+  nt = (int)std::min<uint64_t>((uint64_t)nt, std::max<uint64_t>(ns / 16, 1));
+  std::atomic<uint32_t> next{0};
+  std::vector<int> rcs(nt, GH_OK);
+  std::vector<std::string> msgs(nt);
+  auto work = [&](int t) {
+    for (;;) {
+      const uint32_t i = next.fetch_add(1);
+      if (i >= ns || rcs[t]) return;
+      gh_encode_plan& pl = b->plans[i];
+      pl.n = b->n[i];
+      std::memcpy(pl.count, &counts[256ull * i], sizeof(pl.count));
+      int rc = plan_from_counts(&pl, force_version);
+      if (!rc)
+        for (int v = 0; v < 256; ++v)
+          if (pl.len[v] > GH_MAX_CODE_LEN) rc = fail(GH_E_TABLE, "code longer than 16 bits");
+      if (rc) {
+        rcs[t] = rc;
+        msgs[t] = "stream " + std::to_string(i) + ": " + gh_last_error();
+      }
+    }
+  };
+  if (nt <= 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back(work, t);
+    for (auto& t : th) t.join();
+  }
+  for (int t = 0; t < nt; ++t)
+    if (rcs[t]) return fail(rcs[t], msgs[t]);
+  b->plan_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  // 5. the output arenas (before the upload: the descriptors hold their offsets)
+  std::vector<uint64_t> w(ns), g(ns);
+  b->out_bytes = 0;
+  for (uint32_t i = 0; i < ns; ++i) {
+    w[i] = b->plans[i].w;
+    g[i] = b->plans[i].g;
+    b->out_bytes += b->plans[i].file_bytes;
+  }
+  if (int rc = ebatch_out_plan(w.data(), g.data(), ns, b->outp)) return rc;
+  // 4. one upload: the descriptors, then every stream's 256 left-aligned entries
+  if (ns) {
+    std::vector<uint8_t> up((sizeof(EBatchDesc) + 1024ull) * ns);
+    std::vector<EBatchDesc> d = ebatch_descs(b);
+    uint32_t* tab = (uint32_t*)(up.data() + sizeof(EBatchDesc) * (uint64_t)ns);
+    for (uint32_t i = 0; i < ns; ++i) {
+      const gh_encode_plan& pl = b->plans[i];
+      d[i].pay_off = b->outp.ext[i].pay_off;
+      d[i].gap_off = b->outp.ext[i].gap_off;
+      d[i].bits = pl.bits;
+      for (int v = 0; v < 256; ++v) {
+        const uint32_t l = pl.len[v];
+        tab[256ull * i + v] = l ? (pl.code[v] << (32u - l)) | l : 0u;
+      }
+    }
+    std::memcpy(up.data(), d.data(), sizeof(EBatchDesc) * (uint64_t)ns);
+    GH_HIP(hipMemcpy(b->code.get(), up.data(), up.size(), hipMemcpyHostToDevice));
+  }
+  if (int rc = b->payload.reserve(std::max<uint64_t>(4 * b->outp.pay_words, 16))) return rc;
+  if (int rc = b->gaps.reserve(std::max<uint64_t>(4 * b->outp.gap_words, 16))) return rc;
+  if (int rc = b->unit_bits.reserve(std::max<uint64_t>(4 * nunits, 16))) return rc;
+  if (int rc = b->unit_off.reserve(8 * (nunits + 1))) return rc;
+  if (int rc = b->flags.reserve(16 + 4ull * ns)) return rc;
+  b->planned = true;
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_plan_of(gh_ebatch* b, uint32_t stream, gh_encode_plan* out) {
+  if (!b || !out) return fail(GH_E_ARG, "null argument");
+  if (!b->planned) return fail(GH_E_STATE, "gh_ebatch_plan_of before a plan");
+  if (stream >= b->nstreams) return fail(GH_E_ARG, "no such stream in the batch");
+  *out = b->plans[stream];
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_encode(gh_ebatch* b, void* hip_stream, int timed) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->planned) return fail(GH_E_STATE, "gh_ebatch_encode before a plan");
+  GH_HIP(hipSetDevice(b->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)b->stream;
+  // encodes of one batch share its scratch and its arenas: they run in the order they were made
+  if (b->enqueued) GH_HIP(hipStreamWaitEvent(st, b->done, 0));
+  const EBatchParams p = ebatch_params(b);
+  if (timed) GH_HIP(hipEventRecord(b->ev.a, st));
+  // (no memset of the flags: the scan kernel writes every status word and the summary)
+  if (b->outp.pay_words) GH_HIP(hipMemsetAsync(b->payload.get(), 0, 4 * b->outp.pay_words, st));
+  if (b->outp.gap_words) GH_HIP(hipMemsetAsync(b->gaps.get(), 0, 4 * b->outp.gap_words, st));
+  if (b->nstreams) {
+    const uint32_t grid = ebatch_grid(b);
+    if (p.nunits) hipLaunchKernelGGL(gh_ebatch_bits_kernel, dim3(grid), dim3(EB_TB), 0, st, p);
+    hipLaunchKernelGGL(gh_ebatch_scan_kernel, dim3(1), dim3(EB_SCAN_TB), 0, st, p);
+    if (p.nunits) hipLaunchKernelGGL(gh_ebatch_write_kernel, dim3(grid), dim3(EB_TB), 0, st, p);
+    GH_HIP(hipGetLastError());
+  }
+  if (timed) GH_HIP(hipEventRecord(b->ev.b, st));
+  GH_HIP(hipEventRecord(b->done, st));
+  b->enqueued = true;
+  b->timed = timed != 0;
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_wait(gh_ebatch* b, gh_ebatch_report* rep) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (rep) *rep = gh_ebatch_report{};
+  if (!b->planned || !b->enqueued) return fail(GH_E_STATE, "gh_ebatch_wait without an encode since the plan");
+  GH_HIP(hipSetDevice(b->device));
+  GH_HIP(hipEventSynchronize(b->done));
+  unsigned int sum[2] = {0, 0};
+  if (b->nstreams) GH_HIP(hipMemcpy(sum, b->flags.get(), sizeof(sum), hipMemcpyDeviceToHost));
+  float ms = 0;
+  if (b->timed)
+    if (int rc = b->ev.elapsed(&ms)) return rc;
+  if (rep) {
+    rep->in_bytes = b->inp.sum_n;
+    rep->out_bytes = b->out_bytes;
+    rep->nstreams = b->nstreams;
+    rep->status = sum[1];
+    rep->hist_ms = b->hist_ms;
+    rep->plan_host_ms = b->plan_host_ms;
+    rep->kernel_ms = ms;
+    rep->launches = EBATCH_LAUNCHES;
+  }
+  if (sum[0])
+    return fail(GH_E_HIP, std::to_string(sum[0]) + " stream(s) of the batch: device bit total differs from the plan's");
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_sizes(gh_ebatch* b, uint64_t* file_bytes, uint32_t cap) {
+  if (!b || (cap && !file_bytes)) return fail(GH_E_ARG, "null argument");
+  if (!b->planned) return fail(GH_E_STATE, "gh_ebatch_sizes before a plan");
+  if (cap < b->nstreams) return fail(GH_E_SMALL, "size array smaller than the batch");
+  for (uint32_t i = 0; i < b->nstreams; ++i) file_bytes[i] = b->plans[i].file_bytes;
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_download(gh_ebatch* b, uint32_t stream, void* out, uint64_t out_len) {
+  if (!b || !out) return fail(GH_E_ARG, "null argument");
+  if (!b->planned || !b->enqueued) return fail(GH_E_STATE, "gh_ebatch_download before an encode");
+  if (stream >= b->nstreams) return fail(GH_E_ARG, "no such stream in the batch");
+  const gh_encode_plan& pl = b->plans[stream];
+  if (out_len < pl.file_bytes) return fail(GH_E_SMALL, "output buffer too small");
+  GH_HIP(hipSetDevice(b->device));
+  GH_HIP(hipEventSynchronize(b->done));
+  uint8_t* o = (uint8_t*)out;
+  const size_t hdr = encode_header(&pl, o);
+  const uint64_t GW = ceil_div(pl.g, GH_GAPS_PER_WORD);
+  const EBatchOutExtent& e = b->outp.ext[stream];
+  if (GW) GH_HIP(hipMemcpy(o + hdr, b->gaps.get<uint32_t>() + e.gap_off, 4 * GW, hipMemcpyDeviceToHost));
+  if (pl.w) GH_HIP(hipMemcpy(o + hdr + 4 * GW, b->payload.get<uint32_t>() + e.pay_off, 4 * pl.w, hipMemcpyDeviceToHost));
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_items(gh_ebatch* b, gh_batch_item* items, uint32_t cap) {
+  if (!b || (cap && !items)) return fail(GH_E_ARG, "null argument");
+  if (!b->planned) return fail(GH_E_STATE, "gh_ebatch_items before a plan");
+  if (cap < b->nstreams) return fail(GH_E_SMALL, "item array smaller than the batch");
+  for (uint32_t i = 0; i < b->nstreams; ++i) {
+    const gh_encode_plan& pl = b->plans[i];
+    const EBatchOutExtent& e = b->outp.ext[i];
+    items[i] = gh_batch_item{pl.syms, pl.nsyms, pl.n, pl.w, pl.g, b->payload.get<uint32_t>() + e.pay_off,
+                             b->gaps.get<uint32_t>() + e.gap_off};
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_ebatch_kernel_shape(gh_ebatch* b, char* buf, size_t cap) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->planned) return fail(GH_E_STATE, "gh_ebatch_kernel_shape before a plan");
+  return copy_name(b->inp.nunits ? EBATCH_SHAPE : "", buf, cap);
+}
+
+extern "C" int gh_ebatch_kernel_shapes(char* buf, size_t cap) { return copy_name(std::string(EBATCH_SHAPE) + "\n", buf, cap); }

@@ -83,6 +83,36 @@ struct BatchPlan {
 // sums that overflow; the message names the stream's index.
 int batch_plan(const uint64_t* n, const uint64_t* w, const uint64_t* g, uint32_t nstreams, BatchPlan& out);
 
+// Host layout of a batched encode (gaphuff.h, "batched encode").  Host arithmetic only
+// (gh_core.cpp), shared by gh_ebatch_load / gh_ebatch_load_device / gh_ebatch_plan
+// (gh_encode.hip) and tests/sanitize/ebatch_fuzz.cpp.
+constexpr uint32_t EBATCH_UNIT_BYTES = GH_EBATCH_UNIT_BYTES;  // input bytes per work unit (one wave)
+constexpr uint32_t EBATCH_TAIL_BYTES = 32;                    // bytes a unit's last word can need past it
+constexpr uint32_t EBATCH_MAX_STREAMS = 1u << 24;
+constexpr uint64_t EBATCH_MAX_UNITS = 1ull << 31;             // work units of a batch, exclusive
+struct EBatchInExtent {
+  uint64_t in_off;    // first input byte in the input arena (a multiple of 16)
+  uint64_t in_bytes;  // bytes the stream owns there: whole units + the tail (0 when n = 0), zero past n
+  uint64_t unit0;     // first work unit; the stream has ceil(n / 1024) of them
+};
+struct EBatchInPlan {
+  std::vector<EBatchInExtent> ext;  // nstreams entries
+  uint64_t in_bytes = 0, nunits = 0, sum_n = 0;
+};
+struct EBatchOutExtent {
+  uint64_t pay_off, pay_words;  // first payload word in the payload arena (a multiple of 4); round_up(W, 4)
+  uint64_t gap_off, gap_words;  // first gap word in the gap arena (a multiple of 4); round_up(ceil(G / 8), 4)
+};
+struct EBatchOutPlan {
+  std::vector<EBatchOutExtent> ext;
+  uint64_t pay_words = 0, gap_words = 0;  // arena sizes
+};
+// GH_E_ARG beyond the limits above and on sums that overflow; the message names the stream.
+int ebatch_in_plan(const uint64_t* n, uint32_t nstreams, EBatchInPlan& out);
+// w[i] payload words and g[i] segments of stream i (G = ceil(W / 4), as every encode plan
+// gives: GH_E_ARG otherwise).
+int ebatch_out_plan(const uint64_t* w, const uint64_t* g, uint32_t nstreams, EBatchOutPlan& out);
+
 // Encoder plan from plan->n and plan->count[] (symbol order, package-merge lengths,
 // canonical codes, sizes, header version); shared by the host and GPU encoders.
 int plan_from_counts(gh_encode_plan* plan, int force_version);

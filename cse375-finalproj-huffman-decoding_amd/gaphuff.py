@@ -65,7 +65,11 @@ EXPORTED = (
     "gh_batch_create", "gh_batch_destroy", "gh_batch_layout", "gh_batch_load", "gh_batch_load_device",
     "gh_batch_decode", "gh_batch_wait", "gh_batch_status", "gh_batch_output", "gh_batch_offsets",
     "gh_batch_download", "gh_batch_kernel_shape", "gh_batch_kernel_shapes",
+    "gh_ebatch_create", "gh_ebatch_destroy", "gh_ebatch_load", "gh_ebatch_load_device", "gh_ebatch_plan",
+    "gh_ebatch_plan_of", "gh_ebatch_encode", "gh_ebatch_wait", "gh_ebatch_sizes", "gh_ebatch_download",
+    "gh_ebatch_items", "gh_ebatch_kernel_shape", "gh_ebatch_kernel_shapes",
 )
+GH_EBATCH_UNIT_BYTES = 1024
 
 
 class GapHuffError(RuntimeError):
@@ -149,6 +153,16 @@ class gh_batch_item(ctypes.Structure):
 class gh_batch_report(ctypes.Structure):
     _fields_ = [("out_bytes", ctypes.c_uint64), ("nstreams", ctypes.c_uint32), ("bad_streams", ctypes.c_uint32),
                 ("status", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
+
+
+class gh_ebatch_item(ctypes.Structure):
+    _fields_ = [("d_in", ctypes.c_void_p), ("n", ctypes.c_uint64)]
+
+
+class gh_ebatch_report(ctypes.Structure):
+    _fields_ = [("in_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("nstreams", ctypes.c_uint32),
+                ("status", ctypes.c_uint32), ("hist_ms", ctypes.c_float), ("plan_host_ms", ctypes.c_float),
+                ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
 
 
 class gh_sync_report(ctypes.Structure):
@@ -272,6 +286,19 @@ def lib() -> ctypes.CDLL:
             "gh_batch_download": ([P, U32, P, U64], I),
             "gh_batch_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_batch_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_ebatch_create": ([I, ctypes.POINTER(P)], I),
+            "gh_ebatch_destroy": ([P], I),
+            "gh_ebatch_load": ([P, P, P, U32], I),
+            "gh_ebatch_load_device": ([P, ctypes.POINTER(gh_ebatch_item), U32, P], I),
+            "gh_ebatch_plan": ([P, I, I], I),
+            "gh_ebatch_plan_of": ([P, U32, ctypes.POINTER(gh_encode_plan)], I),
+            "gh_ebatch_encode": ([P, P, I], I),
+            "gh_ebatch_wait": ([P, ctypes.POINTER(gh_ebatch_report)], I),
+            "gh_ebatch_sizes": ([P, P, U32], I),
+            "gh_ebatch_download": ([P, U32, P, U64], I),
+            "gh_ebatch_items": ([P, ctypes.POINTER(gh_batch_item), U32], I),
+            "gh_ebatch_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_ebatch_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -1012,6 +1039,124 @@ def decode_batch(images, device: int = 0) -> list:
     with BatchDecoder(device) as b:
         b.load(images)
         b.decode()
+        b.wait()
+        return b.download_all()
+
+
+# --------------------------------------------------------------------------- batched encode
+def ebatch_kernel_shapes() -> list:
+    """Every kernel name a batched encode can pick (gh_ebatch_kernel_shapes); needs no device."""
+    buf = ctypes.create_string_buffer(1 << 10)
+    _check(lib().gh_ebatch_kernel_shapes(buf, len(buf)))
+    return buf.value.decode().split()
+
+
+class BatchEncoder:
+    """One gh_ebatch: many independent inputs resident on one GPU, each encoded with its own
+    code by one fixed set of launches per batch.  load / load_device, plan, encode, wait, then
+    sizes / download / items."""
+
+    def __init__(self, device: int = 0):
+        self._h = ctypes.c_void_p()
+        _check(lib().gh_ebatch_create(device, ctypes.byref(self._h)))
+        self.device = device
+        self.ns: list = []  # input bytes of every loaded stream
+
+    def close(self) -> None:
+        if self._h:
+            lib().gh_ebatch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def load(self, datas) -> None:
+        """Load a batch of inputs (bytes / np.uint8) from host memory (gh_ebatch_load)."""
+        arrs = [_u8(d) for d in datas]
+        ptrs = (ctypes.c_void_p * max(1, len(arrs)))(*[a.ctypes.data if a.size else None for a in arrs])
+        n = np.asarray([a.size for a in arrs], dtype=np.uint64)
+        _check(lib().gh_ebatch_load(self._h, ptrs, _ptr(n) if n.size else None, len(arrs)))
+        self.ns = [a.size for a in arrs]
+
+    def load_device(self, items, hip_stream: int = 0) -> None:
+        """Load a batch whose inputs are device memory (gh_ebatch_load_device): ``items`` are
+        ``(device address, nbytes)``, any byte alignment."""
+        items = list(items)
+        arr = (gh_ebatch_item * max(1, len(items)))()
+        for i, (ptr, n) in enumerate(items):
+            arr[i].d_in, arr[i].n = ptr or None, n
+        _check(lib().gh_ebatch_load_device(self._h, arr, len(items), ctypes.c_void_p(hip_stream or None)))
+        self.ns = [int(n) for _, n in items]
+
+    def plan(self, force_version: int = 0, threads: int = 0) -> None:
+        """Every stream's histogram (one launch) and host plan (gh_ebatch_plan); synchronous."""
+        _check(lib().gh_ebatch_plan(self._h, force_version, threads))
+
+    def encode(self, hip_stream: int = 0, timed: bool = True) -> None:
+        """Enqueue one encode of the planned batch and return."""
+        _check(lib().gh_ebatch_encode(self._h, ctypes.c_void_p(hip_stream or None), int(timed)))
+
+    def wait(self) -> gh_ebatch_report:
+        """Wait for the last :meth:`encode` and return its report; raises
+        :class:`GapHuffError` (with the report as ``.report``) on a layout tripwire."""
+        r = gh_ebatch_report()
+        rc = lib().gh_ebatch_wait(self._h, ctypes.byref(r))
+        if rc != GH_OK:
+            e = GapHuffError(rc, lib().gh_last_error().decode(errors="replace"))
+            e.report = r
+            raise e
+        return r
+
+    def sizes(self) -> np.ndarray:
+        """file_bytes of every stream's image."""
+        out = np.zeros(len(self.ns), dtype=np.uint64)
+        _check(lib().gh_ebatch_sizes(self._h, _ptr(out) if out.size else None, out.size))
+        return out
+
+    def plan_of(self, i: int) -> gh_encode_plan:
+        plan = gh_encode_plan()
+        _check(lib().gh_ebatch_plan_of(self._h, i, ctypes.byref(plan)))
+        return plan
+
+    def download(self, i: int) -> np.ndarray:
+        """Stream ``i``'s whole compressed.huff image."""
+        out = np.empty(int(self.plan_of(i).file_bytes), dtype=np.uint8)
+        _check(lib().gh_ebatch_download(self._h, i, _ptr(out), out.size))
+        return out
+
+    def download_all(self) -> list:
+        return [self.download(i) for i in range(len(self.ns))]
+
+    def items(self) -> list:
+        """What :meth:`BatchDecoder.load_device` takes: ``(stream, payload_ptr, gap_ptr)`` per
+        stream, pointing into this batch's device arenas (valid until its next load or plan)."""
+        arr = (gh_batch_item * max(1, len(self.ns)))()
+        _check(lib().gh_ebatch_items(self._h, arr, len(self.ns)))
+        return [(Stream.from_plan(self.plan_of(i)), int(arr[i].d_payload or 0), int(arr[i].d_gap_words or 0))
+                for i in range(len(self.ns))]
+
+    def kernel_shape(self) -> str:
+        """Name of the per-unit kernels' shape the last plan picked (gh_ebatch_kernel_shape)."""
+        buf = ctypes.create_string_buffer(64)
+        _check(lib().gh_ebatch_kernel_shape(self._h, buf, len(buf)))
+        return buf.value.decode()
+
+
+def encode_batch(datas, device: int = 0) -> list:
+    """Encode many inputs as one batch, each with its own code; returns their images in order."""
+    with BatchEncoder(device) as b:
+        b.load(datas)
+        b.plan()
+        b.encode()
         b.wait()
         return b.download_all()
 

@@ -13,10 +13,16 @@
 // in K slices (gh_encode_sharded), slice i on the i-th of --devices (round robin; default:
 // the --gpu device); the same file, and the index then from the slices' own entries
 // (gh_encode_sharded_index: gh_ectx_index_slice per slice, no host pass over the input).
+// bin/encoder --batch LIST [--gpu D]
+// --batch LIST (a text file, one input<TAB>output per line) encodes all inputs as one batch
+// on the GPU (gh_ebatch_*: each input with its own code, a fixed set of launches however
+// many inputs) and writes every output.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "gaphuff.h"
@@ -26,7 +32,108 @@ static double now_ms() {
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+static bool read_file(const char* path, std::vector<uint8_t>& out) {
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return false;
+  std::fseek(f, 0, SEEK_END);
+  const long n = std::ftell(f);
+  std::fseek(f, 0, SEEK_SET);
+  out.resize((size_t)std::max(n, 0L));
+  const bool ok = n <= 0 || std::fread(out.data(), 1, (size_t)n, f) == (size_t)n;
+  std::fclose(f);
+  return ok;
+}
+
+// --batch LIST [--gpu D]: every line of the text file is `input<TAB>output` (as bin/decoder
+// --batch reads it); all inputs are encoded as one batch (gh_ebatch_*), each with its own
+// code, and every output file is written.
+static int batch_main(const char* list_file, int device) {
+  std::vector<uint8_t> text;
+  if (!read_file(list_file, text)) {
+    std::fprintf(stderr, "encoder: Could not open batch list %s\n", list_file);
+    return 1;
+  }
+  std::vector<std::string> in, out;
+  {
+    const std::string t(text.begin(), text.end());
+    size_t at = 0, line = 0;
+    while (at < t.size()) {
+      size_t nl = t.find('\n', at);
+      if (nl == std::string::npos) nl = t.size();
+      std::string ln = t.substr(at, nl - at);
+      at = nl + 1;
+      ++line;
+      if (!ln.empty() && ln.back() == '\r') ln.pop_back();
+      if (ln.empty()) continue;
+      const size_t tab = ln.find('\t');
+      if (tab == std::string::npos || tab == 0 || tab + 1 == ln.size()) {
+        std::fprintf(stderr, "encoder: %s: line %zu: expected input<TAB>output\n", list_file, line);
+        return 1;
+      }
+      in.push_back(ln.substr(0, tab));
+      out.push_back(ln.substr(tab + 1));
+    }
+  }
+  const size_t ns = in.size();
+  std::vector<std::vector<uint8_t>> data(ns);
+  std::vector<const uint8_t*> ptr(ns);
+  std::vector<uint64_t> n(ns);
+  for (size_t i = 0; i < ns; ++i) {
+    if (!read_file(in[i].c_str(), data[i])) {
+      std::fprintf(stderr, "encoder: %s: Could not open input file %s\n", list_file, in[i].c_str());
+      return 1;
+    }
+    ptr[i] = data[i].data();
+    n[i] = data[i].size();
+  }
+  auto die = [](const char* what, gh_ebatch* b) {
+    std::fprintf(stderr, "encoder: %s: %s\n", what, gh_last_error());
+    gh_ebatch_destroy(b);
+    return 1;
+  };
+  gh_ebatch* b = nullptr;
+  if (gh_ebatch_create(device, &b)) return die("device init", nullptr);
+  const double t0 = now_ms();
+  if (gh_ebatch_load(b, ptr.data(), n.data(), (uint32_t)ns)) return die("batch load", b);
+  const double t1 = now_ms();
+  if (gh_ebatch_plan(b, 0, 0)) return die("batch plan", b);
+  const double t2 = now_ms();
+  gh_ebatch_report rep{};
+  if (gh_ebatch_encode(b, nullptr, 1) || gh_ebatch_wait(b, &rep)) return die("batch encode", b);
+  const double t3 = now_ms();
+  std::vector<uint64_t> sizes(ns);
+  if (gh_ebatch_sizes(b, sizes.data(), (uint32_t)ns)) return die("sizes", b);
+  std::vector<uint8_t> img;
+  for (size_t i = 0; i < ns; ++i) {
+    img.resize((size_t)sizes[i]);
+    if (gh_ebatch_download(b, (uint32_t)i, img.data(), img.size())) return die("download", b);
+    FILE* f = std::fopen(out[i].c_str(), "wb");
+    bool okw = f && std::fwrite(img.data(), 1, img.size(), f) == img.size();
+    if (f) okw = std::fclose(f) == 0 && okw;
+    if (!okw) {
+      gh_ebatch_destroy(b);
+      std::fprintf(stderr, "encoder: cannot write %s\n", out[i].c_str());
+      return 1;
+    }
+  }
+  gh_ebatch_destroy(b);
+  std::printf("Batch: %u streams, %llu bytes -> %llu bytes; load %.3f ms, plan %.3f ms (histogram %.3f, host %.3f), "
+              "kernel %.3f ms, call %.3f ms\n",
+              rep.nstreams, (unsigned long long)rep.in_bytes, (unsigned long long)rep.out_bytes, t1 - t0, t2 - t1,
+              rep.hist_ms, rep.plan_host_ms, rep.kernel_ms, t3 - t2);
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 3 && !std::strcmp(argv[1], "--batch")) {
+    int device = 0;
+    if (argc == 5 && !std::strcmp(argv[3], "--gpu")) device = std::atoi(argv[4]);
+    else if (argc != 3) {
+      std::fprintf(stderr, "Usage: bin/encoder --batch LIST [--gpu D]   (LIST: one input<TAB>output per line)\n");
+      return 2;
+    }
+    return batch_main(argv[2], device);
+  }
   if (argc < 3) {
     std::printf("Usage: bin/encoder input output\n");
     return 1;

@@ -642,6 +642,83 @@ int gh_batch_download(gh_batch* b, uint32_t stream, uint8_t* dst, uint64_t nbyte
 int gh_batch_kernel_shape(gh_batch* b, char* buf, size_t cap);
 int gh_batch_kernel_shapes(char* buf, size_t cap);
 
+/* ---- batched encode: many independent inputs, a fixed launch count per batch ---------- */
+/* The other half of the batched decode: N independent inputs, each encoded with its own
+ * canonical code into its own compressed.huff image, by a number of launches that does not
+ * depend on N.  Every image is byte-identical to gh_encode_write's.  The payload and gap
+ * words stay on the device in the form gh_batch_load_device takes (gh_ebatch_items), so a
+ * batch can be encoded, decoded and checked without a payload word crossing to the host.  No
+ * reference counterpart.  A gh_ebatch is bound to one device and used from one host thread
+ * at a time.
+ *
+ * Order of calls: load (host or device memory), plan, encode, wait, then sizes / download /
+ * items.  GH_E_STATE: plan before a load; encode, plan_of, sizes or items before a plan; wait
+ * or download before an encode.  A load invalidates the plan.
+ *
+ * Layout (host arithmetic, no device).  A work unit is GH_EBATCH_UNIT_BYTES consecutive
+ * input bytes of one stream.  Input arena: stream i starts 16-byte aligned and owns
+ * ceil(n_i / unit) whole units plus 32 bytes (nothing when n_i = 0), zero past n_i, so every
+ * load of the kernels stays inside the stream's own extent.  Output: one payload arena and
+ * one gap arena; stream i's W_i words and ceil(G_i / 8) gap words each start at a 16-byte
+ * aligned offset; both arenas are zeroed at every encode.
+ * Limits (GH_E_ARG beyond them): nstreams <= 2^24; fewer than 2^31 units in a batch.  Empty
+ * inputs (n = 0) are legal: their image is the 20-byte header alone.  nstreams = 0 is GH_OK.
+ * A load replaces the previous batch; buffers are reused when large enough. */
+#define GH_EBATCH_UNIT_BYTES 1024
+typedef struct gh_ebatch gh_ebatch;
+typedef struct gh_ebatch_item {
+  const void* d_in;  /* device memory, any byte alignment: n bytes */
+  uint64_t n;
+} gh_ebatch_item;
+typedef struct gh_ebatch_report {
+  uint64_t in_bytes, out_bytes;  /* sum n_i, sum file_bytes_i                         */
+  uint32_t nstreams, status;     /* OR of the streams' GH_ST_* bits                   */
+  float hist_ms, plan_host_ms;   /* plan step: histogram kernel (events), host plans  */
+  float kernel_ms;               /* last timed encode, all its kernels (events)       */
+  uint32_t launches;             /* kernels + memsets of one encode: a constant       */
+} gh_ebatch_report;
+/* GH_E_NODEV without a usable gfx950 device, as gh_ctx_create. */
+int gh_ebatch_create(int device, gh_ebatch** out);
+int gh_ebatch_destroy(gh_ebatch* b);
+/* Load inputs from host memory: packed into one staging buffer, one upload.  Synchronous. */
+int gh_ebatch_load(gh_ebatch* b, const uint8_t* const* in, const uint64_t* n, uint32_t nstreams);
+/* Load inputs that are device memory (any address the batch's device can read, any byte
+ * alignment): a pointer table and one copy kernel on the batch's stream, after an event
+ * recorded on hip_stream (NULL: the default stream).  Exactly n_i bytes are read per stream.
+ * Synchronous; the caller's memory is not needed after the call.  Stream i of a batched
+ * decode's output arena, at out_off[i], is a valid source. */
+int gh_ebatch_load_device(gh_ebatch* b, const gh_ebatch_item* items, uint32_t nstreams, void* hip_stream);
+/* Every stream's plan (synchronous): one histogram launch, one read-back of the counts, one
+ * host plan per stream (package-merge with the reference's tie-breaking and the canonical
+ * code, on `threads` host threads; <= 0: all), one upload of the code tables and descriptors,
+ * the sizing of the output arenas.  force_version as gh_encode_plan_make; GH_E_ARG names the
+ * stream that cannot take v1. */
+int gh_ebatch_plan(gh_ebatch* b, int force_version, int threads);
+int gh_ebatch_plan_of(gh_ebatch* b, uint32_t stream, gh_encode_plan* out);
+/* Enqueue one encode of the planned batch on hip_stream (NULL = the batch's own stream) and
+ * return.  timed != 0 brackets it with HIP events. */
+int gh_ebatch_encode(gh_ebatch* b, void* hip_stream, int timed);
+/* Wait for the last encode and report it (rep may be NULL; it is filled before an error is
+ * returned).  GH_E_HIP when a stream carries GH_ST_LAYOUT: its device bit total differed
+ * from its plan's (never expected). */
+int gh_ebatch_wait(gh_ebatch* b, gh_ebatch_report* rep);
+/* file_bytes of every stream; GH_E_SMALL when cap < nstreams. */
+int gh_ebatch_sizes(gh_ebatch* b, uint64_t* file_bytes, uint32_t cap);
+/* Stream `stream`'s whole image to host memory: header from the plan, gap words, payload
+ * words, file_bytes in total.  Waits for the last encode.  GH_E_SMALL when out_len is short. */
+int gh_ebatch_download(gh_ebatch* b, uint32_t stream, void* out, uint64_t out_len);
+/* One gh_batch_item per stream, for gh_batch_load_device: syms points at the batch's own
+ * host copy of the stream's table, d_payload / d_gap_words into the arenas.  Valid until the
+ * batch's next load, plan or destroy.  GH_E_SMALL when cap < nstreams. */
+int gh_ebatch_items(gh_ebatch* b, gh_batch_item* items, uint32_t cap);
+/* The batched encode's per-unit kernels are compiled in one shape, "ebatch<lut=1>" (one copy
+ * of the stream's code table per wave).  gh_ebatch_kernel_shape: the name the last plan
+ * picked (empty for a batch without units); GH_E_STATE before a plan.
+ * gh_ebatch_kernel_shapes: every name, one per line; needs no device.  Neither is part of
+ * gh_kernel_shapes, gh_enc_kernel_shapes or gh_batch_kernel_shapes. */
+int gh_ebatch_kernel_shape(gh_ebatch* b, char* buf, size_t cap);
+int gh_ebatch_kernel_shapes(char* buf, size_t cap);
+
 /* ---- self-synchronising decode of gap-less streams ---- */
 /* Replaces CUHD's decoder for raw Huffman streams without a gap array
  * (gpuhd/src/cuhd_gpu_decoder.cu:145-523, CUHDGPUDecoder::decode declared at
