@@ -1,5 +1,7 @@
 // Batched decode (gaphuff.h, "batched decode"), included by gh_decode.hip after
 // gh_gather_plan.hip.  No reference counterpart: the reference decodes one stream per call.
+// The unit walk (stream search, cursor, a wave's run) is gh_units.hpp and the scan kernel's
+// body is block_excl_scan (gh_wave.hpp): both shared with the batched encode (gh_ebatch.hip).
 //
 // A batch is many independent streams, each with its own code, packed into one payload
 // arena and one gap arena (the host plan: gh::batch_plan, gh_core.cpp).  The unit of work
@@ -143,37 +145,20 @@ __global__ __launch_bounds__(256) void gh_batch_table_kernel(const BatchDesc* de
   }
 }
 
-// The stream of unit u: the last s with unit0[s] <= u (streams without units share their
-// unit0 with their successor and are never found).  Wave-uniform.
-__device__ __forceinline__ uint32_t batch_stream_of(const uint32_t* unit0, uint32_t nstreams, uint32_t u) {
-  uint32_t a = 0, b = nstreams;  // unit0[a] <= u; b == nstreams or unit0[b] > u
-  while (b - a > 1) {
-    const uint32_t mid = a + (b - a) / 2;
-    if (unit0[mid] <= u) a = mid; else b = mid;
-  }
-  return a;
-}
-
-// The wave's view of the unit it is working on.
+// The wave's view of the unit it is working on (c.blk: wave block of the stream).
 struct BatchUnit {
+  UnitCursor c;
   BatchDesc d;
-  uint32_t s;    // stream
-  uint32_t blk;  // wave block of the stream
 };
 
 // Points un at unit u; when the stream changes, copies its tables into the wave's LDS region.
-__device__ __forceinline__ void batch_enter(const BatchParams& bp, uint32_t u, BatchUnit& un, uint32_t& cur_end,
-                                            uint8_t* region, int lane) {
-  if (u >= cur_end || un.s == 0xFFFFFFFFu) {
-    const uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane((int)batch_stream_of(bp.unit0, bp.nstreams, u));
-    un.s = s;
-    un.d = bp.desc[s];
-    cur_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)bp.unit0[s + 1]);
+__device__ __forceinline__ void batch_enter(const BatchParams& bp, uint32_t u, BatchUnit& un, uint8_t* region, int lane) {
+  if (unit_enter(bp.unit0, bp.nstreams, u, un.c)) {
+    un.d = bp.desc[un.c.s];
     const uint4* g = (const uint4*)(bp.tables + un.d.tab_off);
     const uint32_t n16 = (FB_BYTES + max(4u << un.d.kbits, 16u)) / 16u;
     for (uint32_t i = lane; i < n16; i += 64) ((uint4*)region)[i] = g[i];
   }
-  un.blk = u - (uint32_t)__builtin_amdgcn_readfirstlane((int)bp.unit0[un.s]);
 }
 
 // Words, start bit and walk length of the lane's segment of chain c (loads clamped to the
@@ -181,7 +166,7 @@ __device__ __forceinline__ void batch_enter(const BatchParams& bp, uint32_t u, B
 // codewords start; 0 for a lane past the stream's end.
 __device__ __forceinline__ Win batch_segment(const BatchParams& bp, const BatchUnit& un, int c, int lane, int& R) {
   const BatchDesc& d = un.d;
-  const uint32_t seg = un.blk * (uint32_t)(64 * BA_U) + (uint32_t)(64 * c + lane);
+  const uint32_t seg = un.c.blk * (uint32_t)(64 * BA_U) + (uint32_t)(64 * c + lane);
   const uint32_t sc = min(seg, d.nseg - 1u);
   const uint32_t* pay = bp.payload + d.pay_off + 4ull * sc;
   const uint4 w = ws_ld16(pay);
@@ -226,13 +211,11 @@ __global__ __launch_bounds__(BA_TB) void gh_batch_count_kernel(const BatchParams
   uint8_t* region = smem + wid * BA_REGION;
   const uint32_t* s_fb = (const uint32_t*)region;
   const uint32_t* s_lut = (const uint32_t*)(region + FB_BYTES);
-  const unsigned long long nw = (unsigned long long)gridDim.x * (BA_TB / 64), gw = blockIdx.x * (BA_TB / 64) + wid;
-  const uint32_t u0 = (uint32_t)(gw * bp.nunits / nw), u1 = (uint32_t)((gw + 1) * bp.nunits / nw);
+  uint32_t u0, u1;
+  unit_run<BA_TB / 64>(bp.nunits, wid, u0, u1);
   BatchUnit un;
-  un.s = 0xFFFFFFFFu;
-  uint32_t cur_end = 0;
   for (uint32_t u = u0; u < u1; ++u) {
-    batch_enter(bp, u, un, cur_end, region, lane);
+    batch_enter(bp, u, un, region, lane);
     Win v[BA_U];
     int R[BA_U], pos[BA_U];
     uint32_t off[BA_U], cnt[BA_U], bad = 0;
@@ -265,37 +248,15 @@ __global__ __launch_bounds__(BA_TB) void gh_batch_count_kernel(const BatchParams
       tot += (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(cnt[c]), 63);
     }
     if (lane == 0) bp.unit_tot[u] = tot;
-    if (FB && __any(bad != 0) && lane == 0) atomicOr(bp.status + un.s, (unsigned)GH_ST_BADCODE);
+    if (FB && __any(bad != 0) && lane == 0) atomicOr(bp.status + un.c.s, (unsigned)GH_ST_BADCODE);
   }
 }
 
 // One workgroup: exclusive scan of the unit totals, then every stream's total and status.
 __global__ __launch_bounds__(BA_SCAN_TB) void gh_batch_scan_kernel(const BatchParams bp) {
   __shared__ unsigned long long s_w[BA_SCAN_TB / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const uint32_t per = (bp.nunits + BA_SCAN_TB - 1) / BA_SCAN_TB;
-  const uint32_t i0 = min((uint32_t)tid * per, bp.nunits), i1 = min(i0 + per, bp.nunits);
-  unsigned long long s = 0;
-  for (uint32_t i = i0; i < i1; ++i) s += bp.unit_tot[i];
-  unsigned long long incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_w[wid] = incl;
-  __syncthreads();
-  unsigned long long base = 0, all = 0;
-#pragma unroll
-  for (int q = 0; q < BA_SCAN_TB / 64; ++q) {
-    base += q < wid ? s_w[q] : 0ull;
-    all += s_w[q];
-  }
-  unsigned long long run = base + incl - s;
-  for (uint32_t i = i0; i < i1; ++i) {
-    bp.unit_off[i] = run;
-    run += bp.unit_tot[i];
-  }
+  const int tid = threadIdx.x;
+  const unsigned long long all = block_excl_scan<BA_SCAN_TB>(bp.unit_tot, bp.unit_off, bp.nunits, s_w);
   if (tid == 0) bp.unit_off[bp.nunits] = all;
   __threadfence();
   __syncthreads();
@@ -319,15 +280,13 @@ __global__ __launch_bounds__(BA_TB) void gh_batch_write_kernel(const BatchParams
   uint8_t* region = smem + wid * BA_REGION;
   const uint32_t* s_fb = (const uint32_t*)region;
   const uint32_t* s_lut = (const uint32_t*)(region + FB_BYTES);
-  const unsigned long long nw = (unsigned long long)gridDim.x * (BA_TB / 64), gw = blockIdx.x * (BA_TB / 64) + wid;
-  const uint32_t u0 = (uint32_t)(gw * bp.nunits / nw), u1 = (uint32_t)((gw + 1) * bp.nunits / nw);
+  uint32_t u0, u1;
+  unit_run<BA_TB / 64>(bp.nunits, wid, u0, u1);
   BatchUnit un;
-  un.s = 0xFFFFFFFFu;
-  uint32_t cur_end = 0;
   for (uint32_t u = u0; u < u1; ++u) {
-    batch_enter(bp, u, un, cur_end, region, lane);
+    batch_enter(bp, u, un, region, lane);
     // the unit's first symbol inside its stream: its scan value minus the stream's first unit's
-    unsigned long long at = rfl_u64(bp.unit_off[u] - bp.unit_off[u - un.blk]);
+    unsigned long long at = rfl_u64(bp.unit_off[u] - bp.unit_off[un.c.first]);
     Win v[BA_U];
     uint32_t off[BA_U], k[BA_U], kend[BA_U];
     unsigned long long dst[BA_U];

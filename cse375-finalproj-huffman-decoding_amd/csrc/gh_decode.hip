@@ -37,6 +37,7 @@
 #include "gh_hip.hpp"
 #include "gh_internal.hpp"
 #include "gh_lut.hpp"
+#include "gh_units.hpp"
 
 namespace gh {
 
@@ -686,18 +687,11 @@ extern "C" int gh_device_count(void) {
 extern "C" int gh_ctx_create(int device, gh_ctx** out) {
   if (!out) return fail(GH_E_ARG, "null ctx pointer");
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-    return fail(GH_E_NODEV, "no HIP device visible (the decoder has no CPU fallback)");
-  if (device < 0 || device >= n) return fail(GH_E_ARG, "device ordinal out of range");
-  hipDeviceProp_t prop;
-  GH_HIP(hipGetDeviceProperties(&prop, device));
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-    return fail(GH_E_NODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
+  int num_cu = 0;
+  if (int rc = open_device(device, "no HIP device visible (the decoder has no CPU fallback)", &num_cu)) return rc;
   std::unique_ptr<gh_ctx> c(new gh_ctx());  // (a failure below frees what was made)
   c->device = device;
-  c->num_cu = prop.multiProcessorCount;
-  GH_HIP(hipSetDevice(device));
+  c->num_cu = num_cu;
   if (int rc = c->stream.create()) return rc;
   if (int rc = c->done.create(hipEventDisableTiming)) return rc;
   if (int rc = c->misc.alloc(128, true)) return rc;
@@ -1564,11 +1558,6 @@ static BatchKernels batch_kernels_for(bool fb) { return fb ? batch_kernels<true>
 constexpr uint32_t BATCH_LAUNCHES = 3;  // count, scan, write
 
 struct gh_batch {
-  int device = 0, num_cu = 0;
-  Stream stream;
-  Event done;   // end of the last decode, on whatever stream it ran
-  Event ev_in;  // gh_batch_load_device: the producer stream's position
-  EventPair ev;
   DevBuf payload, gaps, tables, desc, unit0, syms, items;  // the loaded batch
   DevBuf seg_cnt, unit_tot, unit_off, symbols;             // decode scratch
   DevBuf flags;                                            // 4 summary words, then a status word per stream
@@ -1576,33 +1565,15 @@ struct gh_batch {
   BatchPlan plan;
   std::vector<uint64_t> n;
   uint32_t nstreams = 0;
-  bool loaded = false, enqueued = false, timed = false, fb = false, own_out = false;
-  ~gh_batch() {
-    (void)hipSetDevice(device);
-    if (enqueued) (void)hipEventSynchronize(done);  // (it may run on a caller's stream)
-    if (stream) (void)hipStreamSynchronize(stream);
-  }
+  bool loaded = false, fb = false, own_out = false;
+  BatchQueue q;  // (last: its destructor waits for the decode before the buffers above go)
 };
 
 extern "C" int gh_batch_create(int device, gh_batch** out) {
   if (!out) return fail(GH_E_ARG, "null batch pointer");
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-    return fail(GH_E_NODEV, "no HIP device visible (the decoder has no CPU fallback)");
-  if (device < 0 || device >= n) return fail(GH_E_ARG, "device ordinal out of range");
-  hipDeviceProp_t prop;
-  GH_HIP(hipGetDeviceProperties(&prop, device));
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-    return fail(GH_E_NODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
   std::unique_ptr<gh_batch> b(new gh_batch());
-  b->device = device;
-  b->num_cu = prop.multiProcessorCount;
-  GH_HIP(hipSetDevice(device));
-  if (int rc = b->stream.create()) return rc;
-  if (int rc = b->done.create(hipEventDisableTiming)) return rc;
-  if (int rc = b->ev_in.create(hipEventDisableTiming)) return rc;
-  if (int rc = b->ev.create()) return rc;
+  if (int rc = b->q.create(device, "no HIP device visible (the decoder has no CPU fallback)")) return rc;
   *out = b.release();
   return GH_OK;
 }
@@ -1612,21 +1583,13 @@ extern "C" int gh_batch_destroy(gh_batch* b) {
   return GH_OK;
 }
 
-// At least `bytes` (and never an empty allocation), then a copy of host memory.
-static int batch_upload(DevBuf& d, const void* src, uint64_t bytes) {
-  if (int rc = d.reserve(std::max<uint64_t>(bytes, 16))) return rc;
-  if (bytes) GH_HIP(hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
-  return GH_OK;
-}
-
 // ss[i]: stream i's header; its word pointers are host memory (any alignment), or device
 // memory when `device`.
 static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device, void* hip_stream) {
   const uint32_t ns = (uint32_t)ss.size();
-  GH_HIP(hipSetDevice(b->device));
-  if (b->enqueued) GH_HIP(hipEventSynchronize(b->done));  // the previous batch's decode reads what is replaced
-  GH_HIP(hipStreamSynchronize(b->stream));
-  b->loaded = b->enqueued = b->own_out = false;
+  GH_HIP(hipSetDevice(b->q.device));
+  if (int rc = b->q.quiesce()) return rc;  // the previous batch's decode reads what is replaced
+  b->loaded = b->own_out = false;
   std::vector<uint64_t> n(ns), w(ns), g(ns);
   std::vector<BatchDesc> desc(ns);
   std::vector<gh_sym> syms;
@@ -1672,9 +1635,9 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
     unit0[i] = (uint32_t)e.unit0;
   }
   unit0[ns] = (uint32_t)plan.nunits;
-  if (int rc = batch_upload(b->desc, desc.data(), sizeof(BatchDesc) * (uint64_t)ns)) return rc;
-  if (int rc = batch_upload(b->unit0, unit0.data(), 4ull * (ns + 1))) return rc;
-  if (int rc = batch_upload(b->syms, syms.data(), sizeof(gh_sym) * (uint64_t)syms.size())) return rc;
+  if (int rc = upload_at_least(b->desc, desc.data(), sizeof(BatchDesc) * (uint64_t)ns)) return rc;
+  if (int rc = upload_at_least(b->unit0, unit0.data(), 4ull * (ns + 1))) return rc;
+  if (int rc = upload_at_least(b->syms, syms.data(), sizeof(gh_sym) * (uint64_t)syms.size())) return rc;
   if (int rc = b->tables.reserve(std::max<uint64_t>(4 * tab_words, 16))) return rc;
   if (int rc = b->payload.reserve(std::max<uint64_t>(4 * plan.pay_words, 16))) return rc;
   if (int rc = b->gaps.reserve(std::max<uint64_t>(4 * plan.gap_words, 16))) return rc;
@@ -1690,13 +1653,7 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
       if (w[i]) std::memcpy(pay.data() + plan.ext[i].pay_off, ss[i].payload, 4 * w[i]);
       if (g[i]) std::memcpy(gap.data() + plan.ext[i].gap_off, ss[i].gap_words, 4 * plan.ext[i].gap_words);
     }
-    if (!pay.empty()) {
-      if (use_staged(4 * pay.size())) {
-        if (int rc = h2d_staged(b->device, pay.data(), 4 * pay.size(), b->payload.get())) return rc;
-      } else {
-        GH_HIP(hipMemcpy(b->payload.get(), pay.data(), 4 * pay.size(), hipMemcpyHostToDevice));
-      }
-    }
+    if (int rc = upload_arena(b->q.device, b->payload, pay.data(), 4 * pay.size())) return rc;
     if (!gap.empty()) GH_HIP(hipMemcpy(b->gaps.get(), gap.data(), 4 * gap.size(), hipMemcpyHostToDevice));
   } else {
     std::vector<BatchCopyItem> items(ns);
@@ -1704,22 +1661,21 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
       const BatchExtent& e = plan.ext[i];
       items[i] = BatchCopyItem{ss[i].payload, ss[i].gap_words, w[i], e.pay_off, e.pay_words, e.gap_off, e.gap_words};
     }
-    if (int rc = batch_upload(b->items, items.data(), sizeof(BatchCopyItem) * (uint64_t)ns)) return rc;
+    if (int rc = upload_at_least(b->items, items.data(), sizeof(BatchCopyItem) * (uint64_t)ns)) return rc;
     // after what the producer's stream holds now, then one copy kernel on the batch's stream
-    GH_HIP(hipEventRecord(b->ev_in, (hipStream_t)hip_stream));
-    GH_HIP(hipStreamWaitEvent(b->stream, b->ev_in, 0));
+    if (int rc = b->q.follow(hip_stream)) return rc;
     if (plan.pay_words) {
-      hipLaunchKernelGGL(gh_batch_copy_kernel, dim3(std::min<uint32_t>(ns, 4096u), BA_COPY_Y), dim3(256), 0, b->stream,
+      hipLaunchKernelGGL(gh_batch_copy_kernel, dim3(std::min<uint32_t>(ns, 4096u), BA_COPY_Y), dim3(256), 0, b->q.stream,
                          b->items.get<BatchCopyItem>(), ns, b->payload.get<uint32_t>(), b->gaps.get<uint32_t>());
       GH_HIP(hipGetLastError());
     }
   }
   if (tab_words) {  // every stream's tables: one launch
-    hipLaunchKernelGGL(gh_batch_table_kernel, dim3(std::min<uint32_t>(ns, 16u * (uint32_t)b->num_cu)), dim3(256), 0,
-                       b->stream, b->desc.get<BatchDesc>(), b->syms.get<gh_sym>(), b->tables.get<uint32_t>(), ns);
+    hipLaunchKernelGGL(gh_batch_table_kernel, dim3(std::min<uint32_t>(ns, 16u * (uint32_t)b->q.num_cu)), dim3(256), 0,
+                       b->q.stream, b->desc.get<BatchDesc>(), b->syms.get<gh_sym>(), b->tables.get<uint32_t>(), ns);
     GH_HIP(hipGetLastError());
   }
-  GH_HIP(hipStreamSynchronize(b->stream));
+  GH_HIP(hipStreamSynchronize(b->q.stream));
   b->plan = std::move(plan);
   b->n = std::move(n);
   b->nstreams = ns;
@@ -1745,18 +1701,10 @@ extern "C" int gh_batch_load_device(gh_batch* b, const gh_batch_item* items, uin
   return batch_load(b, ss, true, hip_stream);
 }
 
-// GH_BATCH_GRID=k (tests): k workgroups for the count and write kernels, so that one wave
-// walks many units and streams.  Read at each decode.
-static uint32_t batch_grid(const gh_batch* b) {
-  if (const char* eg = getenv("GH_BATCH_GRID")) return (uint32_t)std::clamp<long>(atol(eg), 1, 1l << 20);
-  const uint64_t want = ceil_div(b->plan.nunits, BA_TB / 64);
-  return (uint32_t)std::clamp<uint64_t>(want, 1, 8ull * (uint64_t)b->num_cu);
-}
-
 extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void* hip_stream, int timed) {
   if (!b) return fail(GH_E_ARG, "null batch");
   if (!b->loaded) return fail(GH_E_STATE, "gh_batch_decode before a load");
-  GH_HIP(hipSetDevice(b->device));
+  GH_HIP(hipSetDevice(b->q.device));
   const bool own = d_dst == nullptr;
   if (own) {
     if (int rc = b->out.reserve(std::max<uint64_t>(b->plan.out_bytes, 16))) return rc;
@@ -1765,9 +1713,6 @@ extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void*
     if ((uintptr_t)d_dst & 15u) return fail(GH_E_ARG, "destination not 16-byte aligned");
     if (dst_len < b->plan.out_bytes) return fail(GH_E_SMALL, "destination smaller than the batch's arena");
   }
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)b->stream;
-  // decodes of one batch share its scratch: they run in the order they were made
-  if (b->enqueued) GH_HIP(hipStreamWaitEvent(st, b->done, 0));
   BatchParams bp{};
   bp.desc = b->desc.get<BatchDesc>();
   bp.unit0 = b->unit0.get<uint32_t>();
@@ -1783,20 +1728,21 @@ extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void*
   bp.out = (uint8_t*)d_dst;
   bp.nstreams = b->nstreams;
   bp.nunits = (uint32_t)b->plan.nunits;
-  if (timed) GH_HIP(hipEventRecord(b->ev.a, st));
+  // decodes of one batch share its scratch: they run in the order they were made
+  hipStream_t st;
+  if (int rc = b->q.begin(hip_stream, timed != 0, &st)) return rc;
+  // (the count kernel ORs status words before the scan kernel sees them)
   GH_HIP(hipMemsetAsync(b->flags.get(), 0, 16 + 4ull * b->nstreams, st));
   if (b->nstreams) {
     const BatchKernels k = batch_kernels_for(b->fb);
-    const uint32_t grid = batch_grid(b);
+    // GH_BATCH_GRID=k (tests): k workgroups for the count and write kernels
+    const uint32_t grid = unit_grid("GH_BATCH_GRID", b->plan.nunits, BA_TB / 64, b->q.num_cu);
     void* args[] = {&bp};
     if (bp.nunits) GH_HIP(hipLaunchKernel(k.count, dim3(grid), dim3(BA_TB), args, 0, st));
     GH_HIP(hipLaunchKernel((const void*)gh_batch_scan_kernel, dim3(1), dim3(BA_SCAN_TB), args, 0, st));
     if (bp.nunits) GH_HIP(hipLaunchKernel(k.write, dim3(grid), dim3(BA_TB), args, 0, st));
   }
-  if (timed) GH_HIP(hipEventRecord(b->ev.b, st));
-  GH_HIP(hipEventRecord(b->done, st));
-  b->enqueued = true;
-  b->timed = timed != 0;
+  if (int rc = b->q.end(st)) return rc;
   b->own_out = own;
   return GH_OK;
 }
@@ -1804,14 +1750,12 @@ extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void*
 extern "C" int gh_batch_wait(gh_batch* b, gh_batch_report* rep) {
   if (!b) return fail(GH_E_ARG, "null batch");
   if (rep) *rep = gh_batch_report{};
-  if (!b->loaded || !b->enqueued) return fail(GH_E_STATE, "gh_batch_wait without a decode since the load");
-  GH_HIP(hipSetDevice(b->device));
-  GH_HIP(hipEventSynchronize(b->done));
+  if (!b->loaded || !b->q.enqueued) return fail(GH_E_STATE, "gh_batch_wait without a decode since the load");
+  GH_HIP(hipSetDevice(b->q.device));
+  float ms = 0;
+  if (int rc = b->q.wait(&ms)) return rc;
   unsigned int sum[2] = {0, 0};
   GH_HIP(hipMemcpy(sum, b->flags.get(), sizeof(sum), hipMemcpyDeviceToHost));
-  float ms = 0;
-  if (b->timed)
-    if (int rc = b->ev.elapsed(&ms)) return rc;
   if (rep) {
     for (uint64_t v : b->n) rep->out_bytes += v;
     rep->nstreams = b->nstreams;
@@ -1828,10 +1772,10 @@ extern "C" int gh_batch_wait(gh_batch* b, gh_batch_report* rep) {
 
 extern "C" int gh_batch_status(gh_batch* b, uint32_t* status, uint64_t* symbols, uint32_t cap) {
   if (!b) return fail(GH_E_ARG, "null batch");
-  if (!b->loaded || !b->enqueued) return fail(GH_E_STATE, "gh_batch_status without a decode since the load");
+  if (!b->loaded || !b->q.enqueued) return fail(GH_E_STATE, "gh_batch_status without a decode since the load");
   if (cap < b->nstreams) return fail(GH_E_SMALL, "status arrays smaller than the batch");
-  GH_HIP(hipSetDevice(b->device));
-  GH_HIP(hipEventSynchronize(b->done));
+  GH_HIP(hipSetDevice(b->q.device));
+  GH_HIP(hipEventSynchronize(b->q.done));
   if (status && b->nstreams)
     GH_HIP(hipMemcpy(status, b->flags.get<unsigned int>() + 4, 4ull * b->nstreams, hipMemcpyDeviceToHost));
   if (symbols && b->nstreams) GH_HIP(hipMemcpy(symbols, b->symbols.get(), 8ull * b->nstreams, hipMemcpyDeviceToHost));
@@ -1856,12 +1800,12 @@ extern "C" int gh_batch_offsets(gh_batch* b, uint64_t* out_off, uint32_t cap) {
 
 extern "C" int gh_batch_download(gh_batch* b, uint32_t stream, uint8_t* dst, uint64_t nbytes) {
   if (!b || (nbytes && !dst)) return fail(GH_E_ARG, "null argument");
-  if (!b->loaded || !b->enqueued || !b->own_out)
+  if (!b->loaded || !b->q.enqueued || !b->own_out)
     return fail(GH_E_STATE, "gh_batch_download without a decode into the batch's own arena");
   if (stream >= b->nstreams) return fail(GH_E_ARG, "no such stream in the batch");
   if (nbytes > b->n[stream]) return fail(GH_E_ARG, "more bytes than the stream holds");
-  GH_HIP(hipSetDevice(b->device));
-  GH_HIP(hipEventSynchronize(b->done));
+  GH_HIP(hipSetDevice(b->q.device));
+  GH_HIP(hipEventSynchronize(b->q.done));
   if (nbytes)
     GH_HIP(hipMemcpy(dst, b->out.get<uint8_t>() + b->plan.ext[stream].out_off, nbytes, hipMemcpyDeviceToHost));
   return GH_OK;

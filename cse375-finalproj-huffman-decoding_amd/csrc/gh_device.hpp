@@ -1,12 +1,15 @@
-// Device helpers shared by the tile kernel (gh_tile.hip) and the wave split
-// (gh_wsplit.hip): the segment window, gap nibbles, DPP wave scans, look-back granules
-// and LDS accesses at absolute addresses.  Included by gh_decode.hip only.
+// Device helpers of the decode kernels (gh_tile.hip, gh_wsplit.hip and the other files
+// gh_decode.hip includes): the segment window, gap nibbles, look-back granules and LDS
+// accesses at absolute addresses.  Included by gh_decode.hip only; the wave primitives that
+// need none of the decoder's types (wave scans, rfl_u64, the one-workgroup scan) are in
+// gh_wave.hpp, which the encoder includes too.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "gh_lut.hpp"
+#include "gh_wave.hpp"
 
 namespace gh {
 
@@ -60,34 +63,6 @@ __device__ __forceinline__ void win_shift(Win& v, uint32_t q) {
 // Gap nibble `nib` of a gap word (8 nibbles per word, low nibble first:
 // decoder.cu:501-507).
 __device__ __forceinline__ uint32_t gap_nib(uint32_t word, uint32_t nib) { return (word >> (4u * (nib & 7u))) & 15u; }
-
-// Inclusive wave scan on the VALU with DPP: row_shr 1/2/4/8 scans each 16-lane row,
-// row_bcast 15/31 carry the row totals forward (no LDS traffic, unlike
-// ds_bpermute-based shuffles).
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// Wave-uniform copy of a 64-bit value (lane 0's).  readfirstlane returns int: each half
-// is taken as uint32_t before widening (an int low half with bit 31 set would
-// sign-extend over the high half).
-__device__ __forceinline__ unsigned long long rfl_u64(unsigned long long v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 // Look-back granule: [37:0] value, [39:38] flag (1 aggregate, 2 prefix), [63:40] epoch
 // of the launch that wrote it (the data is the flag: no memset between launches).

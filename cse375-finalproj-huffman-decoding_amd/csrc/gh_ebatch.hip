@@ -1,8 +1,9 @@
 // Batched encode (gaphuff.h, "batched encode"), included by gh_encode.hip after its device
-// helpers (enc_byte, enc_pair, enc_wave_scan and the left-aligned entry
-// code << (32 - len) | len are shared, not copied).  No reference counterpart: the
-// reference encodes one input per call.  The structure is the batched decoder's
-// (gh_batch.hip), mirrored.
+// helpers (enc_byte, enc_pair and the left-aligned entry code << (32 - len) | len are
+// shared, not copied).  No reference counterpart: the reference encodes one input per call.
+// The structure is the batched decoder's (gh_batch.hip), and what the two have in common is
+// shared: the unit walk (stream search, cursor, a wave's run) is gh_units.hpp, the wave scan,
+// rfl_u64 and the scan kernel's body (block_excl_scan) are gh_wave.hpp.
 //
 // A batch is many independent inputs, each with its own canonical code, packed into one
 // padded input arena; the images' payload and gap words go to one payload arena and one gap
@@ -124,39 +125,17 @@ __global__ __launch_bounds__(256) void gh_ebatch_copy_kernel(const EBatchCopyIte
   }
 }
 
-// The stream of unit u: the last s with unit0[s] <= u (streams without units share their
-// unit0 with their successor and are never found).  Wave-uniform; at most 25 steps.
-__device__ __forceinline__ uint32_t ebatch_stream_of(const uint32_t* unit0, uint32_t nstreams, uint32_t u) {
-  uint32_t a = 0, b = nstreams;  // unit0[a] <= u; b == nstreams or unit0[b] > u
-  while (b - a > 1) {
-    const uint32_t mid = a + (b - a) / 2;
-    if (unit0[mid] <= u) a = mid; else b = mid;
-  }
-  return a;
-}
-
 // The wave's view of the unit it is working on.
 struct EBatchUnit {
+  UnitCursor c;
   EBatchDesc d;
-  uint32_t s;      // stream (0xFFFFFFFF: none yet)
-  uint32_t first;  // the stream's first unit
-  uint32_t end;    // the stream's last unit + 1
-  uint32_t blk;    // unit of the stream
 };
 
 // Points un at unit u; returns true when the stream changed.
 __device__ __forceinline__ bool ebatch_enter(const EBatchParams& p, uint32_t u, EBatchUnit& un) {
-  bool changed = false;
-  if (un.s == 0xFFFFFFFFu || u >= un.end) {
-    const uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane((int)ebatch_stream_of(p.unit0, p.nstreams, u));
-    un.s = s;
-    un.d = p.desc[s];
-    un.first = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.unit0[s]);
-    un.end = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.unit0[s + 1]);
-    changed = true;
-  }
-  un.blk = u - un.first;
-  return changed;
+  if (!unit_enter(p.unit0, p.nstreams, u, un.c)) return false;
+  un.d = p.desc[un.c.s];
+  return true;
 }
 
 // The stream's table into the wave's LDS region: one 16-byte load and store per lane, and
@@ -171,7 +150,7 @@ __device__ __forceinline__ void ebatch_load_table(const EBatchParams& p, uint32_
 // The lane's 16 bytes of the unit (absent past n: 0x100).  The load is unconditional: the
 // arena pads every stream to whole units.
 __device__ __forceinline__ void ebatch_bytes(const EBatchParams& p, const EBatchUnit& un, int lane, uint32_t (&b)[EBPT]) {
-  const unsigned long long ib = (unsigned long long)un.blk * EB_UNIT + (uint32_t)lane * EBPT;
+  const unsigned long long ib = (unsigned long long)un.c.blk * EB_UNIT + (uint32_t)lane * EBPT;
   const uint4 v = *(const uint4*)(p.in + un.d.in_off + ib);
   if (ib + EBPT <= un.d.n) {
 #pragma unroll
@@ -181,13 +160,6 @@ __device__ __forceinline__ void ebatch_bytes(const EBatchParams& p, const EBatch
 #pragma unroll
     for (int k = 0; k < EBPT; ++k) b[k] = (uint32_t)k < rem ? enc_byte(v, k) : 0x100u;
   }
-}
-
-// This wave's run of units.
-__device__ __forceinline__ void ebatch_run(uint32_t nunits, uint32_t wid, uint32_t& u0, uint32_t& u1) {
-  const unsigned long long nw = (unsigned long long)gridDim.x * EB_WAVES, gw = (unsigned long long)blockIdx.x * EB_WAVES + wid;
-  u0 = (uint32_t)(gw * nunits / nw);
-  u1 = (uint32_t)((gw + 1) * nunits / nw);
 }
 
 __global__ __launch_bounds__(EB_TB) void gh_ebatch_hist_kernel(const EBatchParams p) {
@@ -210,16 +182,14 @@ __global__ __launch_bounds__(EB_TB) void gh_ebatch_hist_kernel(const EBatchParam
     ebatch_wave_sync();
   };
   uint32_t u0, u1;
-  ebatch_run(p.nunits, wid, u0, u1);
+  unit_run<EB_WAVES>(p.nunits, wid, u0, u1);
   EBatchUnit un;
-  un.s = 0xFFFFFFFFu;
-  un.end = 0;
   uint32_t since = 0;  // units counted since the last flush
   for (uint32_t u = u0; u < u1; ++u) {
-    const uint32_t prev = un.s;
+    const uint32_t prev = un.c.s;
     const bool changed = ebatch_enter(p, u, un);
     if ((changed && prev != 0xFFFFFFFFu) || since == EB_FLUSH_UNITS) {
-      flush(changed ? prev : un.s);
+      flush(changed ? prev : un.c.s);
       since = 0;
     }
     uint32_t b[EBPT];
@@ -229,7 +199,7 @@ __global__ __launch_bounds__(EB_TB) void gh_ebatch_hist_kernel(const EBatchParam
       if (b[k] < 256u) atomicAdd(&h[b[k]], 1u);
     ++since;
   }
-  if (un.s != 0xFFFFFFFFu) flush(un.s);
+  if (un.c.s != 0xFFFFFFFFu) flush(un.c.s);
 }
 
 __global__ __launch_bounds__(EB_TB) void gh_ebatch_bits_kernel(const EBatchParams p) {
@@ -238,18 +208,16 @@ __global__ __launch_bounds__(EB_TB) void gh_ebatch_bits_kernel(const EBatchParam
   const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint32_t* s_lut = s_tab[wid];
   uint32_t u0, u1;
-  ebatch_run(p.nunits, wid, u0, u1);
+  unit_run<EB_WAVES>(p.nunits, wid, u0, u1);
   EBatchUnit un;
-  un.s = 0xFFFFFFFFu;
-  un.end = 0;
   for (uint32_t u = u0; u < u1; ++u) {
-    if (ebatch_enter(p, u, un)) ebatch_load_table(p, un.s, s_lut, lane);
+    if (ebatch_enter(p, u, un)) ebatch_load_table(p, un.c.s, s_lut, lane);
     uint32_t b[EBPT], bits = 0;
     ebatch_bytes(p, un, lane, b);
 #pragma unroll
     for (int k = 0; k < EBPT; ++k) bits += s_lut[b[k]];  // (the entries' low 16 bits hold only their lengths)
     bits &= 0xFFFFu;
-    const uint32_t incl = enc_wave_scan(bits);
+    const uint32_t incl = wave_incl_scan(bits);
     if (lane == 63) p.unit_bits[u] = incl;
   }
 }
@@ -258,31 +226,9 @@ __global__ __launch_bounds__(EB_TB) void gh_ebatch_bits_kernel(const EBatchParam
 __global__ __launch_bounds__(EB_SCAN_TB) void gh_ebatch_scan_kernel(const EBatchParams p) {
   __shared__ unsigned long long s_w[EB_SCAN_TB / 64];
   __shared__ unsigned int s_sum[2];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (tid < 2) s_sum[tid] = 0;
-  const uint32_t per = (p.nunits + EB_SCAN_TB - 1) / EB_SCAN_TB;
-  const uint32_t i0 = min((uint32_t)tid * per, p.nunits), i1 = min(i0 + per, p.nunits);
-  unsigned long long s = 0;
-  for (uint32_t i = i0; i < i1; ++i) s += p.unit_bits[i];
-  unsigned long long incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_w[wid] = incl;
-  __syncthreads();
-  unsigned long long base = 0, all = 0;
-#pragma unroll
-  for (int q = 0; q < EB_SCAN_TB / 64; ++q) {
-    base += q < wid ? s_w[q] : 0ull;
-    all += s_w[q];
-  }
-  unsigned long long run = base + incl - s;
-  for (uint32_t i = i0; i < i1; ++i) {
-    p.unit_off[i] = run;
-    run += p.unit_bits[i];
-  }
+  const int tid = threadIdx.x;
+  if (tid < 2) s_sum[tid] = 0;  // (ordered before the epilogue's atomics by the scan's barrier)
+  const unsigned long long all = block_excl_scan<EB_SCAN_TB>(p.unit_bits, p.unit_off, p.nunits, s_w);
   if (tid == 0) p.unit_off[p.nunits] = all;
   __threadfence();
   __syncthreads();
@@ -311,26 +257,22 @@ __global__ __launch_bounds__(EB_TB) void gh_ebatch_write_kernel(const EBatchPara
   for (uint32_t i = lane; i < EB_WORDS; i += 64) s_w[i] = 0;
   if ((uint32_t)lane < EB_GAPW) s_g[lane] = 0;
   uint32_t u0, u1;
-  ebatch_run(p.nunits, wid, u0, u1);
+  unit_run<EB_WAVES>(p.nunits, wid, u0, u1);
   EBatchUnit un;
-  un.s = 0xFFFFFFFFu;
-  un.end = 0;
   unsigned long long off_first = 0;  // the scan value of the stream's first unit
   for (uint32_t u = u0; u < u1; ++u) {
     if (ebatch_enter(p, u, un)) {
-      ebatch_load_table(p, un.s, s_lut, lane);
-      off_first = p.unit_off[un.first];
+      ebatch_load_table(p, un.c.s, s_lut, lane);
+      off_first = p.unit_off[un.c.first];
     }
     ebatch_wave_sync();  // the previous unit's write-out and re-zeroing come before this unit's ORs
     // the unit's first bit inside its stream
-    const unsigned long long o0u = p.unit_off[u] - off_first;
-    const unsigned long long o0 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(o0u >> 32)) << 32) |
-                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)o0u);
+    const unsigned long long o0 = rfl_u64(p.unit_off[u] - off_first);
     uint32_t b[EBPT];
     ebatch_bytes(p, un, lane, b);
     // the next unit's byte `lane` (lanes 0..31), for the last word: inside the stream's own
     // padded extent, and masked by the stream's own n
-    const unsigned long long xb = (unsigned long long)(un.blk + 1u) * EB_UNIT;
+    const unsigned long long xb = (unsigned long long)(un.c.blk + 1u) * EB_UNIT;
     const uint32_t nx = p.in[un.d.in_off + xb + (uint32_t)(lane & 31)];
     uint32_t e[EBPT], bits = 0;
 #pragma unroll
@@ -338,7 +280,7 @@ __global__ __launch_bounds__(EB_TB) void gh_ebatch_write_kernel(const EBatchPara
 #pragma unroll
     for (int k = 0; k < EBPT; ++k) bits += e[k];  // (the entries' low 16 bits hold only their lengths)
     bits &= 0xFFFFu;
-    const uint32_t incl = enc_wave_scan(bits);
+    const uint32_t incl = wave_incl_scan(bits);
     const uint32_t cbits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     // never expected (the scan kernel flags the stream): a unit that would end past its
     // stream's planned bits stores nothing, so no store leaves the stream's extents
@@ -395,7 +337,7 @@ __global__ __launch_bounds__(EB_TB) void gh_ebatch_write_kernel(const EBatchPara
       const uint32_t wend = (qend + 31u) & ~31u;
       const uint32_t ex = (lane < 32 && xb + (uint32_t)lane < un.d.n) ? s_lut[nx] : 0u;
       const uint32_t lx = ex & 31u;
-      const uint32_t st = qend + enc_wave_scan(lx) - lx;  // this codeword's first bit
+      const uint32_t st = qend + wave_incl_scan(lx) - lx;  // this codeword's first bit
       if (lx && st < wend) {
         const uint32_t cw = ex & 0xFFFF0000u, sh = st & 31u;  // left-aligned code
         atomicOr(&s_w[st >> 5], cw >> sh);

@@ -58,6 +58,8 @@
 #include "gaphuff.h"
 #include "gh_hip.hpp"
 #include "gh_internal.hpp"
+#include "gh_units.hpp"
+#include "gh_wave.hpp"
 
 namespace gh {
 
@@ -114,18 +116,6 @@ __global__ __launch_bounds__(ETB) void gh_enc_hist_kernel(const uint8_t* in, uin
     for (int r = 0; r < EREP; ++r) s += h[v * EREP + ((r + v) & (EREP - 1))];
     if (s) atomicAdd(&count[v], s);
   }
-}
-
-// Inclusive wave scan on the VALU with DPP (row_shr 1/2/4/8 within 16-lane rows,
-// row_bcast 15/31 across them): no LDS round trips, unlike ds_bpermute shuffles.
-__device__ __forceinline__ uint32_t enc_wave_scan(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-  return v;
 }
 
 // Workgroup exclusive scan of one u32 per thread; returns the exclusive prefix and
@@ -218,7 +208,7 @@ __global__ __launch_bounds__(ETB) void gh_enc_bits_kernel(const uint8_t* in, uin
     for (int j = 0; j < EBQ; ++j) v[j] = ld(c + (uint32_t)(EBQ + j) * G);
 #pragma unroll
     for (int j = 0; j < EBQ; ++j) {
-      const uint32_t sc = enc_wave_scan(b[j]);  // lane 63: the wave total
+      const uint32_t sc = wave_incl_scan(b[j]);  // lane 63: the wave total
       if (lane == 63) s_red[it & 1][j][wid] = sc;
     }
     __syncthreads();  // (double-buffered partial sums: one barrier per group)
@@ -420,7 +410,7 @@ __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW
     }
     // block scan (double-buffered wave sums: the barrier also orders the previous
     // iteration's write-out and re-zeroing before this iteration's OR-s)
-    const uint32_t incl = enc_wave_scan(bits);
+    const uint32_t incl = wave_incl_scan(bits);
     if (lane == 63) s_red[it & 1][wid] = incl;
     __syncthreads();
     uint32_t before = 0, cbits = 0;
@@ -487,7 +477,7 @@ __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW
       const uint32_t wend = (qend + 31u) & ~31u;
       const uint32_t ex = (lane < 32 && xb + (uint32_t)lane < p.n) ? s_lutr[nx * ELREP + (tid & (ELREP - 1))] : 0u;
       const uint32_t lx = ex & 31u;
-      const uint32_t st = qend + enc_wave_scan(lx) - lx;  // this codeword's first bit
+      const uint32_t st = qend + wave_incl_scan(lx) - lx;  // this codeword's first bit
       if (lx && st < wend) {
         const uint32_t cw = ex & 0xFFFF0000u, sh = st & 31u;  // left-aligned code
         atomicOr(&s_w[st >> 5], cw >> sh);
@@ -503,8 +493,7 @@ __global__ __launch_bounds__(ETB) __attribute__((amdgpu_waves_per_eu(enc_wpe<NSW
     uint32_t* junk = p.junk + (size_t)blockIdx.x * ETB + tid;
     // (GH_ENC_OOB) buffer stores from the chunk's base (B is workgroup-uniform), the
     // padding ones out of range: dropped, no memory traffic
-    const unsigned long long Bu = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(B >> 32)) << 32) |
-                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)B);
+    const unsigned long long Bu = rfl_u64(B);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(p.words + ((Bu - org) >> 5), 0, 0x7FFFFFF0, 0x00020000);
 #pragma unroll
     for (int j = 0; j < NSW; ++j) {
@@ -612,7 +601,7 @@ __global__ __launch_bounds__(ETB) void gh_enc_index_kernel(
     }
 #pragma unroll
     for (int k = 0; k < EBPT; ++k) bits += l[k];
-    const uint32_t incl = enc_wave_scan(bits);
+    const uint32_t incl = wave_incl_scan(bits);
     if (lane == 63) s_red[it & 1][wid] = incl;
     __syncthreads();  // (one barrier per scanned chunk: the other buffer is the previous chunk's)
     uint32_t before = 0;
@@ -723,18 +712,11 @@ struct gh_ectx {
 extern "C" int gh_ectx_create(int device, gh_ectx** out) {
   if (!out) return fail(GH_E_ARG, "null ctx pointer");
   *out = nullptr;
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0)
-    return fail(GH_E_NODEV, "no HIP device visible (the GPU encoder has no CPU fallback)");
-  if (device < 0 || device >= nd) return fail(GH_E_ARG, "device ordinal out of range");
-  hipDeviceProp_t prop;
-  GH_HIP(hipGetDeviceProperties(&prop, device));
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-    return fail(GH_E_NODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
-  GH_HIP(hipSetDevice(device));
+  int num_cu = 0;
+  if (int rc = open_device(device, "no HIP device visible (the GPU encoder has no CPU fallback)", &num_cu)) return rc;
   std::unique_ptr<gh_ectx> e(new gh_ectx());  // (a failure below frees what was made)
   e->device = device;
-  e->num_cu = prop.multiProcessorCount;
+  e->num_cu = num_cu;
   if (int rc = e->stream.create()) return rc;
   if (int rc = e->d_count.alloc(256 * 8)) return rc;
   if (int rc = e->d_lut.alloc(256 * 4)) return rc;
@@ -768,9 +750,7 @@ extern "C" int gh_ectx_load_device(gh_ectx* e, const void* d_in, uint64_t n, voi
   if (int rc = e->d_in.reserve(n + ECHUNK + 64)) return rc;
   if (n) {
     // after what the producer's stream holds now, then device to device on the context's stream
-    if (int rc = e->ev_in.create(hipEventDisableTiming)) return rc;
-    GH_HIP(hipEventRecord(e->ev_in, (hipStream_t)hip_stream));
-    GH_HIP(hipStreamWaitEvent(e->stream, e->ev_in, 0));
+    if (int rc = stream_follow(e->ev_in, hip_stream, e->stream)) return rc;
     GH_HIP(hipMemcpyAsync(e->d_in.get(), d_in, n, hipMemcpyDefault, e->stream));
   }
   GH_HIP(hipStreamSynchronize(e->stream));
@@ -1283,11 +1263,7 @@ constexpr uint32_t EBATCH_LAUNCHES = 5;  // two arena memsets, then bits, scan, 
 static const char* const EBATCH_SHAPE = "ebatch<lut=1>";
 
 struct gh_ebatch {
-  int device = 0, num_cu = 0;
-  Stream stream;
-  Event done;   // end of the last encode, on whatever stream it ran
-  Event ev_in;  // gh_ebatch_load_device: the producer stream's position
-  EventPair ev, ev_hist;
+  EventPair ev_hist;
   DevBuf in, unit0, items;                 // the loaded batch
   DevBuf code;                             // one EBatchDesc per stream, then 256 table entries per stream
   DevBuf counts;                           // 256 u64 per stream
@@ -1300,33 +1276,15 @@ struct gh_ebatch {
   uint32_t nstreams = 0;
   uint64_t out_bytes = 0;
   float hist_ms = 0, plan_host_ms = 0;
-  bool loaded = false, planned = false, enqueued = false, timed = false;
-  ~gh_ebatch() {
-    (void)hipSetDevice(device);
-    if (enqueued) (void)hipEventSynchronize(done);  // (it may run on a caller's stream)
-    if (stream) (void)hipStreamSynchronize(stream);
-  }
+  bool loaded = false, planned = false;
+  BatchQueue q;  // (last: its destructor waits for the encode before the buffers above go)
 };
 
 extern "C" int gh_ebatch_create(int device, gh_ebatch** out) {
   if (!out) return fail(GH_E_ARG, "null batch pointer");
   *out = nullptr;
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0)
-    return fail(GH_E_NODEV, "no HIP device visible (the GPU encoder has no CPU fallback)");
-  if (device < 0 || device >= nd) return fail(GH_E_ARG, "device ordinal out of range");
-  hipDeviceProp_t prop;
-  GH_HIP(hipGetDeviceProperties(&prop, device));
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-    return fail(GH_E_NODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
   std::unique_ptr<gh_ebatch> b(new gh_ebatch());
-  b->device = device;
-  b->num_cu = prop.multiProcessorCount;
-  GH_HIP(hipSetDevice(device));
-  if (int rc = b->stream.create()) return rc;
-  if (int rc = b->done.create(hipEventDisableTiming)) return rc;
-  if (int rc = b->ev_in.create(hipEventDisableTiming)) return rc;
-  if (int rc = b->ev.create()) return rc;
+  if (int rc = b->q.create(device, "no HIP device visible (the GPU encoder has no CPU fallback)")) return rc;
   if (int rc = b->ev_hist.create()) return rc;
   *out = b.release();
   return GH_OK;
@@ -1352,10 +1310,9 @@ static std::vector<EBatchDesc> ebatch_descs(const gh_ebatch* b) {
 static int ebatch_load(gh_ebatch* b, const std::vector<const uint8_t*>& src, const uint64_t* n, bool device,
                        void* hip_stream) {
   const uint32_t ns = (uint32_t)src.size();
-  GH_HIP(hipSetDevice(b->device));
-  if (b->enqueued) GH_HIP(hipEventSynchronize(b->done));  // the previous batch's encode reads what is replaced
-  GH_HIP(hipStreamSynchronize(b->stream));
-  b->loaded = b->planned = b->enqueued = false;
+  GH_HIP(hipSetDevice(b->q.device));
+  if (int rc = b->q.quiesce()) return rc;  // the previous batch's encode reads what is replaced
+  b->loaded = b->planned = false;
   EBatchInPlan inp;
   if (int rc = ebatch_in_plan(n, ns, inp)) return rc;
   for (uint32_t i = 0; i < ns; ++i)
@@ -1367,38 +1324,27 @@ static int ebatch_load(gh_ebatch* b, const std::vector<const uint8_t*>& src, con
   std::vector<uint32_t> unit0(ns + 1);
   for (uint32_t i = 0; i < ns; ++i) unit0[i] = (uint32_t)ip.ext[i].unit0;
   unit0[ns] = (uint32_t)ip.nunits;
-  if (int rc = b->unit0.reserve(4ull * (ns + 1))) return rc;
-  GH_HIP(hipMemcpy(b->unit0.get(), unit0.data(), 4ull * (ns + 1), hipMemcpyHostToDevice));
+  if (int rc = upload_at_least(b->unit0, unit0.data(), 4ull * (ns + 1))) return rc;
+  // (room for the tables too: gh_ebatch_plan uploads the descriptors again, with them)
   if (int rc = b->code.reserve(std::max<uint64_t>((sizeof(EBatchDesc) + 1024ull) * ns, 16))) return rc;
-  if (ns) {
-    const std::vector<EBatchDesc> d = ebatch_descs(b);
-    GH_HIP(hipMemcpy(b->code.get(), d.data(), sizeof(EBatchDesc) * (uint64_t)ns, hipMemcpyHostToDevice));
-  }
+  if (int rc = upload_at_least(b->code, ebatch_descs(b).data(), sizeof(EBatchDesc) * (uint64_t)ns)) return rc;
   if (int rc = b->in.reserve(std::max<uint64_t>(ip.in_bytes, 16))) return rc;
   if (!device) {
     // the arena is assembled in host memory, padding included, and goes up in one copy
     std::vector<uint8_t> stage(ip.in_bytes, 0);
     for (uint32_t i = 0; i < ns; ++i)
       if (n[i]) std::memcpy(stage.data() + ip.ext[i].in_off, src[i], n[i]);
-    if (!stage.empty()) {
-      if (use_staged(stage.size())) {
-        if (int rc = h2d_staged(b->device, stage.data(), stage.size(), b->in.get())) return rc;
-      } else {
-        GH_HIP(hipMemcpy(b->in.get(), stage.data(), stage.size(), hipMemcpyHostToDevice));
-      }
-    }
+    if (int rc = upload_arena(b->q.device, b->in, stage.data(), stage.size())) return rc;
   } else if (ip.in_bytes) {
     std::vector<EBatchCopyItem> items(ns);
     for (uint32_t i = 0; i < ns; ++i) items[i] = EBatchCopyItem{src[i], n[i], ip.ext[i].in_off, ip.ext[i].in_bytes};
-    if (int rc = b->items.reserve(sizeof(EBatchCopyItem) * (uint64_t)ns)) return rc;
-    GH_HIP(hipMemcpy(b->items.get(), items.data(), sizeof(EBatchCopyItem) * (uint64_t)ns, hipMemcpyHostToDevice));
+    if (int rc = upload_at_least(b->items, items.data(), sizeof(EBatchCopyItem) * (uint64_t)ns)) return rc;
     // after what the producer's stream holds now, then one copy kernel on the batch's stream
-    GH_HIP(hipEventRecord(b->ev_in, (hipStream_t)hip_stream));
-    GH_HIP(hipStreamWaitEvent(b->stream, b->ev_in, 0));
-    hipLaunchKernelGGL(gh_ebatch_copy_kernel, dim3(std::min<uint32_t>(ns, 4096u), EB_COPY_Y), dim3(256), 0, b->stream,
+    if (int rc = b->q.follow(hip_stream)) return rc;
+    hipLaunchKernelGGL(gh_ebatch_copy_kernel, dim3(std::min<uint32_t>(ns, 4096u), EB_COPY_Y), dim3(256), 0, b->q.stream,
                        b->items.get<EBatchCopyItem>(), ns, b->in.get<uint8_t>());
     GH_HIP(hipGetLastError());
-    GH_HIP(hipStreamSynchronize(b->stream));
+    GH_HIP(hipStreamSynchronize(b->q.stream));
   }
   b->loaded = true;
   return GH_OK;
@@ -1422,14 +1368,6 @@ extern "C" int gh_ebatch_load_device(gh_ebatch* b, const gh_ebatch_item* items, 
   return ebatch_load(b, src, n.data(), true, hip_stream);
 }
 
-// GH_EBATCH_GRID=k (tests): k workgroups for the per-unit kernels (histogram at plan time;
-// bits and write at encode time), so that one wave walks many units and streams.
-static uint32_t ebatch_grid(const gh_ebatch* b) {
-  if (const char* eg = getenv("GH_EBATCH_GRID")) return (uint32_t)std::clamp<long>(atol(eg), 1, 1l << 20);
-  const uint64_t want = ceil_div(b->inp.nunits, EB_WAVES);
-  return (uint32_t)std::clamp<uint64_t>(want, 1, 8ull * (uint64_t)b->num_cu);
-}
-
 static EBatchParams ebatch_params(const gh_ebatch* b) {
   EBatchParams p{};
   p.desc = b->code.get<EBatchDesc>();
@@ -1451,9 +1389,9 @@ static EBatchParams ebatch_params(const gh_ebatch* b) {
 extern "C" int gh_ebatch_plan(gh_ebatch* b, int force_version, int threads) {
   if (!b) return fail(GH_E_ARG, "null batch");
   if (!b->loaded) return fail(GH_E_STATE, "gh_ebatch_plan before a load");
-  GH_HIP(hipSetDevice(b->device));
-  if (b->enqueued) GH_HIP(hipEventSynchronize(b->done));  // (the tables of the last encode are replaced)
-  b->planned = b->enqueued = false;
+  GH_HIP(hipSetDevice(b->q.device));
+  if (int rc = b->q.quiesce()) return rc;  // (the tables of the last encode are replaced)
+  b->planned = false;
   const uint32_t ns = b->nstreams;
   const uint64_t nunits = b->inp.nunits;
   // 1. every stream's histogram: one launch, 2. one read-back
@@ -1461,16 +1399,18 @@ extern "C" int gh_ebatch_plan(gh_ebatch* b, int force_version, int threads) {
   b->hist_ms = 0;
   if (ns) {
     if (int rc = b->counts.reserve(2048ull * ns)) return rc;
-    GH_HIP(hipMemsetAsync(b->counts.get(), 0, 2048ull * ns, b->stream));
-    GH_HIP(hipEventRecord(b->ev_hist.a, b->stream));
+    GH_HIP(hipMemsetAsync(b->counts.get(), 0, 2048ull * ns, b->q.stream));
+    GH_HIP(hipEventRecord(b->ev_hist.a, b->q.stream));
     if (nunits) {
       const EBatchParams p = ebatch_params(b);
-      hipLaunchKernelGGL(gh_ebatch_hist_kernel, dim3(ebatch_grid(b)), dim3(EB_TB), 0, b->stream, p);
+      // GH_EBATCH_GRID=k (tests): k workgroups for the per-unit kernels, here and at encode time
+      const uint32_t grid = unit_grid("GH_EBATCH_GRID", nunits, EB_WAVES, b->q.num_cu);
+      hipLaunchKernelGGL(gh_ebatch_hist_kernel, dim3(grid), dim3(EB_TB), 0, b->q.stream, p);
       GH_HIP(hipGetLastError());
     }
-    GH_HIP(hipEventRecord(b->ev_hist.b, b->stream));
-    GH_HIP(hipMemcpyAsync(counts.data(), b->counts.get(), 2048ull * ns, hipMemcpyDeviceToHost, b->stream));
-    GH_HIP(hipStreamSynchronize(b->stream));
+    GH_HIP(hipEventRecord(b->ev_hist.b, b->q.stream));
+    GH_HIP(hipMemcpyAsync(counts.data(), b->counts.get(), 2048ull * ns, hipMemcpyDeviceToHost, b->q.stream));
+    GH_HIP(hipStreamSynchronize(b->q.stream));
     if (int rc = b->ev_hist.elapsed(&b->hist_ms)) return rc;
   }
   // 3. the host plans, threaded over streams (streams are handed out by a shared counter)
@@ -1555,40 +1495,33 @@ extern "C" int gh_ebatch_plan_of(gh_ebatch* b, uint32_t stream, gh_encode_plan* 
 extern "C" int gh_ebatch_encode(gh_ebatch* b, void* hip_stream, int timed) {
   if (!b) return fail(GH_E_ARG, "null batch");
   if (!b->planned) return fail(GH_E_STATE, "gh_ebatch_encode before a plan");
-  GH_HIP(hipSetDevice(b->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)b->stream;
-  // encodes of one batch share its scratch and its arenas: they run in the order they were made
-  if (b->enqueued) GH_HIP(hipStreamWaitEvent(st, b->done, 0));
+  GH_HIP(hipSetDevice(b->q.device));
   const EBatchParams p = ebatch_params(b);
-  if (timed) GH_HIP(hipEventRecord(b->ev.a, st));
+  // encodes of one batch share its scratch and its arenas: they run in the order they were made
+  hipStream_t st;
+  if (int rc = b->q.begin(hip_stream, timed != 0, &st)) return rc;
   // (no memset of the flags: the scan kernel writes every status word and the summary)
   if (b->outp.pay_words) GH_HIP(hipMemsetAsync(b->payload.get(), 0, 4 * b->outp.pay_words, st));
   if (b->outp.gap_words) GH_HIP(hipMemsetAsync(b->gaps.get(), 0, 4 * b->outp.gap_words, st));
   if (b->nstreams) {
-    const uint32_t grid = ebatch_grid(b);
+    const uint32_t grid = unit_grid("GH_EBATCH_GRID", p.nunits, EB_WAVES, b->q.num_cu);
     if (p.nunits) hipLaunchKernelGGL(gh_ebatch_bits_kernel, dim3(grid), dim3(EB_TB), 0, st, p);
     hipLaunchKernelGGL(gh_ebatch_scan_kernel, dim3(1), dim3(EB_SCAN_TB), 0, st, p);
     if (p.nunits) hipLaunchKernelGGL(gh_ebatch_write_kernel, dim3(grid), dim3(EB_TB), 0, st, p);
     GH_HIP(hipGetLastError());
   }
-  if (timed) GH_HIP(hipEventRecord(b->ev.b, st));
-  GH_HIP(hipEventRecord(b->done, st));
-  b->enqueued = true;
-  b->timed = timed != 0;
-  return GH_OK;
+  return b->q.end(st);
 }
 
 extern "C" int gh_ebatch_wait(gh_ebatch* b, gh_ebatch_report* rep) {
   if (!b) return fail(GH_E_ARG, "null batch");
   if (rep) *rep = gh_ebatch_report{};
-  if (!b->planned || !b->enqueued) return fail(GH_E_STATE, "gh_ebatch_wait without an encode since the plan");
-  GH_HIP(hipSetDevice(b->device));
-  GH_HIP(hipEventSynchronize(b->done));
+  if (!b->planned || !b->q.enqueued) return fail(GH_E_STATE, "gh_ebatch_wait without an encode since the plan");
+  GH_HIP(hipSetDevice(b->q.device));
+  float ms = 0;
+  if (int rc = b->q.wait(&ms)) return rc;
   unsigned int sum[2] = {0, 0};
   if (b->nstreams) GH_HIP(hipMemcpy(sum, b->flags.get(), sizeof(sum), hipMemcpyDeviceToHost));
-  float ms = 0;
-  if (b->timed)
-    if (int rc = b->ev.elapsed(&ms)) return rc;
   if (rep) {
     rep->in_bytes = b->inp.sum_n;
     rep->out_bytes = b->out_bytes;
@@ -1614,12 +1547,12 @@ extern "C" int gh_ebatch_sizes(gh_ebatch* b, uint64_t* file_bytes, uint32_t cap)
 
 extern "C" int gh_ebatch_download(gh_ebatch* b, uint32_t stream, void* out, uint64_t out_len) {
   if (!b || !out) return fail(GH_E_ARG, "null argument");
-  if (!b->planned || !b->enqueued) return fail(GH_E_STATE, "gh_ebatch_download before an encode");
+  if (!b->planned || !b->q.enqueued) return fail(GH_E_STATE, "gh_ebatch_download before an encode");
   if (stream >= b->nstreams) return fail(GH_E_ARG, "no such stream in the batch");
   const gh_encode_plan& pl = b->plans[stream];
   if (out_len < pl.file_bytes) return fail(GH_E_SMALL, "output buffer too small");
-  GH_HIP(hipSetDevice(b->device));
-  GH_HIP(hipEventSynchronize(b->done));
+  GH_HIP(hipSetDevice(b->q.device));
+  GH_HIP(hipEventSynchronize(b->q.done));
   uint8_t* o = (uint8_t*)out;
   const size_t hdr = encode_header(&pl, o);
   const uint64_t GW = ceil_div(pl.g, GH_GAPS_PER_WORD);

@@ -310,32 +310,8 @@ __global__ __launch_bounds__(TBK) void gh_ws_count_kernel(const WsParams p) {
 // Exclusive scan of the range totals (one workgroup), and the stream total.
 __global__ __launch_bounds__(WS_SCAN_TB) void gh_ws_scan_kernel(const WsParams p) {
   __shared__ unsigned long long s_w[WS_SCAN_TB / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const uint32_t per = (p.nranges + WS_SCAN_TB - 1) / WS_SCAN_TB;
-  const uint32_t i0 = min((uint32_t)tid * per, p.nranges), i1 = min(i0 + per, p.nranges);
-  unsigned long long s = 0;
-  for (uint32_t i = i0; i < i1; ++i) s += p.rng_tot[i];
-  unsigned long long incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_w[wid] = incl;
-  __syncthreads();
-  unsigned long long base = 0, all = 0;
-#pragma unroll
-  for (int q = 0; q < WS_SCAN_TB / 64; ++q) {
-    base += q < wid ? s_w[q] : 0ull;
-    all += s_w[q];
-  }
-  unsigned long long run = base + incl - s;
-  for (uint32_t i = i0; i < i1; ++i) {
-    const unsigned long long t = p.rng_tot[i];
-    p.rng_off[i] = run;
-    run += t;
-  }
-  if (tid == 0) *p.total = all;
+  const unsigned long long all = block_excl_scan<WS_SCAN_TB>(p.rng_tot, p.rng_off, p.nranges, s_w);
+  if (threadIdx.x == 0) *p.total = all;
 }
 
 // ptr += byte 1 of meta (n, the lookup's symbols): one SDWA add.

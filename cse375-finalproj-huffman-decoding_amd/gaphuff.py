@@ -326,6 +326,51 @@ def _ptr(a: np.ndarray) -> ctypes.c_void_p:
     return ctypes.c_void_p(a.ctypes.data)
 
 
+def _name(fn, *args, cap: int = 64) -> str:
+    """A kernel-name query: ``fn(*args, buf, cap)`` fills a NUL-terminated string."""
+    buf = ctypes.create_string_buffer(cap)
+    _check(fn(*args, buf, len(buf)))
+    return buf.value.decode()
+
+
+class _Handle:
+    """Owner of one library object on one device: ``create_fn(device, &h)`` makes it,
+    ``destroy_fn(h)`` releases it, on :meth:`close`, at the end of a ``with`` block or when
+    the object is collected."""
+
+    def __init__(self, create_fn, destroy_fn, device: int):
+        self._h = ctypes.c_void_p()
+        self._destroy = destroy_fn
+        self.device = device
+        _check(create_fn(device, ctypes.byref(self._h)))
+
+    def close(self) -> None:
+        if self._h:
+            self._destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _wait(self, fn, report):
+        """``fn(h, &report)``; raises :class:`GapHuffError` with the report as ``.report``."""
+        rc = fn(self._h, ctypes.byref(report))
+        if rc != GH_OK:
+            e = GapHuffError(rc, lib().gh_last_error().decode(errors="replace"))
+            e.report = report
+            raise e
+        return report
+
+
 # --------------------------------------------------------------------------- format
 @dataclass
 class Stream:
@@ -495,7 +540,7 @@ def merge_index_slices(plan: gh_encode_plan, log2_stride: int, parts) -> np.ndar
     return img
 
 
-class Encoder:
+class Encoder(_Handle):
     """One gh_ectx: the GPU encoder on one gfx950 device.
 
     Mirrors the reference encoder CLI's steps (encoder/src/huff.cpp:30-220): load the
@@ -503,27 +548,9 @@ class Encoder:
     the compressed.huff image -- byte-identical to ``encode()``."""
 
     def __init__(self, device: int = 0):
-        self._h = ctypes.c_void_p()
-        _check(lib().gh_ectx_create(device, ctypes.byref(self._h)))
+        super().__init__(lib().gh_ectx_create, lib().gh_ectx_destroy, device)
         self.plan: Optional[gh_encode_plan] = None
         self._slice: Optional[gh_slice] = None  # extents of the last slice encode
-
-    def close(self) -> None:
-        if self._h:
-            lib().gh_ectx_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def load(self, data) -> None:
         d = _u8(data)
@@ -556,9 +583,7 @@ class Encoder:
     def kernel_shape(self) -> str:
         """Name of the write kernel instantiation the last encode or slice encode picked
         (gh_ectx_kernel_shape)."""
-        buf = ctypes.create_string_buffer(64)
-        _check(lib().gh_ectx_kernel_shape(self._h, buf, len(buf)))
-        return buf.value.decode()
+        return _name(lib().gh_ectx_kernel_shape, self._h)
 
     def counts(self) -> np.ndarray:
         """GPU histogram of the loaded input (256 x np.uint64); makes no plan."""
@@ -681,24 +706,18 @@ def plan_shards(g: int, nshards: int) -> list:
 
 def kernel_shapes() -> list:
     """Every kernel name a load can pick (gh_kernel_shapes); needs no device."""
-    buf = ctypes.create_string_buffer(1 << 14)
-    _check(lib().gh_kernel_shapes(buf, len(buf)))
-    return buf.value.decode().split()
+    return _name(lib().gh_kernel_shapes, cap=1 << 14).split()
 
 
 def enc_kernel_shapes() -> list:
     """Every write kernel name an encode can pick (gh_enc_kernel_shapes); needs no device."""
-    buf = ctypes.create_string_buffer(1 << 10)
-    _check(lib().gh_enc_kernel_shapes(buf, len(buf)))
-    return buf.value.decode().split()
+    return _name(lib().gh_enc_kernel_shapes, cap=1 << 10).split()
 
 
 def enc_kernel_shape_for(n: int, bits: int, slice: bool = False) -> str:
     """The write kernel an encode picks for ``n`` input bytes of ``bits`` code bits
     (gh_enc_kernel_shape_for); needs no device."""
-    buf = ctypes.create_string_buffer(64)
-    _check(lib().gh_enc_kernel_shape_for(n, bits, int(slice), buf, len(buf)))
-    return buf.value.decode()
+    return _name(lib().gh_enc_kernel_shape_for, n, bits, int(slice))
 
 
 def sync_lut_bits() -> int:
@@ -711,32 +730,13 @@ def device_count() -> int:
 
 
 # --------------------------------------------------------------------------- decoder
-class Decoder:
+class Decoder(_Handle):
     """One gh_ctx: a shard of a stream resident on one GPU."""
 
     def __init__(self, device: int = 0):
-        self._h = ctypes.c_void_p()
-        _check(lib().gh_ctx_create(device, ctypes.byref(self._h)))
-        self.device = device
+        super().__init__(lib().gh_ctx_create, lib().gh_ctx_destroy, device)
         self._stream: Optional[Stream] = None
         self._file_g: Optional[int] = None  # G of the last load_file / load_raw
-
-    def close(self) -> None:
-        if self._h:
-            lib().gh_ctx_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def load(self, stream: Stream, seg_begin: int = 0, seg_end: Optional[int] = None,
              out_cap: int = 0) -> None:
@@ -798,9 +798,7 @@ class Decoder:
 
     def kernel_shape(self) -> str:
         """Name of the kernel instantiation(s) the last load picked (gh_ctx_kernel_shape)."""
-        buf = ctypes.create_string_buffer(256)
-        _check(lib().gh_ctx_kernel_shape(self._h, buf, len(buf)))
-        return buf.value.decode()
+        return _name(lib().gh_ctx_kernel_shape, self._h, cap=256)
 
     def build_index(self, log2_stride: int = 8):
         """Seek index of the loaded stream (the load must cover all its segments), built on
@@ -926,37 +924,16 @@ def batch_layout(ns) -> np.ndarray:
 
 def batch_kernel_shapes() -> list:
     """Every kernel name a batch load can pick (gh_batch_kernel_shapes); needs no device."""
-    buf = ctypes.create_string_buffer(1 << 10)
-    _check(lib().gh_batch_kernel_shapes(buf, len(buf)))
-    return buf.value.decode().split()
+    return _name(lib().gh_batch_kernel_shapes, cap=1 << 10).split()
 
 
-class BatchDecoder:
+class BatchDecoder(_Handle):
     """One gh_batch: many independent streams resident on one GPU, decoded by one fixed set
     of kernel launches per batch."""
 
     def __init__(self, device: int = 0):
-        self._h = ctypes.c_void_p()
-        _check(lib().gh_batch_create(device, ctypes.byref(self._h)))
-        self.device = device
+        super().__init__(lib().gh_batch_create, lib().gh_batch_destroy, device)
         self.ns: list = []  # output bytes of every loaded stream
-
-    def close(self) -> None:
-        if self._h:
-            lib().gh_batch_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def load(self, images_or_streams) -> None:
         """Load a batch from host memory: compressed.huff images (bytes / np.uint8) or parsed
@@ -991,13 +968,7 @@ class BatchDecoder:
     def wait(self) -> gh_batch_report:
         """Wait for the last :meth:`decode` and return its report; raises
         :class:`GapHuffError` (with the report as ``.report``) when a stream was bad."""
-        r = gh_batch_report()
-        rc = lib().gh_batch_wait(self._h, ctypes.byref(r))
-        if rc != GH_OK:
-            e = GapHuffError(rc, lib().gh_last_error().decode(errors="replace"))
-            e.report = r
-            raise e
-        return r
+        return self._wait(lib().gh_batch_wait, gh_batch_report())
 
     def status(self):
         """(GH_ST_* bits, codewords counted) per stream, as uint32 / uint64 arrays."""
@@ -1029,9 +1000,7 @@ class BatchDecoder:
 
     def kernel_shape(self) -> str:
         """Name of the kernel instantiations the last load picked (gh_batch_kernel_shape)."""
-        buf = ctypes.create_string_buffer(64)
-        _check(lib().gh_batch_kernel_shape(self._h, buf, len(buf)))
-        return buf.value.decode()
+        return _name(lib().gh_batch_kernel_shape, self._h)
 
 
 def decode_batch(images, device: int = 0) -> list:
@@ -1046,38 +1015,17 @@ def decode_batch(images, device: int = 0) -> list:
 # --------------------------------------------------------------------------- batched encode
 def ebatch_kernel_shapes() -> list:
     """Every kernel name a batched encode can pick (gh_ebatch_kernel_shapes); needs no device."""
-    buf = ctypes.create_string_buffer(1 << 10)
-    _check(lib().gh_ebatch_kernel_shapes(buf, len(buf)))
-    return buf.value.decode().split()
+    return _name(lib().gh_ebatch_kernel_shapes, cap=1 << 10).split()
 
 
-class BatchEncoder:
+class BatchEncoder(_Handle):
     """One gh_ebatch: many independent inputs resident on one GPU, each encoded with its own
     code by one fixed set of launches per batch.  load / load_device, plan, encode, wait, then
     sizes / download / items."""
 
     def __init__(self, device: int = 0):
-        self._h = ctypes.c_void_p()
-        _check(lib().gh_ebatch_create(device, ctypes.byref(self._h)))
-        self.device = device
+        super().__init__(lib().gh_ebatch_create, lib().gh_ebatch_destroy, device)
         self.ns: list = []  # input bytes of every loaded stream
-
-    def close(self) -> None:
-        if self._h:
-            lib().gh_ebatch_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def load(self, datas) -> None:
         """Load a batch of inputs (bytes / np.uint8) from host memory (gh_ebatch_load)."""
@@ -1108,13 +1056,7 @@ class BatchEncoder:
     def wait(self) -> gh_ebatch_report:
         """Wait for the last :meth:`encode` and return its report; raises
         :class:`GapHuffError` (with the report as ``.report``) on a layout tripwire."""
-        r = gh_ebatch_report()
-        rc = lib().gh_ebatch_wait(self._h, ctypes.byref(r))
-        if rc != GH_OK:
-            e = GapHuffError(rc, lib().gh_last_error().decode(errors="replace"))
-            e.report = r
-            raise e
-        return r
+        return self._wait(lib().gh_ebatch_wait, gh_ebatch_report())
 
     def sizes(self) -> np.ndarray:
         """file_bytes of every stream's image."""
@@ -1146,9 +1088,7 @@ class BatchEncoder:
 
     def kernel_shape(self) -> str:
         """Name of the per-unit kernels' shape the last plan picked (gh_ebatch_kernel_shape)."""
-        buf = ctypes.create_string_buffer(64)
-        _check(lib().gh_ebatch_kernel_shape(self._h, buf, len(buf)))
-        return buf.value.decode()
+        return _name(lib().gh_ebatch_kernel_shape, self._h)
 
 
 def encode_batch(datas, device: int = 0) -> list:
