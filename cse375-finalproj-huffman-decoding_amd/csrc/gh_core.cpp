@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "gh_internal.hpp"
+#include "gh_pm_flat.hpp"
 
 namespace gh {
 
@@ -172,6 +173,50 @@ extern "C" int gh_package_merge(const uint64_t* sorted_counts, uint32_t nsyms,
   for (int i = 0; i < n; ++i) {
     if (len[i] < 1 || len[i] > L) return fail(GH_E_TABLE, "package-merge produced bad length");
     lengths[i] = (uint8_t)len[i];
+  }
+  return GH_OK;
+}
+
+// The same lengths by the level-by-level form (gh_pm_flat.hpp), driven serially: what one
+// workgroup of gh_ebatch_code_kernel does per stream, an item at a time.
+extern "C" int gh_package_merge_flat(const uint64_t* sorted_counts, uint32_t nsyms, uint8_t* lengths) {
+  if (!lengths || (nsyms && !sorted_counts)) return fail(GH_E_ARG, "null argument");
+  if (nsyms > GH_MAX_SYMBOLS) return fail(GH_E_ARG, "too many symbols");
+  if (nsyms == 0) return GH_OK;
+  if (nsyms == 1) {
+    lengths[0] = 1;
+    return GH_OK;
+  }
+  const uint64_t* c = sorted_counts;
+  const uint32_t n = nsyms, need = pm_need(n);
+  uint64_t w[2][PM_MAX_ITEMS];
+  uint32_t mask[PM_LEVELS][PM_MASK_WORDS] = {}, pre[PM_LEVELS][PM_MASK_WORDS] = {}, nl[PM_LEVELS];
+  const uint64_t* prev = c;
+  uint32_t m = n;
+  for (uint32_t l = 1; l < PM_LEVELS; ++l) {
+    uint64_t* next = w[l & 1];
+    const uint32_t np = m / 2;
+    for (uint32_t j = 0; j < n; ++j) {
+      const uint32_t pos = pm_leaf_pos(c, prev, np, j);
+      if (pos < need) {
+        next[pos] = c[j];
+        mask[l][pos >> 5] |= 1u << (pos & 31u);
+      }
+    }
+    for (uint32_t i = 0; i < np; ++i) {
+      const uint64_t P = pm_package(prev, i);
+      const uint32_t pos = pm_package_pos(c, n, i, P);
+      if (pos < need) next[pos] = P;
+    }
+    m = pm_next_items(n, m);
+    pm_mask_prefix(mask[l], pre[l]);
+    prev = next;
+  }
+  pm_trace(&mask[0][0], &pre[0][0], n, nl);
+  for (uint32_t j = 0; j < n; ++j) {
+    const uint32_t len = pm_length(nl, j);
+    if (len < 1 || len > PM_LEVELS) return fail(GH_E_TABLE, "package-merge produced bad length");
+    lengths[j] = (uint8_t)len;
   }
   return GH_OK;
 }
@@ -544,6 +589,13 @@ int gh::plan_from_counts(gh_encode_plan* plan, int force_version) {
     bits += (uint64_t)c.len[i] * plan->count[c.sym[i]];
   }
   plan->bits = bits;
+  return plan_sizes(plan, force_version);
+}
+
+// w, g, version and file_bytes from plan->n, plan->nsyms and plan->bits.
+int gh::plan_sizes(gh_encode_plan* plan, int force_version) {
+  const uint64_t bits = plan->bits;
+  const uint32_t ns = plan->nsyms;
   plan->g = ceil_div(bits, GH_SEGMENT_BITS);
   plan->w = ceil_div(bits, 32);
   const uint64_t lim = 1ull << 31;

@@ -19,7 +19,11 @@
 //   gh_ebatch_hist_kernel   every stream's byte histogram: per-wave LDS counters, flushed
 //                           with global u64 atomics into counts[stream][256] when the wave's
 //                           run leaves the stream;
-//   (host)                  one gh::plan_from_counts per stream, threaded over streams;
+//   (host)                  one gh::plan_from_counts per stream, threaded over streams; or
+//   gh_ebatch_code_kernel   (gh_batchenc_plan_device) one workgroup per stream: sort, the
+//                           package-merge level by level (gh_pm_flat.hpp), canonical codes,
+//                           the stream's table and a 528-byte record for the host; at the
+//                           end of this file;
 //   gh_ebatch_bits_kernel   code bits per unit (u32);
 //   gh_ebatch_scan_kernel   one workgroup: exclusive u64 scan of the unit bits; a unit's bit
 //                           offset inside its stream is its scan value minus that of the
@@ -366,6 +370,127 @@ __global__ __launch_bounds__(EB_TB) void gh_ebatch_write_kernel(const EBatchPara
       } else {
         gout[lane] = x;
       }
+    }
+  }
+}
+
+// ---- codes built on the device (gh_batchenc_plan_device) ------------------------------------
+// What the code kernel leaves for the host per stream: all it needs for the image's header
+// and the output layout.
+struct EBatchCodeRec {
+  unsigned long long bits;  // sum len * count
+  uint32_t nsyms, zero;
+  gh_sym syms[GH_MAX_SYMBOLS];  // file order (most frequent first), zero past nsyms
+};
+static_assert(sizeof(EBatchCodeRec) == 528 && sizeof(gh_sym) == 2, "EBatchCodeRec layout");
+
+// One workgroup per stream (grid-stride over streams): from counts[stream][256] to the
+// stream's 256 table entries and its record.  plan_from_counts' steps (gh_core.cpp) with the
+// package-merge in its level-by-level form (gh_pm_flat.hpp, the arithmetic of
+// gh_package_merge_flat): stable sort of the present symbols by (count, symbol value) as
+// 256 compares per thread, 15 level steps (thread t places leaf t and package t: every
+// level holds at most 256 leaves and 255 packages), the trace by one thread over prefix
+// popcounts, the canonical code from the counts per length as gh_batch_table_kernel forms it.
+// Everything is in LDS (about 16 KB).  The only synchronisation is __syncthreads(), and no
+// barrier stands inside a branch: a stream of 0 or 1 symbols runs the same steps with nothing
+// to place (pm_need = 0), and ns is computed by every thread from the same LDS words.  The
+// loops are bounded by nstreams, 256, 16 and the binary searches' 9 steps.
+__global__ __launch_bounds__(EB_TB) void gh_ebatch_code_kernel(const unsigned long long* counts, uint32_t* tables,
+                                                                EBatchCodeRec* recs, uint32_t nstreams) {
+  static_assert(EB_TB == GH_MAX_SYMBOLS && EB_TB == PM_LEVELS * PM_MASK_WORDS, "a thread per symbol and per mask word");
+  __shared__ uint64_t s_cnt[256];      // by symbol value
+  __shared__ uint64_t s_c[256];        // sorted ascending: the leaves
+  __shared__ uint64_t s_w[2][PM_MAX_ITEMS];  // the level below and the level being built
+  __shared__ uint32_t s_mask[PM_LEVELS * PM_MASK_WORDS], s_pre[PM_LEVELS * PM_MASK_WORDS];
+  __shared__ uint32_t s_nl[PM_LEVELS];
+  __shared__ uint32_t s_lcnt[PM_LEVELS + 1], s_base[PM_LEVELS + 1], s_first[PM_LEVELS + 1];
+  __shared__ uint32_t s_ent[256];                   // the table, by symbol value
+  __shared__ uint32_t s_hdr[128];                   // the record's syms, two per word
+  __shared__ uint8_t s_sym[256];                    // symbol value by sorted rank
+  __shared__ unsigned long long s_bits[EB_WAVES];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t s = blockIdx.x; s < nstreams; s += gridDim.x) {
+    __syncthreads();  // the previous stream's stores have read the LDS
+    s_cnt[tid] = counts[256ull * s + tid];
+    s_mask[tid] = 0;
+    s_ent[tid] = 0;
+    if (tid < 128) s_hdr[tid] = 0;
+    if (tid <= PM_LEVELS) s_lcnt[tid] = 0;
+    __syncthreads();
+    // a. the sort: rank among the present symbols by (count, symbol value)
+    const uint64_t cv = s_cnt[tid];
+    uint32_t n = 0, r = 0;
+    for (uint32_t u = 0; u < 256; ++u) {
+      const uint64_t cu = s_cnt[u];
+      n += cu != 0;
+      r += cu != 0 && (cu < cv || (cu == cv && u < tid));
+    }
+    if (cv) {
+      s_c[r] = cv;
+      s_sym[r] = (uint8_t)tid;
+    }
+    __syncthreads();
+    // b. levels 2 .. 16 (level 1 is s_c itself), then the trace
+    const uint32_t need = pm_need(n);
+    const uint64_t* prev = s_c;
+    uint32_t m = n;
+    for (uint32_t l = 1; l < PM_LEVELS; ++l) {
+      uint64_t* next = s_w[l & 1];
+      const uint32_t np = m / 2;  // (<= 255)
+      if (tid < n) {
+        const uint32_t pos = pm_leaf_pos(s_c, prev, np, tid);
+        if (pos < need) {
+          next[pos] = s_c[tid];
+          atomicOr(&s_mask[l * PM_MASK_WORDS + (pos >> 5)], 1u << (pos & 31u));
+        }
+      }
+      if (tid < np) {
+        const uint64_t P = pm_package(prev, tid);
+        const uint32_t pos = pm_package_pos(s_c, n, tid, P);
+        if (pos < need) next[pos] = P;
+      }
+      m = pm_next_items(n, m);
+      __syncthreads();
+      prev = next;
+    }
+    {
+      // thread (l, w): the leaves of level l + 1 in the words before w
+      const uint32_t row = tid & ~(PM_MASK_WORDS - 1u), w = tid & (PM_MASK_WORDS - 1u);
+      uint32_t pre = 0;
+      for (uint32_t k = 0; k < PM_MASK_WORDS; ++k) pre += k < w ? (uint32_t)__builtin_popcount(s_mask[row + k]) : 0u;
+      s_pre[tid] = pre;
+    }
+    __syncthreads();
+    if (tid == 0) pm_trace(s_mask, s_pre, n, s_nl);
+    __syncthreads();
+    uint32_t len = 0;
+    if (tid < n) {
+      len = n == 1 ? 1u : pm_length(s_nl, tid);
+      atomicAdd(&s_lcnt[len], 1u);  // (len <= 16: one per level)
+    }
+    // c. bits, the canonical code and file order
+    const unsigned long long wb = wave_sum_u64(tid < n ? (unsigned long long)len * s_c[tid] : 0ull);
+    if ((tid & 63u) == 0) s_bits[tid >> 6] = wb;
+    __syncthreads();
+    if (tid == 0) pm_canon_bases(s_lcnt, s_base, s_first);
+    __syncthreads();
+    if (tid < n) {
+      const uint32_t f = n - 1u - tid, sym = s_sym[tid];
+      s_ent[sym] = pm_canon_entry(s_base, s_first, f, len);
+      ((uint16_t*)s_hdr)[f] = (uint16_t)(sym | (len << 8));  // {symbol, length}
+    }
+    __syncthreads();
+    // d. the stores
+    tables[256ull * s + tid] = s_ent[tid];
+    uint32_t* rec = (uint32_t*)(recs + s);
+    if (tid < 128) rec[4 + tid] = s_hdr[tid];
+    if (tid == 128) {
+      unsigned long long bits = 0;
+      for (int q = 0; q < EB_WAVES; ++q) bits += s_bits[q];
+      rec[0] = (uint32_t)bits;
+      rec[1] = (uint32_t)(bits >> 32);
+      rec[2] = n;
+      rec[3] = 0;
     }
   }
 }

@@ -58,6 +58,7 @@
 #include "gaphuff.h"
 #include "gh_hip.hpp"
 #include "gh_internal.hpp"
+#include "gh_pm_flat.hpp"
 #include "gh_units.hpp"
 #include "gh_wave.hpp"
 
@@ -1263,10 +1264,11 @@ constexpr uint32_t EBATCH_LAUNCHES = 5;  // two arena memsets, then bits, scan, 
 static const char* const EBATCH_SHAPE = "ebatch<lut=1>";
 
 struct gh_ebatch {
-  EventPair ev_hist;
+  EventPair ev_hist, ev_code;
   DevBuf in, unit0, items;                 // the loaded batch
   DevBuf code;                             // one EBatchDesc per stream, then 256 table entries per stream
   DevBuf counts;                           // 256 u64 per stream
+  DevBuf recs;                             // gh_batchenc_plan_device: one EBatchCodeRec per stream
   DevBuf unit_bits, unit_off, flags;       // encode scratch; flags: 4 summary words, then a status word per stream
   DevBuf payload, gaps;                    // the output arenas
   EBatchInPlan inp;
@@ -1275,8 +1277,9 @@ struct gh_ebatch {
   std::vector<gh_encode_plan> plans;
   uint32_t nstreams = 0;
   uint64_t out_bytes = 0;
-  float hist_ms = 0, plan_host_ms = 0;
+  float hist_ms = 0, code_ms = 0, plan_host_ms = 0;
   bool loaded = false, planned = false;
+  bool counts_on_device = false;  // a device plan: plans[i].count[] is filled by the first plan_of
   BatchQueue q;  // (last: its destructor waits for the encode before the buffers above go)
 };
 
@@ -1286,6 +1289,7 @@ extern "C" int gh_ebatch_create(int device, gh_ebatch** out) {
   std::unique_ptr<gh_ebatch> b(new gh_ebatch());
   if (int rc = b->q.create(device, "no HIP device visible (the GPU encoder has no CPU fallback)")) return rc;
   if (int rc = b->ev_hist.create()) return rc;
+  if (int rc = b->ev_code.create()) return rc;
   *out = b.release();
   return GH_OK;
 }
@@ -1386,29 +1390,68 @@ static EBatchParams ebatch_params(const gh_ebatch* b) {
   return p;
 }
 
+// Enqueues every stream's histogram on the batch's stream (ns > 0): counts zeroed, one launch
+// between the ev_hist events.
+static int ebatch_hist(gh_ebatch* b) {
+  const uint32_t ns = b->nstreams;
+  const uint64_t nunits = b->inp.nunits;
+  if (int rc = b->counts.reserve(2048ull * ns)) return rc;
+  GH_HIP(hipMemsetAsync(b->counts.get(), 0, 2048ull * ns, b->q.stream));
+  GH_HIP(hipEventRecord(b->ev_hist.a, b->q.stream));
+  if (nunits) {
+    const EBatchParams p = ebatch_params(b);
+    // GH_EBATCH_GRID=k (tests): k workgroups for the per-unit kernels, here and at encode time
+    const uint32_t grid = unit_grid("GH_EBATCH_GRID", nunits, EB_WAVES, b->q.num_cu);
+    hipLaunchKernelGGL(gh_ebatch_hist_kernel, dim3(grid), dim3(EB_TB), 0, b->q.stream, p);
+    GH_HIP(hipGetLastError());
+  }
+  GH_HIP(hipEventRecord(b->ev_hist.b, b->q.stream));
+  return GH_OK;
+}
+
+// The output layout from the streams' plans: out_bytes, outp, and the descriptors' plan-time
+// half (d: ebatch_descs).
+static int ebatch_layout(gh_ebatch* b, std::vector<EBatchDesc>& d) {
+  const uint32_t ns = b->nstreams;
+  std::vector<uint64_t> w(ns), g(ns);
+  b->out_bytes = 0;
+  for (uint32_t i = 0; i < ns; ++i) {
+    w[i] = b->plans[i].w;
+    g[i] = b->plans[i].g;
+    b->out_bytes += b->plans[i].file_bytes;
+  }
+  if (int rc = ebatch_out_plan(w.data(), g.data(), ns, b->outp)) return rc;
+  for (uint32_t i = 0; i < ns; ++i) {
+    d[i].pay_off = b->outp.ext[i].pay_off;
+    d[i].gap_off = b->outp.ext[i].gap_off;
+    d[i].bits = b->plans[i].bits;
+  }
+  return GH_OK;
+}
+
+// The arenas and the encode's scratch for the planned batch.
+static int ebatch_reserve_out(gh_ebatch* b) {
+  const uint64_t nunits = b->inp.nunits;
+  if (int rc = b->payload.reserve(std::max<uint64_t>(4 * b->outp.pay_words, 16))) return rc;
+  if (int rc = b->gaps.reserve(std::max<uint64_t>(4 * b->outp.gap_words, 16))) return rc;
+  if (int rc = b->unit_bits.reserve(std::max<uint64_t>(4 * nunits, 16))) return rc;
+  if (int rc = b->unit_off.reserve(8 * (nunits + 1))) return rc;
+  return b->flags.reserve(16 + 4ull * b->nstreams);
+}
+
 extern "C" int gh_ebatch_plan(gh_ebatch* b, int force_version, int threads) {
   if (!b) return fail(GH_E_ARG, "null batch");
   if (!b->loaded) return fail(GH_E_STATE, "gh_ebatch_plan before a load");
   GH_HIP(hipSetDevice(b->q.device));
   if (int rc = b->q.quiesce()) return rc;  // (the tables of the last encode are replaced)
   b->planned = false;
+  b->counts_on_device = false;
   const uint32_t ns = b->nstreams;
-  const uint64_t nunits = b->inp.nunits;
   // 1. every stream's histogram: one launch, 2. one read-back
   std::vector<uint64_t> counts(256ull * ns, 0);
-  b->hist_ms = 0;
+  b->hist_ms = b->code_ms = 0;
   if (ns) {
-    if (int rc = b->counts.reserve(2048ull * ns)) return rc;
-    GH_HIP(hipMemsetAsync(b->counts.get(), 0, 2048ull * ns, b->q.stream));
-    GH_HIP(hipEventRecord(b->ev_hist.a, b->q.stream));
-    if (nunits) {
-      const EBatchParams p = ebatch_params(b);
-      // GH_EBATCH_GRID=k (tests): k workgroups for the per-unit kernels, here and at encode time
-      const uint32_t grid = unit_grid("GH_EBATCH_GRID", nunits, EB_WAVES, b->q.num_cu);
-      hipLaunchKernelGGL(gh_ebatch_hist_kernel, dim3(grid), dim3(EB_TB), 0, b->q.stream, p);
-      GH_HIP(hipGetLastError());
-    }
-    GH_HIP(hipEventRecord(b->ev_hist.b, b->q.stream));
+    if (int rc = ebatch_hist(b)) return rc;
     GH_HIP(hipMemcpyAsync(counts.data(), b->counts.get(), 2048ull * ns, hipMemcpyDeviceToHost, b->q.stream));
     GH_HIP(hipStreamSynchronize(b->q.stream));
     if (int rc = b->ev_hist.elapsed(&b->hist_ms)) return rc;
@@ -1449,24 +1492,14 @@ extern "C" int gh_ebatch_plan(gh_ebatch* b, int force_version, int threads) {
     if (rcs[t]) return fail(rcs[t], msgs[t]);
   b->plan_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   // 5. the output arenas (before the upload: the descriptors hold their offsets)
-  std::vector<uint64_t> w(ns), g(ns);
-  b->out_bytes = 0;
-  for (uint32_t i = 0; i < ns; ++i) {
-    w[i] = b->plans[i].w;
-    g[i] = b->plans[i].g;
-    b->out_bytes += b->plans[i].file_bytes;
-  }
-  if (int rc = ebatch_out_plan(w.data(), g.data(), ns, b->outp)) return rc;
+  std::vector<EBatchDesc> d = ebatch_descs(b);
+  if (int rc = ebatch_layout(b, d)) return rc;
   // 4. one upload: the descriptors, then every stream's 256 left-aligned entries
   if (ns) {
     std::vector<uint8_t> up((sizeof(EBatchDesc) + 1024ull) * ns);
-    std::vector<EBatchDesc> d = ebatch_descs(b);
     uint32_t* tab = (uint32_t*)(up.data() + sizeof(EBatchDesc) * (uint64_t)ns);
     for (uint32_t i = 0; i < ns; ++i) {
       const gh_encode_plan& pl = b->plans[i];
-      d[i].pay_off = b->outp.ext[i].pay_off;
-      d[i].gap_off = b->outp.ext[i].gap_off;
-      d[i].bits = pl.bits;
       for (int v = 0; v < 256; ++v) {
         const uint32_t l = pl.len[v];
         tab[256ull * i + v] = l ? (pl.code[v] << (32u - l)) | l : 0u;
@@ -1475,12 +1508,108 @@ extern "C" int gh_ebatch_plan(gh_ebatch* b, int force_version, int threads) {
     std::memcpy(up.data(), d.data(), sizeof(EBatchDesc) * (uint64_t)ns);
     GH_HIP(hipMemcpy(b->code.get(), up.data(), up.size(), hipMemcpyHostToDevice));
   }
-  if (int rc = b->payload.reserve(std::max<uint64_t>(4 * b->outp.pay_words, 16))) return rc;
-  if (int rc = b->gaps.reserve(std::max<uint64_t>(4 * b->outp.gap_words, 16))) return rc;
-  if (int rc = b->unit_bits.reserve(std::max<uint64_t>(4 * nunits, 16))) return rc;
-  if (int rc = b->unit_off.reserve(8 * (nunits + 1))) return rc;
-  if (int rc = b->flags.reserve(16 + 4ull * ns)) return rc;
+  if (int rc = ebatch_reserve_out(b)) return rc;
   b->planned = true;
+  return GH_OK;
+}
+
+extern "C" int gh_batchenc_plan_device(gh_ebatch* b, int force_version) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_batchenc_plan_device before a load");
+  GH_HIP(hipSetDevice(b->q.device));
+  if (int rc = b->q.quiesce()) return rc;  // (the tables of the last encode are replaced)
+  b->planned = false;
+  b->counts_on_device = false;
+  const uint32_t ns = b->nstreams;
+  // 1. every stream's histogram, 2. every stream's code: its table where the encode kernels
+  // read it, its record for the host, 3. one read-back of the records
+  std::vector<EBatchCodeRec> recs(ns);
+  b->hist_ms = b->code_ms = 0;
+  if (ns) {
+    if (int rc = b->recs.reserve(sizeof(EBatchCodeRec) * (uint64_t)ns)) return rc;
+    if (int rc = ebatch_hist(b)) return rc;
+    GH_HIP(hipEventRecord(b->ev_code.a, b->q.stream));
+    {
+      // GH_EBATCH_GRID=k (tests): k workgroups walk all streams
+      const uint32_t grid = unit_grid("GH_EBATCH_GRID", ns, 1, b->q.num_cu);
+      const EBatchParams p = ebatch_params(b);
+      hipLaunchKernelGGL(gh_ebatch_code_kernel, dim3(grid), dim3(EB_TB), 0, b->q.stream, p.counts,
+                         const_cast<uint32_t*>(p.tables), b->recs.get<EBatchCodeRec>(), ns);
+      GH_HIP(hipGetLastError());
+    }
+    GH_HIP(hipEventRecord(b->ev_code.b, b->q.stream));
+    GH_HIP(hipMemcpyAsync(recs.data(), b->recs.get(), sizeof(EBatchCodeRec) * (uint64_t)ns, hipMemcpyDeviceToHost,
+                          b->q.stream));
+    GH_HIP(hipStreamSynchronize(b->q.stream));
+    if (int rc = b->ev_hist.elapsed(&b->hist_ms)) return rc;
+    if (int rc = b->ev_code.elapsed(&b->code_ms)) return rc;
+  }
+  // 4. the plans from the records: build_canon is the tripwire for the kernel's code (the
+  // scan kernel's GH_ST_LAYOUT is the one for its bit total)
+  const auto t0 = std::chrono::steady_clock::now();
+  b->plans.resize(ns);  // (every plan is cleared by the thread that fills it)
+  const auto plan_one = [&](uint32_t i) -> int {
+    const EBatchCodeRec& r = recs[i];
+    gh_encode_plan& pl = b->plans[i];
+    pl = gh_encode_plan{};
+    const auto who = [i] { return "stream " + std::to_string(i) + ": "; };
+    if (r.nsyms > GH_MAX_SYMBOLS || (r.nsyms == 0) != (b->n[i] == 0))
+      return fail(GH_E_TABLE, who() + "device-built code: bad symbol count");
+    pl.n = b->n[i];
+    pl.nsyms = r.nsyms;
+    std::memcpy(pl.syms, r.syms, sizeof(gh_sym) * r.nsyms);
+    Canon c;
+    if (build_canon(pl.syms, pl.nsyms, c)) return fail(GH_E_TABLE, who() + "device-built code: " + gh_last_error());
+    for (uint32_t k = 0; k < pl.nsyms; ++k) {
+      pl.code[c.sym[k]] = c.code[k];
+      pl.len[c.sym[k]] = c.len[k];
+    }
+    pl.bits = r.bits;
+    if (int rc = plan_sizes(&pl, force_version)) return fail(rc, who() + gh_last_error());
+    return GH_OK;
+  };
+  {
+    // a stream costs about a microsecond (8 KB cleared, build_canon's 256 steps): a thread per
+    // 256 streams, each taking a contiguous run; the error message is its thread's own
+    const int nt = (int)std::min<uint64_t>(std::min(std::max(std::thread::hardware_concurrency(), 1u), 32u),
+                                           std::max<uint64_t>(ns / 256, 1));
+    std::vector<int> rcs(nt, GH_OK);
+    std::vector<std::string> msgs(nt);
+    const auto work = [&](int t) {
+      const uint32_t i1 = (uint32_t)((uint64_t)ns * (t + 1) / nt);
+      for (uint32_t i = (uint32_t)((uint64_t)ns * t / nt); i < i1 && !rcs[t]; ++i)
+        if (int rc = plan_one(i)) {
+          rcs[t] = rc;
+          msgs[t] = gh_last_error();
+        }
+    };
+    if (nt <= 1) {
+      work(0);
+    } else {
+      std::vector<std::thread> th;
+      for (int t = 0; t < nt; ++t) th.emplace_back(work, t);
+      for (auto& t : th) t.join();
+    }
+    for (int t = 0; t < nt; ++t)
+      if (rcs[t]) return fail(rcs[t], msgs[t]);
+  }
+  b->plan_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  // 5. the output arenas, 6. one upload: the descriptors (the tables are on the device)
+  std::vector<EBatchDesc> d = ebatch_descs(b);
+  if (int rc = ebatch_layout(b, d)) return rc;
+  if (ns) GH_HIP(hipMemcpy(b->code.get(), d.data(), sizeof(EBatchDesc) * (uint64_t)ns, hipMemcpyHostToDevice));
+  if (int rc = ebatch_reserve_out(b)) return rc;
+  b->counts_on_device = ns != 0;
+  b->planned = true;
+  return GH_OK;
+}
+
+extern "C" int gh_batchenc_plan_times(gh_ebatch* b, float* hist_ms, float* code_ms, float* host_ms) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->planned) return fail(GH_E_STATE, "gh_batchenc_plan_times before a plan");
+  if (hist_ms) *hist_ms = b->hist_ms;
+  if (code_ms) *code_ms = b->code_ms;
+  if (host_ms) *host_ms = b->plan_host_ms;
   return GH_OK;
 }
 
@@ -1488,6 +1617,14 @@ extern "C" int gh_ebatch_plan_of(gh_ebatch* b, uint32_t stream, gh_encode_plan* 
   if (!b || !out) return fail(GH_E_ARG, "null argument");
   if (!b->planned) return fail(GH_E_STATE, "gh_ebatch_plan_of before a plan");
   if (stream >= b->nstreams) return fail(GH_E_ARG, "no such stream in the batch");
+  if (b->counts_on_device) {
+    // a device plan leaves the histograms where the code kernel read them: all of them back once
+    GH_HIP(hipSetDevice(b->q.device));
+    std::vector<uint64_t> counts(256ull * b->nstreams);
+    GH_HIP(hipMemcpy(counts.data(), b->counts.get(), 2048ull * b->nstreams, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < b->nstreams; ++i) std::memcpy(b->plans[i].count, &counts[256ull * i], sizeof(b->plans[i].count));
+    b->counts_on_device = false;
+  }
   *out = b->plans[stream];
   return GH_OK;
 }

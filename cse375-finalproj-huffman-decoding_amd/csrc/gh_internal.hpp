@@ -116,6 +116,9 @@ int ebatch_out_plan(const uint64_t* w, const uint64_t* g, uint32_t nstreams, EBa
 // Encoder plan from plan->n and plan->count[] (symbol order, package-merge lengths,
 // canonical codes, sizes, header version); shared by the host and GPU encoders.
 int plan_from_counts(gh_encode_plan* plan, int force_version);
+// Its last step, also gh_batchenc_plan_device's: w, g, version and file_bytes from plan->n,
+// plan->nsyms and plan->bits.  GH_E_ARG when force_version = 1 cannot hold the sizes.
+int plan_sizes(gh_encode_plan* plan, int force_version);
 // Writes the image header; returns its size.  out must hold file_bytes - payload.
 size_t encode_header(const gh_encode_plan* plan, uint8_t* out);
 // Writes a seek index image's header (40 bytes, any alignment); returns its size.

@@ -68,6 +68,7 @@ EXPORTED = (
     "gh_ebatch_create", "gh_ebatch_destroy", "gh_ebatch_load", "gh_ebatch_load_device", "gh_ebatch_plan",
     "gh_ebatch_plan_of", "gh_ebatch_encode", "gh_ebatch_wait", "gh_ebatch_sizes", "gh_ebatch_download",
     "gh_ebatch_items", "gh_ebatch_kernel_shape", "gh_ebatch_kernel_shapes",
+    "gh_package_merge_flat", "gh_batchenc_plan_device", "gh_batchenc_plan_times",
 )
 GH_EBATCH_UNIT_BYTES = 1024
 
@@ -196,6 +197,7 @@ def lib() -> ctypes.CDLL:
             "gh_encode_plan_make": ([P, U64, I, I, ctypes.POINTER(gh_encode_plan)], I),
             "gh_encode_write": ([P, ctypes.POINTER(gh_encode_plan), I, P, U64], I),
             "gh_package_merge": ([P, U32, P], I),
+            "gh_package_merge_flat": ([P, U32, P], I),
             "gh_generate": ([U64, ctypes.c_double, U64, U64, P, I], I),
             "gh_ctx_create": ([I, ctypes.POINTER(P)], I),
             "gh_ctx_destroy": ([P], I),
@@ -291,6 +293,8 @@ def lib() -> ctypes.CDLL:
             "gh_ebatch_load": ([P, P, P, U32], I),
             "gh_ebatch_load_device": ([P, ctypes.POINTER(gh_ebatch_item), U32, P], I),
             "gh_ebatch_plan": ([P, I, I], I),
+            "gh_batchenc_plan_device": ([P, I], I),
+            "gh_batchenc_plan_times": ([P, P, P, P], I),
             "gh_ebatch_plan_of": ([P, U32, ctypes.POINTER(gh_encode_plan)], I),
             "gh_ebatch_encode": ([P, P, I], I),
             "gh_ebatch_wait": ([P, ctypes.POINTER(gh_ebatch_report)], I),
@@ -692,6 +696,15 @@ def package_merge(sorted_counts: Sequence[int]) -> list:
     return out[: c.size].tolist()
 
 
+def package_merge_flat(sorted_counts: Sequence[int]) -> list:
+    """:func:`package_merge` by the level-by-level form the batched encoder's code kernel runs
+    (gh_package_merge_flat): the same lengths for every input."""
+    c = np.ascontiguousarray(sorted_counts, dtype=np.uint64)
+    out = np.zeros(max(1, c.size), dtype=np.uint8)
+    _check(lib().gh_package_merge_flat(_ptr(c), c.size, _ptr(out)))
+    return out[: c.size].tolist()
+
+
 def generate(seed: int, redundancy: float, n: int, offset: int = 0, threads: int = 0) -> np.ndarray:
     out = np.empty(n, dtype=np.uint8)
     _check(lib().gh_generate(seed, float(redundancy), offset, n, _ptr(out), threads))
@@ -1049,6 +1062,18 @@ class BatchEncoder(_Handle):
         """Every stream's histogram (one launch) and host plan (gh_ebatch_plan); synchronous."""
         _check(lib().gh_ebatch_plan(self._h, force_version, threads))
 
+    def plan_device(self, force_version: int = 0) -> None:
+        """:meth:`plan` with every stream's code built on the GPU (gh_batchenc_plan_device): no
+        host package-merge; the same plans and images.  Synchronous."""
+        _check(lib().gh_batchenc_plan_device(self._h, force_version))
+
+    def plan_times(self) -> dict:
+        """Times of the last plan of either kind in ms (gh_batchenc_plan_times): ``hist_ms`` and
+        ``code_ms`` by HIP events (``code_ms`` is 0 after :meth:`plan`), ``host_ms`` by wall clock."""
+        t = [ctypes.c_float(0) for _ in range(3)]
+        _check(lib().gh_batchenc_plan_times(self._h, *[ctypes.byref(x) for x in t]))
+        return {"hist_ms": t[0].value, "code_ms": t[1].value, "host_ms": t[2].value}
+
     def encode(self, hip_stream: int = 0, timed: bool = True) -> None:
         """Enqueue one encode of the planned batch and return."""
         _check(lib().gh_ebatch_encode(self._h, ctypes.c_void_p(hip_stream or None), int(timed)))
@@ -1091,11 +1116,15 @@ class BatchEncoder(_Handle):
         return _name(lib().gh_ebatch_kernel_shape, self._h)
 
 
-def encode_batch(datas, device: int = 0) -> list:
-    """Encode many inputs as one batch, each with its own code; returns their images in order."""
+def encode_batch(datas, device: int = 0, device_plan: bool = False) -> list:
+    """Encode many inputs as one batch, each with its own code; returns their images in order.
+    ``device_plan``: build the codes on the GPU (:meth:`BatchEncoder.plan_device`)."""
     with BatchEncoder(device) as b:
         b.load(datas)
-        b.plan()
+        if device_plan:
+            b.plan_device()
+        else:
+            b.plan()
         b.encode()
         b.wait()
         return b.download_all()

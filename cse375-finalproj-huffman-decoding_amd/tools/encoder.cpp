@@ -13,10 +13,11 @@
 // in K slices (gh_encode_sharded), slice i on the i-th of --devices (round robin; default:
 // the --gpu device); the same file, and the index then from the slices' own entries
 // (gh_encode_sharded_index: gh_ectx_index_slice per slice, no host pass over the input).
-// bin/encoder --batch LIST [--gpu D]
+// bin/encoder --batch LIST [--gpu D] [--device-plan]
 // --batch LIST (a text file, one input<TAB>output per line) encodes all inputs as one batch
 // on the GPU (gh_ebatch_*: each input with its own code, a fixed set of launches however
-// many inputs) and writes every output.
+// many inputs) and writes every output.  --device-plan builds the codes on the GPU too
+// (gh_batchenc_plan_device): the same files.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -44,10 +45,11 @@ static bool read_file(const char* path, std::vector<uint8_t>& out) {
   return ok;
 }
 
-// --batch LIST [--gpu D]: every line of the text file is `input<TAB>output` (as bin/decoder
+// --batch LIST [--gpu D] [--device-plan]: every line of the text file is `input<TAB>output` (as bin/decoder
 // --batch reads it); all inputs are encoded as one batch (gh_ebatch_*), each with its own
-// code, and every output file is written.
-static int batch_main(const char* list_file, int device) {
+// code, and every output file is written.  device_plan: gh_batchenc_plan_device instead of
+// gh_ebatch_plan.
+static int batch_main(const char* list_file, int device, bool device_plan) {
   std::vector<uint8_t> text;
   if (!read_file(list_file, text)) {
     std::fprintf(stderr, "encoder: Could not open batch list %s\n", list_file);
@@ -96,8 +98,10 @@ static int batch_main(const char* list_file, int device) {
   const double t0 = now_ms();
   if (gh_ebatch_load(b, ptr.data(), n.data(), (uint32_t)ns)) return die("batch load", b);
   const double t1 = now_ms();
-  if (gh_ebatch_plan(b, 0, 0)) return die("batch plan", b);
+  if (device_plan ? gh_batchenc_plan_device(b, 0) : gh_ebatch_plan(b, 0, 0)) return die("batch plan", b);
   const double t2 = now_ms();
+  float code_ms = 0;
+  if (gh_batchenc_plan_times(b, nullptr, &code_ms, nullptr)) return die("plan times", b);
   gh_ebatch_report rep{};
   if (gh_ebatch_encode(b, nullptr, 1) || gh_ebatch_wait(b, &rep)) return die("batch encode", b);
   const double t3 = now_ms();
@@ -117,22 +121,29 @@ static int batch_main(const char* list_file, int device) {
     }
   }
   gh_ebatch_destroy(b);
-  std::printf("Batch: %u streams, %llu bytes -> %llu bytes; load %.3f ms, plan %.3f ms (histogram %.3f, host %.3f), "
+  char code[48] = "";
+  if (device_plan) std::snprintf(code, sizeof(code), "code kernel %.3f, ", code_ms);
+  std::printf("Batch: %u streams, %llu bytes -> %llu bytes; load %.3f ms, plan %.3f ms (histogram %.3f, %shost %.3f), "
               "kernel %.3f ms, call %.3f ms\n",
               rep.nstreams, (unsigned long long)rep.in_bytes, (unsigned long long)rep.out_bytes, t1 - t0, t2 - t1,
-              rep.hist_ms, rep.plan_host_ms, rep.kernel_ms, t3 - t2);
+              rep.hist_ms, code, rep.plan_host_ms, rep.kernel_ms, t3 - t2);
   return 0;
 }
 
 int main(int argc, char** argv) {
   if (argc >= 3 && !std::strcmp(argv[1], "--batch")) {
     int device = 0;
-    if (argc == 5 && !std::strcmp(argv[3], "--gpu")) device = std::atoi(argv[4]);
-    else if (argc != 3) {
-      std::fprintf(stderr, "Usage: bin/encoder --batch LIST [--gpu D]   (LIST: one input<TAB>output per line)\n");
+    bool device_plan = false, bad = false;
+    for (int i = 3; i < argc; ++i) {
+      if (!std::strcmp(argv[i], "--gpu") && i + 1 < argc) device = std::atoi(argv[++i]);
+      else if (!std::strcmp(argv[i], "--device-plan")) device_plan = true;
+      else bad = true;
+    }
+    if (bad) {
+      std::fprintf(stderr, "Usage: bin/encoder --batch LIST [--gpu D] [--device-plan]   (LIST: one input<TAB>output per line)\n");
       return 2;
     }
-    return batch_main(argv[2], device);
+    return batch_main(argv[2], device, device_plan);
   }
   if (argc < 3) {
     std::printf("Usage: bin/encoder input output\n");

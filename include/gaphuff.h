@@ -159,6 +159,9 @@ int gh_slice_merge(void* image, uint64_t image_len, const gh_encode_plan* plan, 
  * (stable), restating encoder/src/package_merge.cpp:107-166; lengths written in
  * the same (ascending-count) order. */
 int gh_package_merge(const uint64_t* sorted_counts, uint32_t nsyms, uint8_t* lengths);
+/* gh_package_merge's lengths by the level-by-level form the GPU uses (same arguments, same
+ * result for every input; tests/test_pm_flat.py).  Needs no device. */
+int gh_package_merge_flat(const uint64_t* sorted_counts, uint32_t nsyms, uint8_t* lengths);
 
 /* ---- synthetic input (reference generate.cpp:32-47, seeded) ----------------- */
 /* Byte i: with probability `redundancy` 'A'+U{0..3}, else U{0..255}; counter-based
@@ -651,9 +654,10 @@ int gh_batch_kernel_shapes(char* buf, size_t cap);
  * reference counterpart.  A gh_ebatch is bound to one device and used from one host thread
  * at a time.
  *
- * Order of calls: load (host or device memory), plan, encode, wait, then sizes / download /
- * items.  GH_E_STATE: plan before a load; encode, plan_of, sizes or items before a plan; wait
- * or download before an encode.  A load invalidates the plan.
+ * Order of calls: load (host or device memory), plan (gh_ebatch_plan: codes built on the
+ * host, or gh_batchenc_plan_device: on the device; the same plans), encode, wait, then sizes /
+ * download / items.  GH_E_STATE: plan before a load; encode, plan_of, plan_times, sizes or
+ * items before a plan; wait or download before an encode.  A load invalidates the plan.
  *
  * Layout (host arithmetic, no device).  A work unit is GH_EBATCH_UNIT_BYTES consecutive
  * input bytes of one stream.  Input arena: stream i starts 16-byte aligned and owns
@@ -694,6 +698,23 @@ int gh_ebatch_load_device(gh_ebatch* b, const gh_ebatch_item* items, uint32_t ns
  * the sizing of the output arenas.  force_version as gh_encode_plan_make; GH_E_ARG names the
  * stream that cannot take v1. */
 int gh_ebatch_plan(gh_ebatch* b, int force_version, int threads);
+/* gh_ebatch_plan with the codes built on the device: histogram launch, code launch, one
+ * read-back of a 528-byte record per stream (bits, nsyms, the header's symbol list), the
+ * host's O(nsyms) build_canon per stream as a tripwire, the output layout, one upload of
+ * the 64-byte descriptors.  No host package-merge, no read-back of counts, no upload of
+ * tables.  Every plan, image and item is identical to gh_ebatch_plan's.  Synchronous.
+ * GH_E_TABLE names the stream whose device-built code is not a canonical code (never
+ * expected); GH_E_STATE and force_version as gh_ebatch_plan.  (The two gh_batchenc_* entry
+ * points work on a gh_ebatch; the gh_ebatch_* names are a closed set that
+ * tests/test_ebatch_layout.py pins, so later additions carry this prefix.) */
+int gh_batchenc_plan_device(gh_ebatch* b, int force_version);
+/* Times of the last plan of either kind (any pointer may be NULL): histogram kernel and code
+ * kernel by HIP events (code_ms = 0 after gh_ebatch_plan), host work by wall clock.
+ * GH_E_STATE before a plan. */
+int gh_batchenc_plan_times(gh_ebatch* b, float* hist_ms, float* code_ms, float* host_ms);
+/* Stream `stream`'s plan.  After gh_batchenc_plan_device the first call copies every stream's
+ * histogram back once (the plan itself does not need it): count[] is filled as after
+ * gh_ebatch_plan. */
 int gh_ebatch_plan_of(gh_ebatch* b, uint32_t stream, gh_encode_plan* out);
 /* Enqueue one encode of the planned batch on hip_stream (NULL = the batch's own stream) and
  * return.  timed != 0 brackets it with HIP events. */

@@ -13,6 +13,15 @@
 #       same generator) through one Encoder: plan + encode wall, and the encode's kernel_ms.
 # Every batch image is checked against the host encoder once, outside the timed region.
 # Usage: python scripts/bench_batch_encode.py [--m 256] [--big 4096] [--bytes 65536] [--out profiles/batch_encode.jsonl]
+#
+# --plan (DESIGN.md "Codes built on the device"): instead of the above, for M = 256 and
+# M = 4096 the two ways to plan one loaded batch, alternating rep by rep in one process:
+# plan() (histogram, read-back, host package-merges, upload) and plan_device() (histogram,
+# code kernel, record read-back, descriptor upload), each followed by encode() + wait().
+# Per way: wall time of the plan call, its parts from plan_times() (histogram and code kernel
+# by HIP events, host work by wall clock), and plan + encode wall; medians, minima and maxima
+# of 20 reps after 3 warm-up reps of each.  One JSON line per size.
+# Usage: python scripts/bench_batch_encode.py --plan [--m 256] [--big 4096] [--bytes 65536] [--out profiles/batch_encode_plan.jsonl]
 import json
 import os
 import sys
@@ -73,7 +82,65 @@ def batch_fields(prefix, t, m, nbytes):
             prefix + "_GBps_wall": round(m * nbytes / (float(np.median(total)) * 1e6), 3)}
 
 
+def time_plan(b, device):
+    """One rep of plan() or plan_device() + encode: plan wall, its parts, encode-to-wait wall."""
+    t0 = time.perf_counter()
+    if device:
+        b.plan_device()
+    else:
+        b.plan()
+    t1 = time.perf_counter()
+    b.encode()
+    b.wait()
+    t2 = time.perf_counter()
+    t = b.plan_times()
+    return {"plan": (t1 - t0) * 1e3, "hist": t["hist_ms"], "code": t["code_ms"], "host": t["host_ms"],
+            "total": (t2 - t0) * 1e3}
+
+
+def plan_main():
+    nbytes = opt("--bytes", 65536)
+    out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+    lines = []
+    for m in (opt("--m", 256), opt("--big", 4096)):
+        if not m:
+            continue
+        datas = [gh.generate(SEED + i, R, nbytes) for i in range(m)]
+        res = {"bench": "batch_encode_plan", "r": R, "stream_bytes": nbytes, "m": m, "reps": REPS, "warmup": WARMUP}
+        ok = True
+        with gh.BatchEncoder(0) as b:
+            b.load(datas)
+            for device in (False, True):
+                for _ in range(WARMUP):
+                    time_plan(b, device)
+                ok &= all(np.array_equal(b.download(i), gh.encode(datas[i])) for i in range(0, m, 1 if m <= 256 else 37))
+            t = {False: [], True: []}
+            for _ in range(REPS):  # alternating, one rep each
+                for device in (False, True):
+                    t[device].append(time_plan(b, device))
+            ok &= all(np.array_equal(b.download(i), gh.encode(datas[i])) for i in range(0, m, 1 if m <= 256 else 37))
+        for device, prefix in ((False, "host"), (True, "device")):
+            for k in ("plan", "hist", "code", "host", "total"):
+                xs = [x[k] for x in t[device]]
+                name = {"plan": "plan_wall_ms", "hist": "hist_ms", "code": "code_ms", "host": "plan_host_ms",
+                        "total": "plan_encode_wall_ms"}[k]
+                res[f"{prefix}_{name}"] = med(xs)
+                if k in ("plan", "total"):
+                    res[f"{prefix}_{name}_min"] = round(min(xs), 4)
+                    res[f"{prefix}_{name}_max"] = round(max(xs), 4)
+        res["device_plan_below_host_plan"] = bool(res["device_plan_wall_ms"] < res["host_plan_wall_ms"])
+        res["host_over_device_plan"] = round(res["host_plan_wall_ms"] / res["device_plan_wall_ms"], 2)
+        res["bitexact"] = bool(ok)
+        lines.append(json.dumps(res))
+        print(lines[-1], flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
+    if "--plan" in sys.argv:
+        return plan_main()
     m, big, nbytes = opt("--m", 256), opt("--big", 4096), opt("--bytes", 65536)
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
     res = {"bench": "batch_encode", "r": R, "stream_bytes": nbytes, "m": m, "m_big": big, "reps": REPS}
