@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "gh_batch_range.hpp"
 #include "gh_internal.hpp"
 #include "gh_pm_flat.hpp"
 
@@ -479,6 +480,39 @@ int gh::batch_plan(const uint64_t* n, const uint64_t* w, const uint64_t* g, uint
   out.gap_words = gap;
   out.nunits = units;
   out.out_bytes = bytes;
+  return GH_OK;
+}
+
+// Batched gather: the host plan (gaphuff.h, "batched gather"), the loop form of what the plan
+// kernels of gh_batch_gather.hip do with the same arithmetic (gh_batch_range.hpp).
+extern "C" int gh_batchdec_plan(const uint32_t* unit0, const uint64_t* unit_off, const uint64_t* n,
+                                const uint32_t* stream_status, uint32_t nstreams, const gh_brange* ranges,
+                                uint32_t nranges, gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces,
+                                uint64_t* out_bytes, uint32_t* bad_ranges) {
+  if (npieces) *npieces = 0;
+  if (out_bytes) *out_bytes = 0;
+  if (bad_ranges) *bad_ranges = 0;
+  if (!unit0 || !unit_off || !npieces || !out_bytes || !bad_ranges || (nstreams && !n) || (nranges && !ranges) ||
+      (cap && !pieces))
+    return fail(GH_E_ARG, "null argument");
+  uint64_t np = 0, dst = 0;
+  uint32_t bad = 0;
+  for (uint32_t i = 0; i < nranges; ++i) {
+    bool flagged;
+    const RangeLoc loc = br_locate(
+        unit0, unit_off, [&](uint32_t s) { return n[s]; },
+        [&](uint32_t s) { return stream_status ? stream_status[s] : 0u; }, nstreams, ranges[i], &flagged);
+    if (loc.count == GR_BAD_RANGE)
+      return fail(GH_E_ARG, "range " + std::to_string(i) + ": no such stream, or bytes outside [0, n] of its stream");
+    bad += flagged;
+    for (uint64_t j = 0; j < loc.count; ++j, ++np)
+      if (np < cap) pieces[np] = br_piece(unit0, unit_off, ranges[i], loc, j, dst);
+    dst += loc.len;
+  }
+  *npieces = np;
+  *out_bytes = dst;
+  *bad_ranges = bad;
+  if (np > cap) return fail(GH_E_SMALL, "piece buffer smaller than the plan");
   return GH_OK;
 }
 

@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "gh_batch_range.hpp"
 #include "gh_device.hpp"
 #include "gh_gather_range.hpp"
 #include "gh_hip.hpp"
@@ -49,6 +50,7 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 #include "gh_gather.hip"
 #include "gh_gather_plan.hip"
 #include "gh_batch.hip"
+#include "gh_batch_gather.hip"
 #include "gh_mtile.hip"
 
 }  // namespace gh
@@ -1556,6 +1558,24 @@ static BatchKernels batch_kernels() {
 }
 static BatchKernels batch_kernels_for(bool fb) { return fb ? batch_kernels<true>() : batch_kernels<false>(); }
 constexpr uint32_t BATCH_LAUNCHES = 3;  // count, scan, write
+constexpr uint32_t BATCH_INDEX_LAUNCHES = 2;   // count, scan (gh_batchdec_index)
+constexpr uint32_t BATCH_GATHER_LAUNCHES = 5;  // memset, locate, scan, emit, gather
+
+template <bool FB>
+static Kern bgather_kern() {
+  static const std::string n = kern_name("bgather<fb=%d>", (int)FB);
+  return {(const void*)gh_batch_gather_kernel<FB>, n.c_str()};
+}
+static Kern bgather_kern_for(bool fb) { return fb ? bgather_kern<true>() : bgather_kern<false>(); }
+
+// The batched gather's state in a gh_batch (gh_batchdec_*).  words: [0] status, [1] piece
+// count, [2..3] bytes, [4..5] pieces, [6] ranges on flagged streams; its own, not the
+// decode's flag words, which the next decode memsets.
+struct BatchGather {
+  DevBuf loc, slot, dst0, pieces, words, ranges;  // (ranges: gh_batchdec_gather's upload)
+  EventPair ev;
+  bool enqueued = false, timed = false;
+};
 
 struct gh_batch {
   DevBuf payload, gaps, tables, desc, unit0, syms, items;  // the loaded batch
@@ -1564,8 +1584,10 @@ struct gh_batch {
   DevBuf out;                                              // the batch's own output arena (on demand)
   BatchPlan plan;
   std::vector<uint64_t> n;
-  uint32_t nstreams = 0;
+  uint32_t nstreams = 0, launches = 0;  // launches: of the last decode or index
   bool loaded = false, fb = false, own_out = false;
+  bool indexed = false;  // seg_cnt / unit_off / status are (being) made by a decode or an index since the load
+  BatchGather g;
   BatchQueue q;  // (last: its destructor waits for the decode before the buffers above go)
 };
 
@@ -1589,7 +1611,7 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
   const uint32_t ns = (uint32_t)ss.size();
   GH_HIP(hipSetDevice(b->q.device));
   if (int rc = b->q.quiesce()) return rc;  // the previous batch's decode reads what is replaced
-  b->loaded = b->own_out = false;
+  b->loaded = b->own_out = b->indexed = b->g.enqueued = false;
   std::vector<uint64_t> n(ns), w(ns), g(ns);
   std::vector<BatchDesc> desc(ns);
   std::vector<gh_sym> syms;
@@ -1701,18 +1723,8 @@ extern "C" int gh_batch_load_device(gh_batch* b, const gh_batch_item* items, uin
   return batch_load(b, ss, true, hip_stream);
 }
 
-extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void* hip_stream, int timed) {
-  if (!b) return fail(GH_E_ARG, "null batch");
-  if (!b->loaded) return fail(GH_E_STATE, "gh_batch_decode before a load");
-  GH_HIP(hipSetDevice(b->q.device));
-  const bool own = d_dst == nullptr;
-  if (own) {
-    if (int rc = b->out.reserve(std::max<uint64_t>(b->plan.out_bytes, 16))) return rc;
-    d_dst = b->out.get();
-  } else {
-    if ((uintptr_t)d_dst & 15u) return fail(GH_E_ARG, "destination not 16-byte aligned");
-    if (dst_len < b->plan.out_bytes) return fail(GH_E_SMALL, "destination smaller than the batch's arena");
-  }
+// The kernels' view of the loaded batch; out: where a write or gather kernel stores.
+static BatchParams batch_params(const gh_batch* b, void* out) {
   BatchParams bp{};
   bp.desc = b->desc.get<BatchDesc>();
   bp.unit0 = b->unit0.get<uint32_t>();
@@ -1725,9 +1737,15 @@ extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void*
   bp.summary = b->flags.get<unsigned int>();
   bp.status = bp.summary + 4;
   bp.symbols = b->symbols.get<unsigned long long>();
-  bp.out = (uint8_t*)d_dst;
+  bp.out = (uint8_t*)out;
   bp.nstreams = b->nstreams;
   bp.nunits = (uint32_t)b->plan.nunits;
+  return bp;
+}
+
+// Enqueues the count and scan kernels and, with `write`, the write kernel into d_dst.
+static int batch_run(gh_batch* b, void* d_dst, void* hip_stream, int timed, bool write) {
+  BatchParams bp = batch_params(b, d_dst);
   // decodes of one batch share its scratch: they run in the order they were made
   hipStream_t st;
   if (int rc = b->q.begin(hip_stream, timed != 0, &st)) return rc;
@@ -1740,9 +1758,27 @@ extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void*
     void* args[] = {&bp};
     if (bp.nunits) GH_HIP(hipLaunchKernel(k.count, dim3(grid), dim3(BA_TB), args, 0, st));
     GH_HIP(hipLaunchKernel((const void*)gh_batch_scan_kernel, dim3(1), dim3(BA_SCAN_TB), args, 0, st));
-    if (bp.nunits) GH_HIP(hipLaunchKernel(k.write, dim3(grid), dim3(BA_TB), args, 0, st));
+    if (bp.nunits && write) GH_HIP(hipLaunchKernel(k.write, dim3(grid), dim3(BA_TB), args, 0, st));
   }
   if (int rc = b->q.end(st)) return rc;
+  b->indexed = true;
+  b->launches = write ? BATCH_LAUNCHES : BATCH_INDEX_LAUNCHES;
+  return GH_OK;
+}
+
+extern "C" int gh_batch_decode(gh_batch* b, void* d_dst, uint64_t dst_len, void* hip_stream, int timed) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_batch_decode before a load");
+  GH_HIP(hipSetDevice(b->q.device));
+  const bool own = d_dst == nullptr;
+  if (own) {
+    if (int rc = b->out.reserve(std::max<uint64_t>(b->plan.out_bytes, 16))) return rc;
+    d_dst = b->out.get();
+  } else {
+    if ((uintptr_t)d_dst & 15u) return fail(GH_E_ARG, "destination not 16-byte aligned");
+    if (dst_len < b->plan.out_bytes) return fail(GH_E_SMALL, "destination smaller than the batch's arena");
+  }
+  if (int rc = batch_run(b, d_dst, hip_stream, timed, true)) return rc;
   b->own_out = own;
   return GH_OK;
 }
@@ -1762,7 +1798,7 @@ extern "C" int gh_batch_wait(gh_batch* b, gh_batch_report* rep) {
     rep->bad_streams = sum[0];
     rep->status = sum[1];
     rep->kernel_ms = ms;
-    rep->launches = BATCH_LAUNCHES;
+    rep->launches = b->launches;
   }
   if (sum[0])
     return fail(GH_E_CORRUPT, std::to_string(sum[0]) + " stream(s) of the batch decoded to fewer than N symbols or met "
@@ -1819,6 +1855,169 @@ extern "C" int gh_batch_kernel_shape(gh_batch* b, char* buf, size_t cap) {
 
 extern "C" int gh_batch_kernel_shapes(char* buf, size_t cap) {
   return copy_name(std::string(batch_kernels_for(false).name) + "\n" + batch_kernels_for(true).name + "\n", buf, cap);
+}
+
+// ---- batched gather (gaphuff.h; kernels: gh_batch_gather.hip; arithmetic: gh_batch_range.hpp) ----
+extern "C" int gh_batchdec_index(gh_batch* b, void* hip_stream, int timed) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_batchdec_index before a load");
+  GH_HIP(hipSetDevice(b->q.device));
+  return batch_run(b, nullptr, hip_stream, timed, false);
+}
+
+// A member of the batch's queue without its timing events: it starts after the queue's last
+// run (decode, index or gather) and its end becomes the queue's `done`, so the next decode,
+// whose memset and count kernel rewrite what the gather reads, starts after it.
+extern "C" int gh_batchdec_gather_device(gh_batch* b, const gh_brange* d_ranges, uint32_t nranges, void* d_dst,
+                                         uint64_t dst_len, void* hip_stream, int timed) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded || !b->indexed)
+    return fail(GH_E_STATE, "gh_batchdec_gather_device without gh_batchdec_index or gh_batch_decode since the load");
+  if (nranges == 0) return GH_OK;
+  if (!d_ranges || !d_dst) return fail(GH_E_ARG, "null argument");
+  if (nranges > GH_GATHER_MAX_RANGES) return fail(GH_E_ARG, "gh_batchdec_gather_device: more than 2^24 ranges in one batch");
+  GH_HIP(hipSetDevice(b->q.device));
+  BatchGather& g = b->g;
+  // (the gather kernel counts pieces in 32 bits)
+  const uint64_t cap = std::min<uint64_t>(gh_gather_piece_bound(nranges, dst_len, 8), (1ull << 31) - 1);
+  if (int rc = g.ev.create()) return rc;
+  if (g.loc.capacity() < nranges * sizeof(RangeLoc) || g.pieces.capacity() < cap * sizeof(gh_gather_piece) || !g.words) {
+    if (b->q.enqueued) GH_HIP(hipEventSynchronize(b->q.done));  // the last gather in flight uses the old buffers
+    if (int rc = g.loc.reserve(nranges * sizeof(RangeLoc))) return rc;
+    if (int rc = g.slot.reserve(nranges * 4ull)) return rc;
+    if (int rc = g.dst0.reserve(nranges * 8ull)) return rc;
+    if (int rc = g.pieces.reserve(std::max<uint64_t>(cap * sizeof(gh_gather_piece), 16))) return rc;
+    if (int rc = g.words.reserve(32)) return rc;
+  }
+  unsigned int* words = g.words.get<unsigned int>();
+  GplanParams sp{};  // what gh_gplan_scan_kernel reads
+  sp.loc = g.loc.get<RangeLoc>();
+  sp.slot = g.slot.get<uint32_t>();
+  sp.dst0 = g.dst0.get<unsigned long long>();
+  sp.status = words;
+  sp.npieces = words + 1;
+  sp.totals = (unsigned long long*)(words + 2);
+  sp.cap = cap;
+  sp.dst_len = dst_len;
+  sp.nranges = nranges;
+  BatchGatherParams gp{};
+  gp.bp = batch_params(b, d_dst);
+  gp.pieces = g.pieces.get<gh_gather_piece>();
+  gp.d_npieces = sp.npieces;
+  BgplanParams pp{};
+  pp.ranges = d_ranges;
+  pp.desc = gp.bp.desc;
+  pp.unit0 = gp.bp.unit0;
+  pp.unit_off = gp.bp.unit_off;
+  pp.stream_status = gp.bp.status;
+  pp.loc = sp.loc;
+  pp.slot = sp.slot;
+  pp.dst0 = sp.dst0;
+  pp.pieces = g.pieces.get<gh_gather_piece>();
+  pp.status = sp.status;
+  pp.npieces = sp.npieces;
+  pp.bad_ranges = words + 6;
+  pp.cap = cap;
+  pp.nranges = nranges;
+  pp.nstreams = b->nstreams;
+  // the host knows only the bound: a wave per piece that could exist, at most what unit_grid allows
+  const uint32_t grid = unit_grid("GH_BATCH_GRID", cap, BA_TB / 64, b->q.num_cu);
+  const uint32_t grid_r = (uint32_t)ceil_div((uint64_t)nranges, (uint64_t)GP_TB);
+  const uint32_t grid_e = (uint32_t)std::clamp<uint64_t>(ceil_div(cap, (uint64_t)GP_TB), 1, 1024);
+  void* pa[1] = {&pp};
+  void* sa[1] = {&sp};
+  void* ga[1] = {&gp};
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)b->q.stream;
+  GH_HIP(hipStreamWaitEvent(st, b->q.done, 0));  // (indexed: the queue has a run)
+  if (timed) GH_HIP(hipEventRecord(g.ev.a, st));
+  GH_HIP(hipMemsetAsync(words, 0, 32, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_bgplan_locate_kernel, dim3(grid_r), dim3(GP_TB), pa, 0, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_gplan_scan_kernel, dim3(1), dim3(GP_SCAN_TB), sa, 0, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_bgplan_emit_kernel, dim3(grid_e), dim3(GP_TB), pa, 0, st));
+  // (a batch without units has no non-empty valid range: the plan kernels alone refuse or pass it)
+  if (gp.bp.nunits) GH_HIP(hipLaunchKernel(bgather_kern_for(b->fb).fn, dim3(grid), dim3(BA_TB), ga, 0, st));
+  GH_HIP(hipGetLastError());
+  if (timed) GH_HIP(hipEventRecord(g.ev.b, st));
+  GH_HIP(hipEventRecord(b->q.done, st));
+  g.enqueued = true;
+  g.timed = timed != 0;
+  return GH_OK;
+}
+
+// Waits for the queue's last run (the last gather or something after it) and reads the
+// gather's words.
+static int bgather_words(gh_batch* b, const char* who, unsigned int w[8]) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded || !b->g.enqueued) return fail(GH_E_STATE, std::string(who) + ": no gather since the load");
+  GH_HIP(hipSetDevice(b->q.device));
+  GH_HIP(hipEventSynchronize(b->q.done));
+  GH_HIP(hipMemcpy(w, b->g.words.get(), 32, hipMemcpyDeviceToHost));
+  return GH_OK;
+}
+
+extern "C" int gh_batchdec_gather_wait(gh_batch* b, gh_bgather_report* rep) {
+  if (rep) *rep = gh_bgather_report{};
+  unsigned int w[8] = {};
+  if (int rc = bgather_words(b, "gh_batchdec_gather_wait", w)) return rc;
+  float ms = 0;
+  if (b->g.timed)
+    if (int rc = b->g.ev.elapsed(&ms)) return rc;
+  const uint32_t status = w[0] | (w[6] ? (uint32_t)GH_ST_BADCODE : 0u);
+  if (rep) {
+    std::memcpy(&rep->out_bytes, w + 2, 8);
+    rep->npieces = w[1];
+    rep->bad_ranges = w[6];
+    rep->status = status;
+    rep->kernel_ms = ms;
+    rep->launches = BATCH_GATHER_LAUNCHES;
+  }
+  if (status & GH_ST_RANGE) return fail(GH_E_ARG, "batched gather: a range names no stream of the batch or bytes outside [0, n] of its stream");
+  if (status & GH_ST_DSTSMALL) return fail(GH_E_SMALL, "batched gather: destination smaller than the ranges' bytes");
+  if (status & GH_ST_PIECES) return fail(GH_E_CORRUPT, "batched gather: the plan exceeds the piece bound");
+  if (status & GH_ST_BADCODE)
+    return fail(GH_E_CORRUPT, std::to_string(w[6]) + " range(s) name a stream the index pass flagged (gh_batch_status "
+                                                     "names it); their bytes were left as they were");
+  return GH_OK;
+}
+
+extern "C" int gh_batchdec_gather(gh_batch* b, const gh_brange* ranges, uint32_t nranges, void* d_dst, uint64_t dst_len,
+                                  void* hip_stream, gh_bgather_report* rep) {
+  if (rep) *rep = gh_bgather_report{};
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded || !b->indexed)
+    return fail(GH_E_STATE, "gh_batchdec_gather without gh_batchdec_index or gh_batch_decode since the load");
+  if (nranges == 0) {
+    if (rep) rep->launches = BATCH_GATHER_LAUNCHES;
+    return GH_OK;
+  }
+  if (!ranges) return fail(GH_E_ARG, "null argument");
+  GH_HIP(hipSetDevice(b->q.device));
+  if (b->g.enqueued) GH_HIP(hipEventSynchronize(b->q.done));  // (the last gather may still read the old upload)
+  if (int rc = upload_at_least(b->g.ranges, ranges, sizeof(gh_brange) * (uint64_t)nranges)) return rc;
+  if (int rc = gh_batchdec_gather_device(b, b->g.ranges.get<gh_brange>(), nranges, d_dst, dst_len, hip_stream, 1)) return rc;
+  return gh_batchdec_gather_wait(b, rep);
+}
+
+extern "C" int gh_batchdec_gather_pieces(gh_batch* b, gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces) {
+  if (!npieces || (cap && !pieces)) return fail(GH_E_ARG, "null argument");
+  *npieces = 0;
+  unsigned int w[8] = {};
+  if (int rc = bgather_words(b, "gh_batchdec_gather_pieces", w)) return rc;
+  const uint64_t np = w[1];
+  *npieces = np;
+  if (np > cap) return fail(GH_E_SMALL, "piece buffer smaller than the plan");
+  if (np) GH_HIP(hipMemcpy(pieces, b->g.pieces.get(), np * sizeof(gh_gather_piece), hipMemcpyDeviceToHost));
+  return GH_OK;
+}
+
+extern "C" int gh_batchdec_kernel_shape(gh_batch* b, char* buf, size_t cap) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_batchdec_kernel_shape before a load");
+  return copy_name(b->plan.nunits ? bgather_kern_for(b->fb).name : "", buf, cap);
+}
+
+extern "C" int gh_batchdec_kernel_shapes(char* buf, size_t cap) {
+  return copy_name(std::string(bgather_kern_for(false).name) + "\n" + bgather_kern_for(true).name + "\n", buf, cap);
 }
 
 // Decode time of a set of shards: decodes on one device run in turn (DevChain), so a

@@ -69,6 +69,8 @@ EXPORTED = (
     "gh_ebatch_plan_of", "gh_ebatch_encode", "gh_ebatch_wait", "gh_ebatch_sizes", "gh_ebatch_download",
     "gh_ebatch_items", "gh_ebatch_kernel_shape", "gh_ebatch_kernel_shapes",
     "gh_package_merge_flat", "gh_batchenc_plan_device", "gh_batchenc_plan_times",
+    "gh_batchdec_index", "gh_batchdec_gather_device", "gh_batchdec_gather_wait", "gh_batchdec_gather",
+    "gh_batchdec_gather_pieces", "gh_batchdec_plan", "gh_batchdec_kernel_shape", "gh_batchdec_kernel_shapes",
 )
 GH_EBATCH_UNIT_BYTES = 1024
 
@@ -153,6 +155,15 @@ class gh_batch_item(ctypes.Structure):
 
 class gh_batch_report(ctypes.Structure):
     _fields_ = [("out_bytes", ctypes.c_uint64), ("nstreams", ctypes.c_uint32), ("bad_streams", ctypes.c_uint32),
+                ("status", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
+
+
+class gh_brange(ctypes.Structure):
+    _fields_ = [("stream", ctypes.c_uint64), ("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64)]
+
+
+class gh_bgather_report(ctypes.Structure):
+    _fields_ = [("out_bytes", ctypes.c_uint64), ("npieces", ctypes.c_uint64), ("bad_ranges", ctypes.c_uint32),
                 ("status", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
 
 
@@ -288,6 +299,15 @@ def lib() -> ctypes.CDLL:
             "gh_batch_download": ([P, U32, P, U64], I),
             "gh_batch_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_batch_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_batchdec_index": ([P, P, I], I),
+            "gh_batchdec_gather_device": ([P, P, U32, P, U64, P, I], I),
+            "gh_batchdec_gather_wait": ([P, ctypes.POINTER(gh_bgather_report)], I),
+            "gh_batchdec_gather": ([P, P, U32, P, U64, P, ctypes.POINTER(gh_bgather_report)], I),
+            "gh_batchdec_gather_pieces": ([P, P, U64, ctypes.POINTER(U64)], I),
+            "gh_batchdec_plan": ([P, P, P, P, U32, P, U32, P, U64, ctypes.POINTER(U64), ctypes.POINTER(U64),
+                                  ctypes.POINTER(U32)], I),
+            "gh_batchdec_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_batchdec_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_ebatch_create": ([I, ctypes.POINTER(P)], I),
             "gh_ebatch_destroy": ([P], I),
             "gh_ebatch_load": ([P, P, P, U32], I),
@@ -940,6 +960,47 @@ def batch_kernel_shapes() -> list:
     return _name(lib().gh_batch_kernel_shapes, cap=1 << 10).split()
 
 
+def batchdec_kernel_shapes() -> list:
+    """Every kernel name a batched gather can pick (gh_batchdec_kernel_shapes); needs no device."""
+    return _name(lib().gh_batchdec_kernel_shapes, cap=1 << 10).split()
+
+
+def _branges(ranges) -> np.ndarray:
+    """(stream, lo, hi) triples as the C array of gh_brange: a contiguous (n, 3) uint64 array."""
+    if not isinstance(ranges, np.ndarray):
+        ranges = list(ranges)
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 3))
+    if r.shape[0] >= 1 << 32:
+        raise GapHuffError(-1, "2^32 or more ranges in one batch")
+    return r
+
+
+def batch_gather_plan(unit0, unit_off, n, status, ranges):
+    """The batched gather's plan from host arrays (gh_batchdec_plan; needs no device):
+    ``(pieces, out_bytes, bad_ranges)`` with the pieces as a :data:`PIECE_DTYPE` record array
+    whose ``block`` is the global unit index.  ``unit0``: ``nstreams + 1`` prefix of the
+    streams' unit counts; ``unit_off``: ``unit0[-1] + 1`` exclusive scan of the codewords per
+    unit; ``n``: the streams' bytes; ``status``: their status words, or None."""
+    u0 = np.ascontiguousarray(unit0, dtype=np.uint32)
+    uo = np.ascontiguousarray(unit_off, dtype=np.uint64)
+    nn = np.ascontiguousarray(n, dtype=np.uint64)
+    st = None if status is None else np.ascontiguousarray(status, dtype=np.uint32)
+    r = _branges(ranges)
+    ns = nn.size
+    if u0.size != ns + 1 or uo.size != int(u0[-1]) + 1 or (st is not None and st.size != ns):
+        raise GapHuffError(-1, "batch_gather_plan: array sizes disagree")
+    np_, total, bad = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+    args = (_ptr(u0), _ptr(uo), _ptr(nn) if ns else None, _ptr(st) if st is not None and ns else None, ns,
+            _ptr(r) if r.size else None, r.shape[0])
+    tail = (ctypes.byref(np_), ctypes.byref(total), ctypes.byref(bad))
+    rc = lib().gh_batchdec_plan(*args, None, 0, *tail)
+    if rc not in (GH_OK, -9):
+        _check(rc)
+    pieces = np.zeros(int(np_.value), dtype=PIECE_DTYPE)
+    _check(lib().gh_batchdec_plan(*args, _ptr(pieces) if pieces.size else None, pieces.size, *tail))
+    return pieces, int(total.value), int(bad.value)
+
+
 class BatchDecoder(_Handle):
     """One gh_batch: many independent streams resident on one GPU, decoded by one fixed set
     of kernel launches per batch."""
@@ -947,6 +1008,7 @@ class BatchDecoder(_Handle):
     def __init__(self, device: int = 0):
         super().__init__(lib().gh_batch_create, lib().gh_batch_destroy, device)
         self.ns: list = []  # output bytes of every loaded stream
+        self._indexed = False  # an index() or decode() since the load
 
     def load(self, images_or_streams) -> None:
         """Load a batch from host memory: compressed.huff images (bytes / np.uint8) or parsed
@@ -955,6 +1017,7 @@ class BatchDecoder(_Handle):
         arr = (gh_stream * max(1, len(streams)))()
         for i, s in enumerate(streams):
             arr[i] = s.c
+        self._indexed = False
         _check(lib().gh_batch_load(self._h, arr, len(streams)))
         self.ns = [s.n for s in streams]
 
@@ -969,6 +1032,7 @@ class BatchDecoder(_Handle):
             arr[i].syms, arr[i].nsyms = s.c.syms, s.c.nsyms
             arr[i].n, arr[i].w, arr[i].g = s.c.n, s.c.w, s.c.g
             arr[i].d_payload, arr[i].d_gap_words = pay or None, gap or None
+        self._indexed = False
         _check(lib().gh_batch_load_device(self._h, arr, len(items), ctypes.c_void_p(hip_stream or None)))
         self.ns = [s.n for s, _, _ in items]
 
@@ -977,6 +1041,69 @@ class BatchDecoder(_Handle):
         aligned, ``dst_len`` bytes), or into the batch's own arena, and return."""
         _check(lib().gh_batch_decode(self._h, ctypes.c_void_p(dst_ptr or None), dst_len,
                                      ctypes.c_void_p(hip_stream or None), int(timed)))
+        self._indexed = True
+
+    def index(self, hip_stream: int = 0, timed: bool = True) -> None:
+        """Enqueue the count and scan kernels alone (gh_batchdec_index): the seek index the
+        gathers read, and the per-stream status :meth:`wait` and :meth:`status` report,
+        without writing an output byte."""
+        _check(lib().gh_batchdec_index(self._h, ctypes.c_void_p(hip_stream or None), int(timed)))
+        self._indexed = True
+
+    def gather(self, ranges) -> list:
+        """The bytes of each ``(stream, lo, hi)`` range of the loaded batch, as a list of
+        np.uint8 arrays in request order (gh_batchdec_gather).  ``ranges``: an iterable of
+        triples or an int64 / uint64 ``[n, 3]`` array.  Runs :meth:`index` first when the batch
+        is neither indexed nor decoded."""
+        r = _branges(ranges)
+        if not self._indexed:
+            self.index()
+        lens = (r[:, 2] - r[:, 1]).astype(np.int64) if r.size and (r[:, 2] >= r[:, 1]).all() else np.zeros(0, np.int64)
+        total = int(lens.sum())
+        out = np.zeros(total, dtype=np.uint8)
+        with DeviceBuffer(max(total, 16), self.device) as buf:
+            rep = gh_bgather_report()
+            rc = lib().gh_batchdec_gather(self._h, _ptr(r) if r.size else None, r.shape[0], buf.ptr, total, None,
+                                          ctypes.byref(rep))
+            if rc != GH_OK:
+                e = GapHuffError(rc, lib().gh_last_error().decode(errors="replace"))
+                e.report = rep
+                raise e
+            if total:
+                buf.download(out)
+        ends = np.cumsum(lens)
+        return [out[int(e - l): int(e)] for e, l in zip(ends, lens)]
+
+    def gather_device(self, ranges_ptr: int, nranges: int, dst_ptr: int, dst_len: int, hip_stream: int = 0,
+                      timed: bool = True) -> None:
+        """Enqueue the gather of ``nranges`` (stream, lo, hi) triples held in device memory at
+        ``ranges_ptr`` (a contiguous int64 / uint64 [n, 3] array) into the ``dst_len`` device
+        bytes at ``dst_ptr`` and return without waiting (gh_batchdec_gather_device).  What only
+        the device finds is raised by :meth:`gather_wait`."""
+        _check(lib().gh_batchdec_gather_device(self._h, ctypes.c_void_p(ranges_ptr or None), nranges,
+                                               ctypes.c_void_p(dst_ptr or None), dst_len,
+                                               ctypes.c_void_p(hip_stream or None), int(timed)))
+
+    def gather_wait(self) -> gh_bgather_report:
+        """Wait for the last gather and return its report; raises :class:`GapHuffError` (with
+        the report as ``.report``) on a device-side refusal or a range on a flagged stream."""
+        return self._wait(lib().gh_batchdec_gather_wait, gh_bgather_report())
+
+    def gather_pieces(self) -> np.ndarray:
+        """The pieces of the last gather as a :data:`PIECE_DTYPE` record array
+        (gh_batchdec_gather_pieces); ``block`` is the global unit index."""
+        n = ctypes.c_uint64()
+        rc = lib().gh_batchdec_gather_pieces(self._h, None, 0, ctypes.byref(n))
+        if rc not in (GH_OK, -9):
+            _check(rc)
+        pieces = np.zeros(int(n.value), dtype=PIECE_DTYPE)
+        _check(lib().gh_batchdec_gather_pieces(self._h, _ptr(pieces) if pieces.size else None, pieces.size,
+                                               ctypes.byref(n)))
+        return pieces
+
+    def gather_kernel_shape(self) -> str:
+        """Name of the gather kernel instantiation for the loaded batch (gh_batchdec_kernel_shape)."""
+        return _name(lib().gh_batchdec_kernel_shape, self._h)
 
     def wait(self) -> gh_batch_report:
         """Wait for the last :meth:`decode` and return its report; raises
@@ -1023,6 +1150,14 @@ def decode_batch(images, device: int = 0) -> list:
         b.decode()
         b.wait()
         return b.download_all()
+
+
+def decode_batch_ranges(images, ranges, device: int = 0) -> list:
+    """The bytes of each ``(stream, lo, hi)`` range of many compressed.huff images loaded as
+    one batch: indexed, never decoded in full (BatchDecoder.gather)."""
+    with BatchDecoder(device) as b:
+        b.load(images)
+        return b.gather(ranges)
 
 
 # --------------------------------------------------------------------------- batched encode

@@ -1,9 +1,13 @@
 // bin/decoder <compressed.huff | raw container> <output> [--gpus N] [--shards S] [--reps R] [--json]
 //             [--verify FILE] [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]
 //             [--index FILE --ranges FILE]
-// bin/decoder --batch LIST
+// bin/decoder --batch LIST [--ranges FILE OUT]
 // --batch LIST (a text file, one input<TAB>output per line) decodes all inputs as one batch
 // (gh_batch_*: one fixed set of launches however many streams) and writes every output.
+// --batch LIST --ranges FILE OUT (FILE: one `STREAM LO:HI` per line, STREAM the 0-based line
+// of LIST, blank lines not counted) indexes the batch without decoding it and gathers only the
+// named byte ranges (gh_batchdec_*); their concatenation in file order goes to OUT and the
+// per-input outputs of LIST are not written (its lines may then omit <TAB>output).
 // --shards S (default: one per GPU) splits the gap segments into S shards, shard k on
 // device k mod N, each streaming its own payload range and writing at its offset.
 // A raw-stream container (bin/encoder --raw, GH_RAW_MAGIC) is decoded by the
@@ -145,7 +149,8 @@ static int gather_main(const char* input, const char* output, const char* index_
 // --batch LIST: every line of the text file is `input<TAB>output`; all inputs are decoded as
 // one batch (gh_batch_*) and every output file is written.  A corrupt stream: exit code 1,
 // its line named, no output written for it.
-static int batch_main(const char* list_file) {
+// With ranges_file / range_out: --batch LIST --ranges FILE OUT, the byte ranges alone.
+static int batch_main(const char* list_file, const char* ranges_file = nullptr, const char* range_out = nullptr) {
   std::vector<uint8_t> text;
   if (!read_file(list_file, text)) { std::fprintf(stderr, "decoder: Could not open batch list %s\n", list_file); return 1; }
   std::vector<std::string> in, out;
@@ -162,6 +167,12 @@ static int batch_main(const char* list_file) {
       if (!ln.empty() && ln.back() == '\r') ln.pop_back();
       if (ln.empty()) continue;
       const size_t tab = ln.find('\t');
+      if (ranges_file && tab == std::string::npos) {  // (no per-input output is written)
+        in.push_back(ln);
+        out.push_back("");
+        line_of.push_back(line);
+        continue;
+      }
       if (tab == std::string::npos || tab == 0 || tab + 1 == ln.size()) {
         std::fprintf(stderr, "decoder: %s: line %zu: expected input<TAB>output\n", list_file, line);
         return 1;
@@ -191,6 +202,78 @@ static int batch_main(const char* list_file) {
   const double t0 = now_ms();
   if ((rc = gh_batch_load(b, streams.data(), (uint32_t)ns))) { gh_batch_destroy(b); return die("batch load", rc); }
   const double t1 = now_ms();
+  if (ranges_file) {
+    std::vector<gh_brange> ranges;
+    std::vector<uint8_t> rtext;
+    if (!read_file(ranges_file, rtext)) { gh_batch_destroy(b); std::fprintf(stderr, "decoder: Could not open ranges file %s\n", ranges_file); return 1; }
+    rtext.push_back(0);
+    uint64_t total = 0;
+    for (const char* p = (const char*)rtext.data(); *p;) {
+      while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') ++p;
+      if (!*p) break;
+      char* end = nullptr;
+      gh_brange r{};
+      bool ok = *p >= '0' && *p <= '9';
+      if (ok) r.stream = std::strtoull(p, &end, 10);
+      ok = ok && (*end == ' ' || *end == '\t');
+      if (ok) {
+        p = end;
+        while (*p == ' ' || *p == '\t') ++p;
+        ok = *p >= '0' && *p <= '9';
+      }
+      if (ok) r.lo = std::strtoull(p, &end, 10);
+      ok = ok && *end == ':' && end[1] >= '0' && end[1] <= '9';
+      if (ok) {
+        p = end + 1;
+        r.hi = std::strtoull(p, &end, 10);
+        ok = *end == 0 || *end == ' ' || *end == '\t' || *end == '\r' || *end == '\n';
+      }
+      if (!ok || ranges.size() >= GH_GATHER_MAX_RANGES) {
+        gh_batch_destroy(b);
+        std::fprintf(stderr, "decoder: %s: range %zu: expected STREAM LO:HI\n", ranges_file, ranges.size() + 1);
+        return 1;
+      }
+      if (r.stream >= ns || r.lo > r.hi || r.hi > streams[r.stream].n) {
+        gh_batch_destroy(b);
+        std::fprintf(stderr, "decoder: %s: range %zu: no such stream, or bytes outside [0, N] of it\n", ranges_file, ranges.size() + 1);
+        return 1;
+      }
+      total += r.hi - r.lo;
+      ranges.push_back(r);
+      p = end;
+    }
+    void* d_dst = nullptr;
+    if ((rc = gh_dev_alloc(0, total ? total : 16, &d_dst))) { gh_batch_destroy(b); return die("device allocation", rc); }
+    gh_bgather_report grep{};
+    std::vector<uint8_t> bytes((size_t)total);
+    if ((rc = gh_batchdec_index(b, nullptr, 1)) == GH_OK)
+      rc = gh_batchdec_gather(b, ranges.data(), (uint32_t)ranges.size(), d_dst, total, nullptr, &grep);
+    const double t2 = now_ms();
+    if (rc == GH_E_CORRUPT && grep.bad_ranges) {
+      std::vector<uint32_t> status(ns, 0);
+      if (gh_batch_status(b, status.data(), nullptr, (uint32_t)ns) == GH_OK)
+        for (size_t i = 0; i < ns; ++i)
+          if (status[i])
+            std::fprintf(stderr, "decoder: %s: line %zu: %s: corrupt stream (status 0x%x)\n", list_file, line_of[i],
+                         in[i].c_str(), status[i]);
+    }
+    if (rc == GH_OK && total) rc = gh_dev_copy(bytes.data(), d_dst, total);
+    if (rc) {
+      const int r = die("batched gather", rc);
+      gh_dev_free(d_dst);
+      gh_batch_destroy(b);
+      return r;
+    }
+    gh_dev_free(d_dst);
+    gh_batch_destroy(b);
+    FILE* f = std::fopen(range_out, "wb");
+    bool okw = f && std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (f) okw = std::fclose(f) == 0 && okw;
+    if (!okw) { std::fprintf(stderr, "decoder: cannot write %s\n", range_out); return 1; }
+    std::printf("Batch gather: %zu streams, %zu ranges, %llu pieces, %llu bytes; load %.3f ms, kernel %.3f ms, call %.3f ms\n",
+                ns, ranges.size(), (unsigned long long)grep.npieces, (unsigned long long)total, t1 - t0, grep.kernel_ms, t2 - t1);
+    return 0;
+  }
   gh_batch_report rep{};
   if ((rc = gh_batch_decode(b, nullptr, 0, nullptr, 1))) { gh_batch_destroy(b); return die("batch decode", rc); }
   rc = gh_batch_wait(b, &rep);
@@ -224,12 +307,15 @@ static int batch_main(const char* list_file) {
 
 int main(int argc, char** argv) {
   if (argc == 3 && !std::strcmp(argv[1], "--batch")) return batch_main(argv[2]);
+  if (argc == 6 && !std::strcmp(argv[1], "--batch") && !std::strcmp(argv[3], "--ranges"))
+    return batch_main(argv[2], argv[4], argv[5]);
   if (argc < 3) {
     std::fprintf(stderr,
                  "Usage: bin/decoder input output [--gpus N] [--shards S] [--reps R] [--json] [--verify FILE]\n"
                  "       [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]\n"
                  "       [--index FILE --ranges FILE]\n"
-                 "       bin/decoder --batch LIST   (LIST: one input<TAB>output per line)\n");
+                 "       bin/decoder --batch LIST   (LIST: one input<TAB>output per line)\n"
+                 "       bin/decoder --batch LIST --ranges FILE OUT   (FILE: one STREAM LO:HI per line)\n");
     return 2;
   }
   int ngpus = 1, reps = 1, nshards = 0;

@@ -645,6 +645,84 @@ int gh_batch_download(gh_batch* b, uint32_t stream, uint8_t* dst, uint64_t nbyte
 int gh_batch_kernel_shape(gh_batch* b, char* buf, size_t cap);
 int gh_batch_kernel_shapes(char* buf, size_t cap);
 
+/* ---- batched gather: byte ranges of many streams in a fixed launch count --------------- */
+/* The random access of gh_ctx_gather_device for a resident batch: byte ranges (stream, lo, hi)
+ * of its streams, decoded without decoding the rest.  No sidecar and no per-stream index
+ * build: a decode's count and scan kernels leave one byte per segment (the codewords that
+ * start in it) and the exclusive scan of the codewords per 256-segment unit on the device,
+ * which is a seek index of stride 2^8 for every stream of the batch; gh_batchdec_index runs
+ * those two kernels alone.  The plan is cut by three kernels and one gather kernel decodes
+ * the pieces, each by one wave: a constant launch count however many ranges there are.  No
+ * reference counterpart.
+ *
+ * Output layout: range i's bytes start at sum_{j<i} (hi_j - lo_j) of d_dst, tight and in
+ * request order, as gh_ctx_gather's.  Ranges may be empty, overlap, repeat and name the
+ * streams in any order (a wave reloads its tables when the stream changes from one piece to
+ * the next: ranges sorted by stream cost one table load per stream and wave).
+ * A piece is a gh_gather_piece whose `block` is the GLOBAL unit index of the batch and
+ * whose a, b count from that unit's first symbol. */
+typedef struct gh_brange { uint64_t stream, lo, hi; } gh_brange;   /* a contiguous int64[n,3] tensor */
+typedef struct gh_bgather_report {
+  uint64_t out_bytes;   /* sum of hi - lo over the batch's valid ranges                      */
+  uint64_t npieces;     /* pieces the device plan cut (0: refused)                           */
+  uint32_t bad_ranges;  /* ranges that name a stream flagged by the index pass               */
+  uint32_t status;      /* GH_ST_RANGE | GH_ST_DSTSMALL | GH_ST_PIECES | GH_ST_BADCODE       */
+  float kernel_ms;      /* HIP events: plan kernels + gather kernel                          */
+  uint32_t launches;    /* kernels + memsets of one gather: a constant                       */
+} gh_bgather_report;
+/* Enqueue the count and scan kernels of the loaded batch, and nothing else: no write kernel,
+ * no output arena.  Afterwards the per-segment counts, the unit scan, the per-stream status
+ * words and symbol counts are valid.  It counts as a decode for gh_batch_wait and
+ * gh_batch_status (which then report what the count pass found: a batch can be validated
+ * without writing a byte), not for gh_batch_download.  A full gh_batch_decode leaves the same
+ * state.  A load drops it.  GH_E_STATE before a load. */
+int gh_batchdec_index(gh_batch* b, void* hip_stream, int timed);
+/* Enqueue the gather of d_ranges[0 .. nranges) (device memory) into d_dst (device memory,
+ * dst_len bytes) on hip_stream (NULL = the batch's stream), and return.  It runs after every
+ * earlier decode, index or gather of the batch, whatever their streams.  d_ranges and d_dst
+ * must stay untouched until the wait.  The call blocks only to grow a batch-owned buffer (the
+ * piece buffer holds min(gh_gather_piece_bound(nranges, dst_len, 8), 2^31 - 1) pieces); a
+ * repeated call with the same or a smaller nranges and dst_len allocates nothing.
+ * timed != 0 brackets the kernels with HIP events.  nranges = 0: GH_OK, nothing is launched.
+ * GH_E_STATE before an index or decode since the load; GH_E_ARG: a null pointer, more than
+ * GH_GATHER_MAX_RANGES ranges. */
+int gh_batchdec_gather_device(gh_batch* b, const gh_brange* d_ranges, uint32_t nranges,
+                              void* d_dst, uint64_t dst_len, void* hip_stream, int timed);
+/* Wait for the batch's last gather and report it (rep may be NULL; it is filled before an
+ * error is returned).  GH_E_ARG: some range had stream >= nstreams, lo > hi or hi > n_stream
+ * (GH_ST_RANGE); GH_E_SMALL: the batch's bytes exceed dst_len (GH_ST_DSTSMALL); GH_E_CORRUPT:
+ * the plan would exceed the piece buffer (GH_ST_PIECES); after these three not one byte of
+ * d_dst has been written.  GH_E_CORRUPT also when a range names a stream whose status word is
+ * non-zero (GH_ST_BADCODE in the report): such a range keeps its hi - lo bytes in the layout,
+ * gets no pieces and leaves its bytes as they were, every other range is gathered exactly,
+ * and bad_ranges counts them.  GH_E_STATE when no gather has been enqueued since the load. */
+int gh_batchdec_gather_wait(gh_batch* b, gh_bgather_report* rep);
+/* The same with the ranges in host memory: uploads them, then gather_device (timed) and
+ * gather_wait.  Synchronous.  rep may be NULL. */
+int gh_batchdec_gather(gh_batch* b, const gh_brange* ranges /* host */, uint32_t nranges,
+                       void* d_dst, uint64_t dst_len, void* hip_stream, gh_bgather_report* rep);
+/* Pieces of the last gather, copied to host memory (tests, diagnosis); waits for it.
+ * *npieces is always written; GH_E_SMALL when cap is smaller. */
+int gh_batchdec_gather_pieces(gh_batch* b, gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces);
+/* The device plan from host arrays, the same pieces in the same order: unit0[0 .. nstreams]
+ * the prefix of the streams' unit counts, unit_off[0 .. unit0[nstreams]] the exclusive scan
+ * of the codewords per unit, n[s] the streams' output bytes, stream_status[s] their status
+ * words (NULL: none is flagged).  *npieces / *out_bytes / *bad_ranges are always written (a
+ * first call with cap = 0 sizes the buffer; GH_E_SMALL then).  GH_E_ARG: stream >= nstreams,
+ * lo > hi or hi > n[stream] (the counts are then 0).  A range on a flagged stream adds its
+ * bytes to *out_bytes, counts in *bad_ranges and gives no pieces; the return stays GH_OK.
+ * No device. */
+int gh_batchdec_plan(const uint32_t* unit0, const uint64_t* unit_off, const uint64_t* n,
+                     const uint32_t* stream_status, uint32_t nstreams, const gh_brange* ranges,
+                     uint32_t nranges, gh_gather_piece* pieces, uint64_t cap, uint64_t* npieces,
+                     uint64_t* out_bytes, uint32_t* bad_ranges);
+/* The gather kernel is one of two instantiations, "bgather<fb=0>" and "bgather<fb=1>", picked
+ * as the batch's decode kernels are.  gh_batchdec_kernel_shape: the name for the loaded batch
+ * (empty for a batch without segments); GH_E_STATE before a load.  gh_batchdec_kernel_shapes:
+ * both names, one per line; needs no device.  Neither is part of another shape list. */
+int gh_batchdec_kernel_shape(gh_batch* b, char* buf, size_t cap);
+int gh_batchdec_kernel_shapes(char* buf, size_t cap);
+
 /* ---- batched encode: many independent inputs, a fixed launch count per batch ---------- */
 /* The other half of the batched decode: N independent inputs, each encoded with its own
  * canonical code into its own compressed.huff image, by a number of launches that does not
