@@ -23,6 +23,7 @@
 #include "gh_batch_range.hpp"
 #include "gh_internal.hpp"
 #include "gh_pm_flat.hpp"
+#include "gh_raw_trans.hpp"
 
 namespace gh {
 
@@ -513,6 +514,55 @@ extern "C" int gh_batchdec_plan(const uint32_t* unit0, const uint64_t* unit_off,
   *out_bytes = dst;
   *bad_ranges = bad;
   if (np > cap) return fail(GH_E_SMALL, "piece buffer smaller than the plan");
+  return GH_OK;
+}
+
+// Batched gap-less load: the host twin of gh_batch_raw.hip (gaphuff.h, "batched gap-less
+// decode"), cut as the kernels are: T_j of every segment (gh_raw_trans.hpp), each unit's
+// aggregate, the units' entries chained, then every unit's nibbles from its entry.
+extern "C" int gh_batchraw_gaps_host(const gh_sym* syms, uint32_t nsyms, const uint32_t* words, uint64_t w,
+                                     uint32_t* gap_words, uint64_t cap) {
+  if ((nsyms && !syms) || (w && !words)) return fail(GH_E_ARG, "null argument");
+  Canon c;
+  if (int rc = build_canon(syms, nsyms, c)) return rc;
+  if (w && c.nsyms == 0) return fail(GH_E_TABLE, "segments but an empty code");
+  const uint64_t g = ceil_div(w, 4), ngapw = ceil_div(g, GH_GAPS_PER_WORD);
+  if (g >= BATCH_MAX_G) return fail(GH_E_ARG, "2^32 - 256 or more segments");
+  if (cap < ngapw) return fail(GH_E_SMALL, "gap word buffer smaller than ceil(G / 8)");
+  if (ngapw && !gap_words) return fail(GH_E_ARG, "null argument");
+  auto word = [&](uint64_t i) { return i < w ? words[i] : 0u; };  // (zero past W, as the payload arena)
+  // the batch's lookup rule at stream bit p: the canonical codeword's length, maxlen outside the code
+  auto length_at = [&](uint64_t p) {
+    const uint64_t two = ((uint64_t)word(p >> 5) << 32) | word((p >> 5) + 1);
+    uint32_t index;
+    const uint32_t l = canon_decode16(c, (uint32_t)(two >> (48 - (p & 31))) & 0xFFFFu, &index);
+    return l ? l : c.maxlen;
+  };
+  const uint64_t nunits = ceil_div(g, BATCH_UNIT_SEGS);
+  std::vector<unsigned long long> trans(g), agg(nunits, TRANS_IDENTITY);
+  for (uint64_t j = 0; j < g; ++j) {
+    unsigned long long f = 0;
+    for (uint32_t x = 0; x < 16; ++x) {
+      uint64_t p = 128 * j + x;
+      f |= trans_nibble(x, trans_walk(x, [&]() {
+             const uint32_t l = length_at(p);
+             p += l;
+             return l;
+           }));
+    }
+    trans[j] = f;
+    agg[j / BATCH_UNIT_SEGS] = trans_compose(agg[j / BATCH_UNIT_SEGS], f);
+  }
+  std::fill(gap_words, gap_words + ngapw, 0u);
+  uint32_t entry = 0;  // of unit u: 0 at the stream's first bit
+  for (uint64_t u = 0; u < nunits; ++u) {
+    uint32_t e = entry;
+    for (uint64_t j = u * BATCH_UNIT_SEGS; j < std::min<uint64_t>(g, (u + 1) * BATCH_UNIT_SEGS); ++j) {
+      e = trans_apply(trans[j], e);  // e_{j+1}: gap nibble j, but 0 for the stream's last segment
+      if (j + 1 < g) gap_words[j / GH_GAPS_PER_WORD] |= e << (4 * (j % GH_GAPS_PER_WORD));
+    }
+    entry = trans_apply(agg[u], entry);
+  }
   return GH_OK;
 }
 

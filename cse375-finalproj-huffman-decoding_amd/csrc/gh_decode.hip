@@ -38,6 +38,7 @@
 #include "gh_hip.hpp"
 #include "gh_internal.hpp"
 #include "gh_lut.hpp"
+#include "gh_raw_trans.hpp"
 #include "gh_units.hpp"
 
 namespace gh {
@@ -50,6 +51,7 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 #include "gh_gather.hip"
 #include "gh_gather_plan.hip"
 #include "gh_batch.hip"
+#include "gh_batch_raw.hip"
 #include "gh_batch_gather.hip"
 #include "gh_mtile.hip"
 
@@ -1560,6 +1562,15 @@ static BatchKernels batch_kernels_for(bool fb) { return fb ? batch_kernels<true>
 constexpr uint32_t BATCH_LAUNCHES = 3;  // count, scan, write
 constexpr uint32_t BATCH_INDEX_LAUNCHES = 2;   // count, scan (gh_batchdec_index)
 constexpr uint32_t BATCH_GATHER_LAUNCHES = 5;  // memset, locate, scan, emit, gather
+constexpr uint32_t BATCH_RAW_LAUNCHES = 3;     // trans, chain, apply (a raw load's gap kernels)
+
+// The trans kernel of a raw load, picked as the decode kernels are.
+template <bool FB>
+static Kern batchraw_kern() {
+  static const std::string n = kern_name("batchraw<fb=%d>", (int)FB);
+  return {(const void*)gh_batchraw_trans_kernel<FB>, n.c_str()};
+}
+static Kern batchraw_kern_for(bool fb) { return fb ? batchraw_kern<true>() : batchraw_kern<false>(); }
 
 template <bool FB>
 static Kern bgather_kern() {
@@ -1582,6 +1593,10 @@ struct gh_batch {
   DevBuf seg_cnt, unit_tot, unit_off, symbols;             // decode scratch
   DevBuf flags;                                            // 4 summary words, then a status word per stream
   DevBuf out;                                              // the batch's own output arena (on demand)
+  DevBuf raw_scratch;  // raw loads: per unit 256 T_j (8 bytes each), its aggregate (8) and its entry (4)
+  EventPair raw_ev;    // around the gap kernels of the last raw load
+  uint64_t raw_scratch_bytes = 0;
+  bool raw = false;    // the last load was a raw load
   BatchPlan plan;
   std::vector<uint64_t> n;
   uint32_t nstreams = 0, launches = 0;  // launches: of the last decode or index
@@ -1606,12 +1621,13 @@ extern "C" int gh_batch_destroy(gh_batch* b) {
 }
 
 // ss[i]: stream i's header; its word pointers are host memory (any alignment), or device
-// memory when `device`.
-static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device, void* hip_stream) {
+// memory when `device`.  raw: gap-less streams (g = ceil(w / 4), no gap source); their gap
+// words are built in the gap arena by the three kernels of gh_batch_raw.hip.
+static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device, void* hip_stream, bool raw = false) {
   const uint32_t ns = (uint32_t)ss.size();
   GH_HIP(hipSetDevice(b->q.device));
   if (int rc = b->q.quiesce()) return rc;  // the previous batch's decode reads what is replaced
-  b->loaded = b->own_out = b->indexed = b->g.enqueued = false;
+  b->loaded = b->own_out = b->indexed = b->g.enqueued = b->raw = false;
   std::vector<uint64_t> n(ns), w(ns), g(ns);
   std::vector<BatchDesc> desc(ns);
   std::vector<gh_sym> syms;
@@ -1624,8 +1640,8 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
     Canon cn;
     if (int rc = build_canon(s.syms, s.nsyms, cn)) return fail(rc, who + gh_last_error());
     if (s.g > 0 && cn.nsyms == 0) return fail(GH_E_TABLE, who + "segments but an empty code");
-    if ((s.w && !s.payload) || (s.g && !s.gap_words)) return fail(GH_E_ARG, who + "null word pointer");
-    if (device && ((((uintptr_t)s.payload) | ((uintptr_t)s.gap_words)) & 3u))
+    if ((s.w && !s.payload) || (s.g && !raw && !s.gap_words)) return fail(GH_E_ARG, who + "null word pointer");
+    if (device && ((((uintptr_t)s.payload) | (raw ? 0 : (uintptr_t)s.gap_words)) & 3u))
       return fail(GH_E_ARG, who + "device words not 4-byte aligned");
     n[i] = s.n;
     w[i] = s.w;
@@ -1668,20 +1684,26 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
   if (int rc = b->unit_off.reserve(8 * (plan.nunits + 1))) return rc;
   if (int rc = b->symbols.reserve(std::max<uint64_t>(8ull * ns, 16))) return rc;
   if (int rc = b->flags.reserve(16 + 4ull * ns)) return rc;
+  const uint64_t raw_bytes = (BR_T_BYTES + 8ull + 4ull) * plan.nunits;
+  if (raw) {
+    if (int rc = b->raw_scratch.reserve(std::max<uint64_t>(raw_bytes, 16))) return rc;
+    if (int rc = b->raw_ev.create()) return rc;
+  }
   if (!device) {
     // the arenas are assembled in host memory, padding included, and go up in two copies
     std::vector<uint32_t> pay(plan.pay_words, 0u), gap(plan.gap_words, 0u);
     for (uint32_t i = 0; i < ns; ++i) {
       if (w[i]) std::memcpy(pay.data() + plan.ext[i].pay_off, ss[i].payload, 4 * w[i]);
-      if (g[i]) std::memcpy(gap.data() + plan.ext[i].gap_off, ss[i].gap_words, 4 * plan.ext[i].gap_words);
+      if (g[i] && !raw) std::memcpy(gap.data() + plan.ext[i].gap_off, ss[i].gap_words, 4 * plan.ext[i].gap_words);
     }
     if (int rc = upload_arena(b->q.device, b->payload, pay.data(), 4 * pay.size())) return rc;
-    if (!gap.empty()) GH_HIP(hipMemcpy(b->gaps.get(), gap.data(), 4 * gap.size(), hipMemcpyHostToDevice));
+    if (!gap.empty() && !raw) GH_HIP(hipMemcpy(b->gaps.get(), gap.data(), 4 * gap.size(), hipMemcpyHostToDevice));
   } else {
     std::vector<BatchCopyItem> items(ns);
     for (uint32_t i = 0; i < ns; ++i) {
       const BatchExtent& e = plan.ext[i];
-      items[i] = BatchCopyItem{ss[i].payload, ss[i].gap_words, w[i], e.pay_off, e.pay_words, e.gap_off, e.gap_words};
+      items[i] = BatchCopyItem{ss[i].payload, raw ? nullptr : ss[i].gap_words, w[i], e.pay_off, e.pay_words, e.gap_off,
+                               raw ? 0ull : e.gap_words};
     }
     if (int rc = upload_at_least(b->items, items.data(), sizeof(BatchCopyItem) * (uint64_t)ns)) return rc;
     // after what the producer's stream holds now, then one copy kernel on the batch's stream
@@ -1697,7 +1719,36 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
                        b->q.stream, b->desc.get<BatchDesc>(), b->syms.get<gh_sym>(), b->tables.get<uint32_t>(), ns);
     GH_HIP(hipGetLastError());
   }
+  if (raw) {  // the gap arena from the payload: three launches, whatever ns is (every unit's gap words are written whole)
+    GH_HIP(hipEventRecord(b->raw_ev.a, b->q.stream));
+    if (plan.nunits) {
+      BatchParams bp{};
+      bp.desc = b->desc.get<BatchDesc>();
+      bp.unit0 = b->unit0.get<uint32_t>();
+      bp.payload = b->payload.get<uint32_t>();
+      bp.tables = b->tables.get<uint32_t>();
+      bp.nstreams = ns;
+      bp.nunits = (uint32_t)plan.nunits;
+      unsigned long long* trans = b->raw_scratch.get<unsigned long long>();
+      unsigned long long* agg = trans + plan.nunits * BATCH_UNIT_SEGS;
+      uint32_t* entry = (uint32_t*)(agg + plan.nunits);
+      const uint32_t* cunit0 = bp.unit0;
+      uint32_t* dgaps = b->gaps.get<uint32_t>();
+      const uint32_t grid = unit_grid("GH_BATCH_GRID", plan.nunits, BA_TB / 64, b->q.num_cu);
+      const uint32_t cgrid = (uint32_t)std::clamp<uint64_t>(ceil_div(ns, BR_CHAIN_TB / 64), 1, 4ull * (uint64_t)b->q.num_cu);
+      uint32_t nsv = ns;
+      void* targs[] = {&bp, &trans, &agg};
+      GH_HIP(hipLaunchKernel(batchraw_kern_for(fb).fn, dim3(grid), dim3(BA_TB), targs, 0, b->q.stream));
+      void* cargs[] = {&cunit0, &nsv, &agg, &entry};
+      GH_HIP(hipLaunchKernel((const void*)gh_batchraw_chain_kernel, dim3(cgrid), dim3(BR_CHAIN_TB), cargs, 0, b->q.stream));
+      void* aargs[] = {&bp, &trans, &entry, &dgaps};
+      GH_HIP(hipLaunchKernel((const void*)gh_batchraw_apply_kernel, dim3(grid), dim3(BA_TB), aargs, 0, b->q.stream));
+    }
+    GH_HIP(hipEventRecord(b->raw_ev.b, b->q.stream));
+  }
   GH_HIP(hipStreamSynchronize(b->q.stream));
+  b->raw = raw;
+  b->raw_scratch_bytes = raw ? raw_bytes : 0;
   b->plan = std::move(plan);
   b->n = std::move(n);
   b->nstreams = ns;
@@ -1721,6 +1772,67 @@ extern "C" int gh_batch_load_device(gh_batch* b, const gh_batch_item* items, uin
     ss[i] = gh_stream{it.syms, it.nsyms, 2u, it.n, it.w, it.g, it.d_gap_words, it.d_payload};
   }
   return batch_load(b, ss, true, hip_stream);
+}
+
+// ---- batched gap-less load (gaphuff.h; kernels: gh_batch_raw.hip; functions: gh_raw_trans.hpp) ----
+extern "C" int gh_batchraw_load(gh_batch* b, const gh_raw_stream* streams, uint32_t nstreams) {
+  if (!b || (nstreams && !streams)) return fail(GH_E_ARG, "null argument");
+  if (nstreams > BATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  std::vector<gh_stream> ss(nstreams);
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    const gh_raw_stream& r = streams[i];
+    ss[i] = gh_stream{r.syms, r.nsyms, 2u, r.n, r.w, r.w / 4 + (r.w % 4 != 0), nullptr, r.units};
+  }
+  return batch_load(b, ss, false, nullptr, true);
+}
+
+extern "C" int gh_batchraw_load_device(gh_batch* b, const gh_batch_item* items, uint32_t nstreams, void* hip_stream) {
+  if (!b || (nstreams && !items)) return fail(GH_E_ARG, "null argument");
+  if (nstreams > BATCH_MAX_STREAMS) return fail(GH_E_ARG, "more than 2^24 streams in a batch");
+  std::vector<gh_stream> ss(nstreams);
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    const gh_batch_item& it = items[i];
+    if (it.g != it.w / 4 + (it.w % 4 != 0))
+      return fail(GH_E_ARG, "stream " + std::to_string(i) + ": a raw stream has G = ceil(W / 4) segments");
+    ss[i] = gh_stream{it.syms, it.nsyms, 2u, it.n, it.w, it.g, nullptr, it.d_payload};
+  }
+  return batch_load(b, ss, true, hip_stream, true);
+}
+
+extern "C" int gh_batchraw_gaps(gh_batch* b, uint32_t stream, uint32_t* gap_words, uint64_t cap, uint64_t* ngapw) {
+  if (ngapw) *ngapw = 0;
+  if (!b || !ngapw) return fail(GH_E_ARG, "null argument");
+  if (!b->loaded) return fail(GH_E_STATE, "gh_batchraw_gaps before a load");
+  if (stream >= b->nstreams) return fail(GH_E_ARG, "no such stream in the batch");
+  const BatchExtent& e = b->plan.ext[stream];
+  *ngapw = e.gap_words;
+  if (cap < e.gap_words) return fail(GH_E_SMALL, "gap word buffer smaller than the stream's gap words");
+  if (e.gap_words && !gap_words) return fail(GH_E_ARG, "null argument");
+  GH_HIP(hipSetDevice(b->q.device));
+  if (e.gap_words)
+    GH_HIP(hipMemcpy(gap_words, b->gaps.get<uint32_t>() + e.gap_off, 4 * e.gap_words, hipMemcpyDeviceToHost));
+  return GH_OK;
+}
+
+extern "C" int gh_batchraw_report_get(gh_batch* b, gh_batchraw_report* rep) {
+  if (!b || !rep) return fail(GH_E_ARG, "null argument");
+  *rep = gh_batchraw_report{};
+  if (!b->loaded || !b->raw) return fail(GH_E_STATE, "gh_batchraw_report_get: the last load was not a raw load");
+  GH_HIP(hipSetDevice(b->q.device));
+  if (int rc = b->raw_ev.elapsed(&rep->gap_ms)) return rc;
+  rep->launches = BATCH_RAW_LAUNCHES;
+  rep->scratch_bytes = b->raw_scratch_bytes;
+  return GH_OK;
+}
+
+extern "C" int gh_batchraw_kernel_shape(gh_batch* b, char* buf, size_t cap) {
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded || !b->raw) return fail(GH_E_STATE, "gh_batchraw_kernel_shape: the last load was not a raw load");
+  return copy_name(b->plan.nunits ? batchraw_kern_for(b->fb).name : "", buf, cap);
+}
+
+extern "C" int gh_batchraw_kernel_shapes(char* buf, size_t cap) {
+  return copy_name(std::string(batchraw_kern_for(false).name) + "\n" + batchraw_kern_for(true).name + "\n", buf, cap);
 }
 
 // The kernels' view of the loaded batch; out: where a write or gather kernel stores.

@@ -71,6 +71,8 @@ EXPORTED = (
     "gh_package_merge_flat", "gh_batchenc_plan_device", "gh_batchenc_plan_times",
     "gh_batchdec_index", "gh_batchdec_gather_device", "gh_batchdec_gather_wait", "gh_batchdec_gather",
     "gh_batchdec_gather_pieces", "gh_batchdec_plan", "gh_batchdec_kernel_shape", "gh_batchdec_kernel_shapes",
+    "gh_batchraw_load", "gh_batchraw_load_device", "gh_batchraw_gaps", "gh_batchraw_report_get",
+    "gh_batchraw_gaps_host", "gh_batchraw_kernel_shape", "gh_batchraw_kernel_shapes",
 )
 GH_EBATCH_UNIT_BYTES = 1024
 
@@ -165,6 +167,10 @@ class gh_brange(ctypes.Structure):
 class gh_bgather_report(ctypes.Structure):
     _fields_ = [("out_bytes", ctypes.c_uint64), ("npieces", ctypes.c_uint64), ("bad_ranges", ctypes.c_uint32),
                 ("status", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
+
+
+class gh_batchraw_report(ctypes.Structure):
+    _fields_ = [("gap_ms", ctypes.c_float), ("launches", ctypes.c_uint32), ("scratch_bytes", ctypes.c_uint64)]
 
 
 class gh_ebatch_item(ctypes.Structure):
@@ -308,6 +314,13 @@ def lib() -> ctypes.CDLL:
                                   ctypes.POINTER(U32)], I),
             "gh_batchdec_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_batchdec_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_batchraw_load": ([P, ctypes.POINTER(gh_raw_stream), U32], I),
+            "gh_batchraw_load_device": ([P, ctypes.POINTER(gh_batch_item), U32, P], I),
+            "gh_batchraw_gaps": ([P, U32, P, U64, ctypes.POINTER(U64)], I),
+            "gh_batchraw_report_get": ([P, ctypes.POINTER(gh_batchraw_report)], I),
+            "gh_batchraw_gaps_host": ([P, U32, P, U64, P, U64], I),
+            "gh_batchraw_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_batchraw_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_ebatch_create": ([I, ctypes.POINTER(P)], I),
             "gh_ebatch_destroy": ([P], I),
             "gh_ebatch_load": ([P, P, P, U32], I),
@@ -960,6 +973,23 @@ def batch_kernel_shapes() -> list:
     return _name(lib().gh_batch_kernel_shapes, cap=1 << 10).split()
 
 
+def batchraw_kernel_shapes() -> list:
+    """Every kernel name a raw batch load can pick (gh_batchraw_kernel_shapes); needs no device."""
+    return _name(lib().gh_batchraw_kernel_shapes, cap=1 << 10).split()
+
+
+def raw_gaps_host(units, symbols: Sequence[tuple]) -> np.ndarray:
+    """Gap words of the raw stream ``units`` (u32) under the canonical ``symbols`` list, by the
+    host twin of the batched raw load's kernels (gh_batchraw_gaps_host); needs no device."""
+    u = np.ascontiguousarray(units, dtype=np.uint32)
+    sy = _syms(symbols)
+    g = -(-u.size // 4)
+    out = np.zeros(-(-g // 8), dtype=np.uint32)
+    _check(lib().gh_batchraw_gaps_host(ctypes.byref(sy) if len(symbols) else None, len(symbols),
+                                       _ptr(u) if u.size else None, u.size, _ptr(out) if out.size else None, out.size))
+    return out
+
+
 def batchdec_kernel_shapes() -> list:
     """Every kernel name a batched gather can pick (gh_batchdec_kernel_shapes); needs no device."""
     return _name(lib().gh_batchdec_kernel_shapes, cap=1 << 10).split()
@@ -1035,6 +1065,60 @@ class BatchDecoder(_Handle):
         self._indexed = False
         _check(lib().gh_batch_load_device(self._h, arr, len(items), ctypes.c_void_p(hip_stream or None)))
         self.ns = [s.n for s, _, _ in items]
+
+    def load_raw(self, raws) -> None:
+        """Load a batch of gap-less (raw) streams from host memory (gh_batchraw_load): each item
+        is a raw-stream container image (bytes / np.uint8) or a ``(symbols, n, units)`` triple
+        as :func:`parse_raw` returns.  Their gap arrays are built on the GPU."""
+        triples = [r if isinstance(r, tuple) else parse_raw(r) for r in raws]
+        arr = (gh_raw_stream * max(1, len(triples)))()
+        keep = []
+        for i, (symbols, n, units) in enumerate(triples):
+            # (symbol, length) byte pairs are gh_sym's layout; a batch holds thousands of tables
+            sy = np.ascontiguousarray(np.asarray(symbols, dtype=np.uint8).reshape(-1, 2))
+            u = np.ascontiguousarray(units, dtype=np.uint32)
+            keep.append((sy, u))
+            arr[i].syms = ctypes.cast(_ptr(sy), ctypes.POINTER(gh_sym)) if sy.size else None
+            arr[i].nsyms, arr[i].n, arr[i].w = len(symbols), n, u.size
+            arr[i].units = _ptr(u) if u.size else None
+        self._indexed = False
+        _check(lib().gh_batchraw_load(self._h, arr, len(triples)))
+        self.ns = [int(n) for _, n, _ in triples]
+
+    def load_raw_device(self, items, hip_stream: int = 0) -> None:
+        """:meth:`load_device` for gap-less streams (gh_batchraw_load_device): the same
+        ``(stream, payload_ptr, gap_ptr)`` items, ``gap_ptr`` ignored, ``stream.g`` equal to
+        ceil(w / 4).  :meth:`BatchEncoder.items` output is a valid source."""
+        items = list(items)
+        arr = (gh_batch_item * max(1, len(items)))()
+        for i, (s, pay, _) in enumerate(items):
+            arr[i].syms, arr[i].nsyms = s.c.syms, s.c.nsyms
+            arr[i].n, arr[i].w, arr[i].g = s.c.n, s.c.w, s.c.g
+            arr[i].d_payload, arr[i].d_gap_words = pay or None, None
+        self._indexed = False
+        _check(lib().gh_batchraw_load_device(self._h, arr, len(items), ctypes.c_void_p(hip_stream or None)))
+        self.ns = [s.n for s, _, _ in items]
+
+    def raw_gaps(self, i: int) -> np.ndarray:
+        """The resident gap words of stream ``i`` (gh_batchraw_gaps), after either kind of load."""
+        n = ctypes.c_uint64()
+        rc = lib().gh_batchraw_gaps(self._h, i, None, 0, ctypes.byref(n))
+        if rc not in (GH_OK, -9):
+            _check(rc)
+        out = np.zeros(int(n.value), dtype=np.uint32)
+        _check(lib().gh_batchraw_gaps(self._h, i, _ptr(out) if out.size else None, out.size, ctypes.byref(n)))
+        return out
+
+    def raw_report(self) -> gh_batchraw_report:
+        """Event time, launch count and scratch of the last raw load's gap kernels
+        (gh_batchraw_report_get); GH_E_STATE when the last load was not raw."""
+        rep = gh_batchraw_report()
+        _check(lib().gh_batchraw_report_get(self._h, ctypes.byref(rep)))
+        return rep
+
+    def raw_kernel_shape(self) -> str:
+        """Name of the T_j kernel instantiation the last raw load picked (gh_batchraw_kernel_shape)."""
+        return _name(lib().gh_batchraw_kernel_shape, self._h)
 
     def decode(self, dst_ptr: int = 0, dst_len: int = 0, hip_stream: int = 0, timed: bool = True) -> None:
         """Enqueue one decode of the batch into the device memory at ``dst_ptr`` (16-byte
@@ -1147,6 +1231,16 @@ def decode_batch(images, device: int = 0) -> list:
     """Decode many compressed.huff images as one batch; returns their bytes in order."""
     with BatchDecoder(device) as b:
         b.load(images)
+        b.decode()
+        b.wait()
+        return b.download_all()
+
+
+def decode_batch_raw(raws, device: int = 0) -> list:
+    """Decode many gap-less streams (container images or ``(symbols, n, units)`` triples) as one
+    batch; returns their bytes in order."""
+    with BatchDecoder(device) as b:
+        b.load_raw(raws)
         b.decode()
         b.wait()
         return b.download_all()

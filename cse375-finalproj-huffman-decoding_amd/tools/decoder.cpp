@@ -4,6 +4,8 @@
 // bin/decoder --batch LIST [--ranges FILE OUT]
 // --batch LIST (a text file, one input<TAB>output per line) decodes all inputs as one batch
 // (gh_batch_*: one fixed set of launches however many streams) and writes every output.
+// When every input is a raw container the batch is loaded by gh_batchraw_load (the gap arrays
+// are built on the GPU); a list that mixes the two kinds is refused.
 // --batch LIST --ranges FILE OUT (FILE: one `STREAM LO:HI` per line, STREAM the 0-based line
 // of LIST, blank lines not counted) indexes the batch without decoding it and gathers only the
 // named byte ranges (gh_batchdec_*); their concatenation in file order goes to OUT and the
@@ -185,13 +187,33 @@ static int batch_main(const char* list_file, const char* ranges_file = nullptr, 
   const size_t ns = in.size();
   std::vector<std::vector<uint8_t>> img(ns);
   std::vector<gh_stream> streams(ns);
+  std::vector<gh_raw_stream> raws;  // a list of raw containers: the batch's gap arrays are built on the GPU
+  bool raw = false;
   int rc;
   for (size_t i = 0; i < ns; ++i) {
     if (!read_file(in[i].c_str(), img[i])) {
       std::fprintf(stderr, "decoder: %s: line %zu: Could not open input file %s\n", list_file, line_of[i], in[i].c_str());
       return 1;
     }
-    if ((rc = gh_stream_parse(img[i].data(), img[i].size(), &streams[i]))) {
+    uint64_t magic = 0;
+    if (img[i].size() >= 8) std::memcpy(&magic, img[i].data(), 8);
+    const bool is_raw = magic == GH_RAW_MAGIC;
+    if (i == 0) raw = is_raw;
+    if (is_raw != raw) {
+      std::fprintf(stderr, "decoder: %s: line %zu: %s is %s, the lines before it are %s: a batch is all raw containers or all "
+                           "compressed.huff files\n", list_file, line_of[i], in[i].c_str(), is_raw ? "a raw container" : "a compressed.huff file",
+                   raw ? "raw containers" : "compressed.huff files");
+      return 1;
+    }
+    if (raw) {
+      gh_raw_stream r;
+      if ((rc = gh_raw_parse(img[i].data(), img[i].size(), &r))) {
+        std::fprintf(stderr, "decoder: %s: line %zu: %s: ", list_file, line_of[i], in[i].c_str());
+        return die("bad raw stream", rc);
+      }
+      raws.push_back(r);
+      streams[i].n = r.n;  // (what the ranges and the downloads below read)
+    } else if ((rc = gh_stream_parse(img[i].data(), img[i].size(), &streams[i]))) {
       std::fprintf(stderr, "decoder: %s: line %zu: %s: ", list_file, line_of[i], in[i].c_str());
       return die("bad compressed stream", rc);
     }
@@ -200,7 +222,10 @@ static int batch_main(const char* list_file, const char* ranges_file = nullptr, 
   gh_batch* b = nullptr;
   if ((rc = gh_batch_create(0, &b))) return die("device init", rc);
   const double t0 = now_ms();
-  if ((rc = gh_batch_load(b, streams.data(), (uint32_t)ns))) { gh_batch_destroy(b); return die("batch load", rc); }
+  if ((rc = raw ? gh_batchraw_load(b, raws.data(), (uint32_t)ns) : gh_batch_load(b, streams.data(), (uint32_t)ns))) {
+    gh_batch_destroy(b);
+    return die("batch load", rc);
+  }
   const double t1 = now_ms();
   if (ranges_file) {
     std::vector<gh_brange> ranges;

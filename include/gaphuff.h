@@ -864,6 +864,53 @@ int gh_raw_parse(const void* file, size_t file_len, gh_raw_stream* out);
 int gh_ctx_load_raw(gh_ctx* ctx, const gh_sym* syms, uint32_t nsyms, uint64_t n,
                     const uint32_t* words, uint64_t w, uint64_t out_cap, gh_sync_report* rep);
 
+/* ---- batched gap-less decode: raw streams into a gh_batch, gap arrays built on the GPU ---- */
+/* The batch treatment for raw streams: any number of gap-less streams, each with its own code,
+ * loaded into a gh_batch by a fixed number of launches, with no read-back and no host loop.
+ * gh_batch_decode, gh_batchdec_index, the gathers and gh_batch_status then run unchanged.
+ *
+ * The method is exact.  A codeword has at most 16 bits, so a segment's entry (its first
+ * codeword start minus 128 j) lies in 0..15 and segment j is a total function T_j on 16
+ * states, one u64 of 16 nibbles.  e_0 = 0, e_{j+1} = T_j(e_j); composition is associative, so
+ * all entries come from a prefix scan of composed functions, segmented by stream.  Gap nibble
+ * j is e_{j+1} for j < G - 1 and 0 for j = G - 1 and the tail of the last gap word: what the
+ * encoders write.  Three kernels: T_j and the aggregate of every 256-segment unit; the units'
+ * entries, stream by stream; the gap words of every unit.  G = ceil(W / 4).  (The gh_batch_*,
+ * gh_batchdec_* and gh_ebatch_* names are closed sets pinned by tests; these carry gh_batchraw_.) */
+/* gh_batch_load for raw streams in host memory (any alignment); synchronous.  Runs the checks
+ * of gh_raw_parse (a canonical code; N symbols fit the 32 W bits) and the batch limits; an
+ * error names the stream as gh_batch_load's do. */
+int gh_batchraw_load(gh_batch* b, const gh_raw_stream* streams, uint32_t nstreams);
+/* gh_batch_load_device for raw streams: d_gap_words is not read; g must equal ceil(w / 4)
+ * (GH_E_ARG otherwise).  Follows hip_stream as gh_batch_load_device.  gh_ebatch_items output
+ * is a valid source: a batch can be encoded and decoded on the device without its gap words
+ * ever being read. */
+int gh_batchraw_load_device(gh_batch* b, const gh_batch_item* items, uint32_t nstreams, void* hip_stream);
+/* The resident gap words of one stream (ceil(G / 8) u32) to host memory, after either kind of
+ * load.  *ngapw is always written; GH_E_SMALL when cap is smaller. */
+int gh_batchraw_gaps(gh_batch* b, uint32_t stream, uint32_t* gap_words, uint64_t cap, uint64_t* ngapw);
+typedef struct gh_batchraw_report {
+  float gap_ms;            /* HIP events around the gap kernels of the last raw load        */
+  uint32_t launches;       /* their count: a constant                                       */
+  uint64_t scratch_bytes;  /* 8 * 256 + 8 + 4 bytes per work unit                           */
+} gh_batchraw_report;
+/* GH_E_STATE when the last load was not a raw load. */
+int gh_batchraw_report_get(gh_batch* b, gh_batchraw_report* rep);
+/* The host twin: the same gap words (ceil(ceil(w / 4) / 8) u32; GH_E_SMALL when cap is
+ * smaller) from the same functions (csrc/gh_raw_trans.hpp) under the batch's lookup rule (a
+ * pattern outside an incomplete code advances maxlen bits), composed per 256-segment unit and
+ * chained, as the kernels are cut.  Any words are accepted, valid streams or not.  GH_E_TABLE
+ * for a non-canonical code, or an empty one with w > 0.  Needs no device. */
+int gh_batchraw_gaps_host(const gh_sym* syms, uint32_t nsyms, const uint32_t* words, uint64_t w,
+                          uint32_t* gap_words, uint64_t cap);
+/* The T_j kernel is one of two instantiations, "batchraw<fb=0>" and "batchraw<fb=1>", picked as
+ * the batch's decode kernels are.  gh_batchraw_kernel_shape: the name the last raw load picked
+ * (empty for a batch without segments); GH_E_STATE when the last load was not a raw load.
+ * gh_batchraw_kernel_shapes: both names, one per line; needs no device.  Neither is part of
+ * another shape list. */
+int gh_batchraw_kernel_shape(gh_batch* b, char* buf, size_t cap);
+int gh_batchraw_kernel_shapes(char* buf, size_t cap);
+
 /* One-shot decode of a whole stream into host memory `out` (out_len >= N):
  * mirrors decoder_l1_l2 (decoder.cu:732-815) without its 200-iteration loop.
  * ngpus <= 0 or 1: device `devices ? devices[0] : 0`; ngpus > 1 shards the
