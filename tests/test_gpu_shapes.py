@@ -88,8 +88,8 @@ MTILE_ROWS = {
 MTILE_RUNS = (("shuffled", False), ("sorted", False), ("shuffled", True))  # (ordering, GH_TILE_GRID=3)
 
 # Wave split (GH_MODE=wsplit): count kernel by GH_WS_KC, write kernel by GH_WS_K and
-# GH_WS_NS (lookups per shift as above); fb: an incomplete code (one symbol) or codewords
-# longer than the tables.
+# GH_WS_NS (lookups per shift as above); fb: an incomplete code (here the one-symbol code;
+# multi-symbol ones are in tests/test_gpu_foreign_codes.py) or codewords longer than the tables.
 ONE_SYMBOL = {1: 1}
 
 
