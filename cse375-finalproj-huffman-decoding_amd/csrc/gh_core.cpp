@@ -23,6 +23,7 @@
 #include "gh_batch_range.hpp"
 #include "gh_internal.hpp"
 #include "gh_pm_flat.hpp"
+#include "gh_planes.hpp"
 #include "gh_raw_trans.hpp"
 
 namespace gh {
@@ -1062,6 +1063,190 @@ extern "C" int gh_plan_shards(uint64_t g, uint32_t nshards, uint64_t* bounds) {
   if (!bounds || nshards == 0) return fail(GH_E_ARG, "bad shard request");
   for (uint32_t k = 0; k <= nshards; ++k)
     bounds[k] = (uint64_t)((unsigned __int128)g * k / nshards);
+  return GH_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Byte planes (gaphuff.h, "byte planes"): the layout, the CPU twins of the split and join
+// kernels (the same text, csrc/gh_planes.hpp) and the container.  No device.
+// ---------------------------------------------------------------------------
+static int planes_item_check(const gh_planes_item& it, const std::string& who) {
+  if (!planes_elem_ok(it.elem_size)) return fail(GH_E_ARG, who + "element size not 1, 2, 4 or 8");
+  if (!planes_mask_ok(it.elem_size, it.coded_mask)) return fail(GH_E_ARG, who + "coded_mask names a plane >= elem_size");
+  return GH_OK;
+}
+
+extern "C" int gh_planes_layout(const gh_planes_item* items, uint32_t ntensors, gh_planes_slot* slots,
+                                uint32_t* nstreams, uint64_t* stored_bytes) {
+  if (nstreams) *nstreams = 0;
+  if (stored_bytes) *stored_bytes = 0;
+  if (!nstreams || !stored_bytes || (ntensors && (!items || !slots))) return fail(GH_E_ARG, "null argument");
+  uint64_t ns = 0, at = 0;
+  for (uint32_t t = 0; t < ntensors; ++t) {
+    const gh_planes_item& it = items[t];
+    const std::string who = "tensor " + std::to_string(t) + ": ";
+    if (int rc = planes_item_check(it, who)) return rc;
+    uint64_t padded;
+    if (!planes_padded(it.nelem, &padded)) return fail(GH_E_ARG, who + "the stored arena overflows 64 bits");
+    for (uint32_t p = 0; p < PLANES_MAX_E; ++p) {
+      gh_planes_slot& s = slots[(uint64_t)PLANES_MAX_E * t + p];
+      s = gh_planes_slot{GH_PLANES_STORED, 0, 0};
+      if (p >= it.elem_size) continue;
+      if ((it.coded_mask >> p) & 1u) {
+        if (ns == PLANES_MAX_CODED) return fail(GH_E_ARG, who + "more than 2^24 coded planes");
+        s.stream = (uint32_t)ns++;
+      } else {
+        s.stored_off = at;
+        if (!planes_add(at, padded, &at)) return fail(GH_E_ARG, who + "the stored arena overflows 64 bits");
+      }
+    }
+  }
+  *nstreams = (uint32_t)ns;
+  *stored_bytes = at;
+  return GH_OK;
+}
+
+// Whole groups of 16 elements by the vector rule, the rest by the scalar rule.
+template <uint32_t E>
+static void planes_split_t(const uint8_t* src, uint64_t nelem, uint8_t* const* pl) {
+  uint64_t i = 0;
+  for (; i + PLANES_GROUP <= nelem; i += PLANES_GROUP) {
+    uint32_t w[4 * E], o[E][4];
+    std::memcpy(w, src + i * E, sizeof(w));
+    planes_split16<E>(w, o);
+    for (uint32_t p = 0; p < E; ++p) std::memcpy(pl[p] + i, o[p], 16);
+  }
+  for (; i < nelem; ++i)
+    for (uint32_t p = 0; p < E; ++p) pl[p][i] = src[planes_src_index(i, E, p)];
+}
+
+template <uint32_t E>
+static void planes_join_t(uint8_t* dst, uint64_t nelem, const uint8_t* const* pl) {
+  uint64_t i = 0;
+  for (; i + PLANES_GROUP <= nelem; i += PLANES_GROUP) {
+    uint32_t w[4 * E], o[E][4];
+    for (uint32_t p = 0; p < E; ++p) std::memcpy(o[p], pl[p] + i, 16);
+    planes_join16<E>(o, w);
+    std::memcpy(dst + i * E, w, sizeof(w));
+  }
+  for (; i < nelem; ++i)
+    for (uint32_t p = 0; p < E; ++p) dst[planes_src_index(i, E, p)] = pl[p][i];
+}
+
+static int planes_twin_check(const gh_planes_item* item, const void* const* planes) {
+  if (!item || !planes) return fail(GH_E_ARG, "null argument");
+  if (int rc = planes_item_check(*item, "")) return rc;
+  if (item->nelem) {
+    if (!item->data) return fail(GH_E_ARG, "null tensor pointer");
+    for (uint32_t p = 0; p < item->elem_size; ++p)
+      if (!planes[p]) return fail(GH_E_ARG, "null plane pointer");
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_planes_split_host(const gh_planes_item* item, void* const* planes) {
+  if (int rc = planes_twin_check(item, planes)) return rc;
+  const uint8_t* src = (const uint8_t*)item->data;
+  uint8_t* const* pl = (uint8_t* const*)planes;
+  switch (item->elem_size) {
+    case 1: planes_split_t<1>(src, item->nelem, pl); break;
+    case 2: planes_split_t<2>(src, item->nelem, pl); break;
+    case 4: planes_split_t<4>(src, item->nelem, pl); break;
+    default: planes_split_t<8>(src, item->nelem, pl); break;
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_planes_join_host(const gh_planes_item* item, const void* const* planes) {
+  if (int rc = planes_twin_check(item, planes)) return rc;
+  uint8_t* dst = (uint8_t*)item->data;
+  const uint8_t* const* pl = (const uint8_t* const*)planes;
+  switch (item->elem_size) {
+    case 1: planes_join_t<1>(dst, item->nelem, pl); break;
+    case 2: planes_join_t<2>(dst, item->nelem, pl); break;
+    case 4: planes_join_t<4>(dst, item->nelem, pl); break;
+    default: planes_join_t<8>(dst, item->nelem, pl); break;
+  }
+  return GH_OK;
+}
+
+// The container: 24 header bytes, E plane sizes, then the planes on 8-byte boundaries.
+constexpr uint64_t PLANES_HEADER = 24;
+
+extern "C" int gh_planes_image_bytes(uint32_t elem_size, const uint64_t* plane_bytes, uint64_t* total) {
+  if (total) *total = 0;
+  if (!plane_bytes || !total) return fail(GH_E_ARG, "null argument");
+  if (!planes_elem_ok(elem_size)) return fail(GH_E_ARG, "element size not 1, 2, 4 or 8");
+  uint64_t at = PLANES_HEADER + 8ull * elem_size;
+  for (uint32_t p = 0; p < elem_size; ++p) {
+    uint64_t start;
+    if (!planes_add(at, 7, &start) || !planes_add(start & ~7ull, plane_bytes[p], &at))
+      return fail(GH_E_ARG, "the container's size overflows 64 bits");
+  }
+  *total = at;
+  return GH_OK;
+}
+
+extern "C" int gh_planes_image_write(const gh_planes_item* item, const void* const* planes, const uint64_t* plane_bytes,
+                                     void* out, uint64_t out_len) {
+  if (!item || !planes || !plane_bytes || !out) return fail(GH_E_ARG, "null argument");
+  if (int rc = planes_item_check(*item, "")) return rc;
+  const uint32_t e = item->elem_size;
+  for (uint32_t p = 0; p < e; ++p) {
+    if (plane_bytes[p] && !planes[p]) return fail(GH_E_ARG, "null plane pointer");
+    if (!((item->coded_mask >> p) & 1u) && plane_bytes[p] != item->nelem)
+      return fail(GH_E_ARG, "plane " + std::to_string(p) + ": a stored plane holds nelem bytes");
+  }
+  uint64_t total;
+  if (int rc = gh_planes_image_bytes(e, plane_bytes, &total)) return rc;
+  if (out_len < total) return fail(GH_E_SMALL, "output buffer smaller than the container");
+  uint8_t* o = (uint8_t*)out;
+  std::memset(o, 0, total);
+  const uint64_t magic = GH_PLANES_MAGIC;
+  std::memcpy(o, &magic, 8);
+  std::memcpy(o + 8, &item->elem_size, 4);
+  std::memcpy(o + 12, &item->coded_mask, 4);
+  std::memcpy(o + 16, &item->nelem, 8);
+  uint64_t at = PLANES_HEADER + 8ull * e;
+  for (uint32_t p = 0; p < e; ++p) {
+    std::memcpy(o + PLANES_HEADER + 8ull * p, &plane_bytes[p], 8);
+    at = (at + 7) & ~7ull;
+    if (plane_bytes[p]) std::memcpy(o + at, planes[p], plane_bytes[p]);
+    at += plane_bytes[p];
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_planes_parse(const void* file, size_t file_len, gh_planes_image* out) {
+  if (!file || !out) return fail(GH_E_ARG, "null argument");
+  *out = gh_planes_image{};
+  const uint8_t* f = (const uint8_t*)file;
+  const uint64_t len = file_len;
+  if (len < PLANES_HEADER || rd<uint64_t>(f) != GH_PLANES_MAGIC) return fail(GH_E_FORMAT, "not a byte-plane container");
+  gh_planes_image im{};
+  im.elem_size = rd<uint32_t>(f + 8);
+  im.coded_mask = rd<uint32_t>(f + 12);
+  im.nelem = rd<uint64_t>(f + 16);
+  if (!planes_elem_ok(im.elem_size)) return fail(GH_E_FORMAT, "element size not 1, 2, 4 or 8");
+  if (!planes_mask_ok(im.elem_size, im.coded_mask)) return fail(GH_E_FORMAT, "coded_mask names a plane >= elem_size");
+  uint64_t at = PLANES_HEADER + 8ull * im.elem_size;
+  if (len < at) return fail(GH_E_FORMAT, "truncated plane sizes");
+  for (uint32_t p = 0; p < im.elem_size; ++p) {
+    const std::string who = "plane " + std::to_string(p) + ": ";
+    const uint64_t nb = rd<uint64_t>(f + PLANES_HEADER + 8ull * p);
+    at = (at + 7) & ~7ull;  // (at <= len < 2^64 - 7: a file in memory)
+    if (at > len || nb > len - at) return fail(GH_E_FORMAT, who + "outside the file");
+    im.plane[p] = f + at;
+    im.plane_bytes[p] = nb;
+    if ((im.coded_mask >> p) & 1u) {
+      if (gh_stream_parse(f + at, nb, &im.stream[p])) return fail(GH_E_FORMAT, who + gh_last_error());
+      if (im.stream[p].n != im.nelem) return fail(GH_E_FORMAT, who + "its stream's n is not nelem");
+    } else if (nb != im.nelem) {
+      return fail(GH_E_FORMAT, who + "a stored plane holds nelem bytes");
+    }
+    at += nb;  // (<= len)
+  }
+  *out = im;
   return GH_OK;
 }
 

@@ -38,6 +38,7 @@
 #include "gh_hip.hpp"
 #include "gh_internal.hpp"
 #include "gh_lut.hpp"
+#include "gh_planes.hpp"
 #include "gh_raw_trans.hpp"
 #include "gh_units.hpp"
 
@@ -53,6 +54,7 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 #include "gh_batch.hip"
 #include "gh_batch_raw.hip"
 #include "gh_batch_gather.hip"
+#include "gh_planes_join.hip"
 #include "gh_mtile.hip"
 
 }  // namespace gh
@@ -1588,6 +1590,16 @@ struct BatchGather {
   bool enqueued = false, timed = false;
 };
 
+// The byte-plane join's state in a gh_batch (gh_planes_*).  desc: the tensors' descriptors,
+// then their unit prefix; words: [0] tensors with a flagged plane.
+struct BatchPlanes {
+  DevBuf desc, words;
+  EventPair ev;
+  uint64_t out_bytes = 0;
+  uint32_t ntensors = 0;
+  bool enqueued = false, timed = false;
+};
+
 struct gh_batch {
   DevBuf payload, gaps, tables, desc, unit0, syms, items;  // the loaded batch
   DevBuf seg_cnt, unit_tot, unit_off, symbols;             // decode scratch
@@ -1603,6 +1615,7 @@ struct gh_batch {
   bool loaded = false, fb = false, own_out = false;
   bool indexed = false;  // seg_cnt / unit_off / status are (being) made by a decode or an index since the load
   BatchGather g;
+  BatchPlanes pl;
   BatchQueue q;  // (last: its destructor waits for the decode before the buffers above go)
 };
 
@@ -1627,7 +1640,7 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
   const uint32_t ns = (uint32_t)ss.size();
   GH_HIP(hipSetDevice(b->q.device));
   if (int rc = b->q.quiesce()) return rc;  // the previous batch's decode reads what is replaced
-  b->loaded = b->own_out = b->indexed = b->g.enqueued = b->raw = false;
+  b->loaded = b->own_out = b->indexed = b->g.enqueued = b->pl.enqueued = b->raw = false;
   std::vector<uint64_t> n(ns), w(ns), g(ns);
   std::vector<BatchDesc> desc(ns);
   std::vector<gh_sym> syms;
@@ -2130,6 +2143,113 @@ extern "C" int gh_batchdec_kernel_shape(gh_batch* b, char* buf, size_t cap) {
 
 extern "C" int gh_batchdec_kernel_shapes(char* buf, size_t cap) {
   return copy_name(std::string(bgather_kern_for(false).name) + "\n" + bgather_kern_for(true).name + "\n", buf, cap);
+}
+
+// ---- byte planes (gaphuff.h; kernel: gh_planes_join.hip; layout: gh_planes_layout) -----------
+constexpr uint32_t PLANES_JOIN_LAUNCHES = 2;  // the counter's memset, the join kernel
+
+// A member of the batch's queue as the gather is: after the queue's last run, its end the
+// queue's `done`.
+extern "C" int gh_planes_join_device(gh_batch* b, const gh_planes_item* items, uint32_t ntensors, const void* d_stored,
+                                     uint64_t stored_len, void* hip_stream, int timed) {
+  if (!b || (ntensors && !items)) return fail(GH_E_ARG, "null argument");
+  if (!b->loaded || !b->q.enqueued || !b->own_out)
+    return fail(GH_E_STATE, "gh_planes_join_device without a decode into the batch's own arena since the load");
+  if ((uintptr_t)d_stored & 15u) return fail(GH_E_ARG, "stored arena not 16-byte aligned");
+  std::vector<gh_planes_slot> slots((size_t)PLANES_MAX_E * std::max(ntensors, 1u));
+  uint32_t ns = 0;
+  uint64_t stored_bytes = 0;
+  if (int rc = gh_planes_layout(items, ntensors, slots.data(), &ns, &stored_bytes)) return rc;
+  if (ns != b->nstreams) return fail(GH_E_ARG, "the tensors' coded planes are not the loaded batch's streams");
+  if (stored_bytes && !d_stored) return fail(GH_E_ARG, "null stored arena");
+  if (stored_len < stored_bytes) return fail(GH_E_SMALL, "stored arena smaller than the stored planes");
+  // the tensors' descriptors, then their unit prefix, in one upload
+  const size_t dbytes = sizeof(PlanesTensor) * (size_t)ntensors;
+  std::vector<uint8_t> up(dbytes + 4ull * (ntensors + 1));
+  PlanesTensor* d = (PlanesTensor*)up.data();
+  std::vector<uint32_t> unit0(ntensors + 1);
+  uint64_t units = 0, out_bytes = 0;
+  for (uint32_t t = 0; t < ntensors; ++t) {
+    const gh_planes_item& it = items[t];
+    const std::string who = "tensor " + std::to_string(t) + ": ";
+    if (it.nelem && !it.data) return fail(GH_E_ARG, who + "null pointer");
+    unit0[t] = (uint32_t)units;
+    units += planes_units(it.nelem);
+    if (units >= PLANES_MAX_UNITS) return fail(GH_E_ARG, who + "the list reaches 2^31 work units");
+    out_bytes += it.nelem * it.elem_size;  // (every nelem is a loaded stream's n or fills a stored plane)
+    d[t] = PlanesTensor{};
+    d[t].data = (uint8_t*)it.data;
+    d[t].nelem = it.nelem;
+    d[t].elem = it.elem_size;
+    d[t].mask = it.coded_mask;
+    for (uint32_t p = 0; p < it.elem_size; ++p) {
+      const gh_planes_slot& s = slots[PLANES_MAX_E * t + p];
+      d[t].stream[p] = s.stream;
+      if (s.stream == GH_PLANES_STORED) {
+        d[t].off[p] = s.stored_off;
+        continue;
+      }
+      if (b->n[s.stream] != it.nelem) return fail(GH_E_ARG, who + "nelem differs from its stream's n in the loaded batch");
+      d[t].off[p] = b->plan.ext[s.stream].out_off;
+    }
+  }
+  unit0[ntensors] = (uint32_t)units;
+  std::memcpy(up.data() + dbytes, unit0.data(), 4ull * (ntensors + 1));
+  GH_HIP(hipSetDevice(b->q.device));
+  BatchPlanes& pl = b->pl;
+  if (int rc = pl.ev.create()) return rc;
+  if (pl.enqueued) GH_HIP(hipEventSynchronize(b->q.done));  // (the last join may still read the old upload)
+  if (int rc = upload_at_least(pl.desc, up.data(), up.size())) return rc;
+  if (int rc = pl.words.reserve(16)) return rc;
+  PlanesJoinParams jp{};
+  jp.desc = pl.desc.get<PlanesTensor>();
+  jp.unit0 = (const uint32_t*)(pl.desc.get<uint8_t>() + dbytes);
+  jp.out = b->out.get<uint8_t>();
+  jp.stored = (const uint8_t*)d_stored;
+  jp.status = b->flags.get<unsigned int>() + 4;
+  jp.bad = pl.words.get<unsigned int>();
+  jp.ntensors = ntensors;
+  jp.nunits = (uint32_t)units;
+  // GH_PLANES_GRID=k (tests): k workgroups, so that one wave walks many units and tensors
+  const uint32_t grid = unit_grid("GH_PLANES_GRID", units, PJ_WAVES, b->q.num_cu);
+  void* ja[1] = {&jp};
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)b->q.stream;
+  GH_HIP(hipStreamWaitEvent(st, b->q.done, 0));
+  GH_HIP(hipMemsetAsync(pl.words.get(), 0, 16, st));
+  if (timed) GH_HIP(hipEventRecord(pl.ev.a, st));  // (the join alone)
+  if (units) GH_HIP(hipLaunchKernel((const void*)gh_planes_join_kernel, dim3(grid), dim3(PJ_TB), ja, 0, st));
+  GH_HIP(hipGetLastError());
+  if (timed) GH_HIP(hipEventRecord(pl.ev.b, st));
+  GH_HIP(hipEventRecord(b->q.done, st));
+  pl.enqueued = true;
+  pl.timed = timed != 0;
+  pl.out_bytes = out_bytes;
+  pl.ntensors = ntensors;
+  return GH_OK;
+}
+
+extern "C" int gh_planes_wait(gh_batch* b, gh_planes_report* rep) {
+  if (rep) *rep = gh_planes_report{};
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded || !b->pl.enqueued) return fail(GH_E_STATE, "gh_planes_wait without a join since the load");
+  GH_HIP(hipSetDevice(b->q.device));
+  GH_HIP(hipEventSynchronize(b->q.done));
+  unsigned int bad = 0;
+  GH_HIP(hipMemcpy(&bad, b->pl.words.get(), sizeof(bad), hipMemcpyDeviceToHost));
+  float ms = 0;
+  if (b->pl.timed)
+    if (int rc = b->pl.ev.elapsed(&ms)) return rc;
+  if (rep) {
+    rep->out_bytes = b->pl.out_bytes;
+    rep->ntensors = b->pl.ntensors;
+    rep->bad_tensors = bad;
+    rep->kernel_ms = ms;
+    rep->launches = PLANES_JOIN_LAUNCHES;
+  }
+  if (bad)
+    return fail(GH_E_CORRUPT, std::to_string(bad) + " tensor(s) have a coded plane the decode flagged (gh_batch_status "
+                                                    "names its stream); their bytes were left as they were");
+  return GH_OK;
 }
 
 // Decode time of a set of shards: decodes on one device run in turn (DevChain), so a

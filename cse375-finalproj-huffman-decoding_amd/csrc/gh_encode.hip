@@ -32,6 +32,8 @@
 //                        the stream's device-resident arrays: see enc_merge_span.
 // Batched encode (gh_ebatch_*): many inputs with their own codes, wave-sized units; its
 // kernels are in gh_ebatch.hip, its host side at the end of this file.
+// Byte planes (gh_planes_load, gh_planes_load_device): a batched encode whose streams are the
+// coded byte planes of typed tensors; the split kernel is in gh_planes_split.hip.
 // Sliced encode (gh_ectx_encode_slice): the same kernels on an input that is one slice of
 // a longer stream; the block scan starts at the slice's first stream bit and the write
 // kernel's SLICE variant indexes its outputs from the slice's origin; the index kernel's
@@ -58,6 +60,7 @@
 #include "gaphuff.h"
 #include "gh_hip.hpp"
 #include "gh_internal.hpp"
+#include "gh_planes.hpp"
 #include "gh_pm_flat.hpp"
 #include "gh_units.hpp"
 #include "gh_wave.hpp"
@@ -676,6 +679,7 @@ __global__ __launch_bounds__(MERGE_TB) void gh_enc_merge_kernel(const EncMergePa
 }
 
 #include "gh_ebatch.hip"
+#include "gh_planes_split.hip"
 
 }  // namespace gh
 
@@ -1265,6 +1269,8 @@ static const char* const EBATCH_SHAPE = "ebatch<lut=1>";
 
 struct gh_ebatch {
   EventPair ev_hist, ev_code;
+  EventPair ev_split;                      // gh_planes_load_device: around the split kernel
+  bool split_timed = false;                // the last load was gh_planes_load_device and launched it
   DevBuf in, unit0, items;                 // the loaded batch
   DevBuf code;                             // one EBatchDesc per stream, then 256 table entries per stream
   DevBuf counts;                           // 256 u64 per stream
@@ -1310,17 +1316,17 @@ static std::vector<EBatchDesc> ebatch_descs(const gh_ebatch* b) {
   return d;
 }
 
-// src[i]: stream i's bytes, host memory or (device) device memory.
-static int ebatch_load(gh_ebatch* b, const std::vector<const uint8_t*>& src, const uint64_t* n, bool device,
-                       void* hip_stream) {
-  const uint32_t ns = (uint32_t)src.size();
+// A load's first half: the previous batch retired, the input plan of ns streams of n[i] bytes.
+static int ebatch_load_plan(gh_ebatch* b, const uint64_t* n, uint32_t ns, EBatchInPlan& inp) {
   GH_HIP(hipSetDevice(b->q.device));
   if (int rc = b->q.quiesce()) return rc;  // the previous batch's encode reads what is replaced
-  b->loaded = b->planned = false;
-  EBatchInPlan inp;
-  if (int rc = ebatch_in_plan(n, ns, inp)) return rc;
-  for (uint32_t i = 0; i < ns; ++i)
-    if (n[i] && !src[i]) return fail(GH_E_ARG, "stream " + std::to_string(i) + ": null input pointer");
+  b->loaded = b->planned = b->split_timed = false;
+  return ebatch_in_plan(n, ns, inp);
+}
+
+// Its second half, up to the arena's bytes: the batch's sizes, the unit prefix and the
+// descriptors uploaded, the input arena reserved.
+static int ebatch_load_reserve(gh_ebatch* b, const uint64_t* n, uint32_t ns, EBatchInPlan&& inp) {
   b->n.assign(n, n + ns);
   b->nstreams = ns;
   b->inp = std::move(inp);
@@ -1332,7 +1338,19 @@ static int ebatch_load(gh_ebatch* b, const std::vector<const uint8_t*>& src, con
   // (room for the tables too: gh_ebatch_plan uploads the descriptors again, with them)
   if (int rc = b->code.reserve(std::max<uint64_t>((sizeof(EBatchDesc) + 1024ull) * ns, 16))) return rc;
   if (int rc = upload_at_least(b->code, ebatch_descs(b).data(), sizeof(EBatchDesc) * (uint64_t)ns)) return rc;
-  if (int rc = b->in.reserve(std::max<uint64_t>(ip.in_bytes, 16))) return rc;
+  return b->in.reserve(std::max<uint64_t>(ip.in_bytes, 16));
+}
+
+// src[i]: stream i's bytes, host memory or (device) device memory.
+static int ebatch_load(gh_ebatch* b, const std::vector<const uint8_t*>& src, const uint64_t* n, bool device,
+                       void* hip_stream) {
+  const uint32_t ns = (uint32_t)src.size();
+  EBatchInPlan inp;
+  if (int rc = ebatch_load_plan(b, n, ns, inp)) return rc;
+  for (uint32_t i = 0; i < ns; ++i)
+    if (n[i] && !src[i]) return fail(GH_E_ARG, "stream " + std::to_string(i) + ": null input pointer");
+  if (int rc = ebatch_load_reserve(b, n, ns, std::move(inp))) return rc;
+  const EBatchInPlan& ip = b->inp;
   if (!device) {
     // the arena is assembled in host memory, padding included, and goes up in one copy
     std::vector<uint8_t> stage(ip.in_bytes, 0);
@@ -1370,6 +1388,122 @@ extern "C" int gh_ebatch_load_device(gh_ebatch* b, const gh_ebatch_item* items, 
     n[i] = items[i].n;
   }
   return ebatch_load(b, src, n.data(), true, hip_stream);
+}
+
+// ---- byte planes (gaphuff.h; kernel: gh_planes_split.hip; layout: gh_planes_layout) ----------
+// The layout of a tensor list and what both loads derive from it: n[s] of every coded plane's
+// stream and the prefix of the tensors' unit counts.
+struct PlanesList {
+  std::vector<gh_planes_slot> slots;
+  std::vector<uint64_t> n;
+  std::vector<uint32_t> unit0;  // ntensors + 1
+  uint32_t nstreams = 0;
+  uint64_t stored_bytes = 0;
+};
+
+static int planes_list(const gh_planes_item* items, uint32_t nt, const void* stored, uint64_t stored_len, PlanesList& pl) {
+  pl.slots.resize((size_t)PLANES_MAX_E * std::max(nt, 1u));
+  if (int rc = gh_planes_layout(items, nt, pl.slots.data(), &pl.nstreams, &pl.stored_bytes)) return rc;
+  if (pl.stored_bytes && !stored) return fail(GH_E_ARG, "null stored arena");
+  if (stored_len < pl.stored_bytes) return fail(GH_E_SMALL, "stored arena smaller than the stored planes");
+  pl.n.resize(pl.nstreams);
+  pl.unit0.resize(nt + 1);
+  uint64_t units = 0;
+  for (uint32_t t = 0; t < nt; ++t) {
+    if (items[t].nelem && !items[t].data) return fail(GH_E_ARG, "tensor " + std::to_string(t) + ": null pointer");
+    pl.unit0[t] = (uint32_t)units;
+    units += planes_units(items[t].nelem);  // (< 2^31 + 2^54)
+    if (units >= PLANES_MAX_UNITS) return fail(GH_E_ARG, "tensor " + std::to_string(t) + ": the list reaches 2^31 work units");
+    for (uint32_t p = 0; p < items[t].elem_size; ++p)
+      if (pl.slots[PLANES_MAX_E * t + p].stream != GH_PLANES_STORED) pl.n[pl.slots[PLANES_MAX_E * t + p].stream] = items[t].nelem;
+  }
+  pl.unit0[nt] = (uint32_t)units;
+  return GH_OK;
+}
+
+extern "C" int gh_planes_load(gh_ebatch* b, const gh_planes_item* items, uint32_t ntensors, void* stored,
+                              uint64_t stored_len) {
+  if (!b || (ntensors && !items)) return fail(GH_E_ARG, "null argument");
+  PlanesList pl;
+  if (int rc = planes_list(items, ntensors, stored, stored_len, pl)) return rc;
+  // the host split: coded planes into buffers of their own, stored planes into the caller's arena
+  std::vector<std::vector<uint8_t>> coded(pl.nstreams);
+  std::vector<const uint8_t*> src(pl.nstreams);
+  if (pl.stored_bytes) std::memset(stored, 0, pl.stored_bytes);
+  for (uint32_t t = 0; t < ntensors; ++t) {
+    void* planes[PLANES_MAX_E] = {};
+    for (uint32_t p = 0; p < items[t].elem_size; ++p) {
+      const gh_planes_slot& s = pl.slots[PLANES_MAX_E * t + p];
+      if (s.stream != GH_PLANES_STORED) {
+        coded[s.stream].resize(std::max<uint64_t>(items[t].nelem, 1));
+        planes[p] = coded[s.stream].data();
+        src[s.stream] = coded[s.stream].data();
+      } else {
+        planes[p] = (uint8_t*)stored + s.stored_off;
+      }
+    }
+    if (int rc = gh_planes_split_host(&items[t], planes)) return rc;
+  }
+  return ebatch_load(b, src, pl.n.data(), false, nullptr);
+}
+
+extern "C" int gh_planes_load_device(gh_ebatch* b, const gh_planes_item* items, uint32_t ntensors, void* d_stored,
+                                     uint64_t stored_len, void* hip_stream) {
+  if (!b || (ntensors && !items)) return fail(GH_E_ARG, "null argument");
+  if ((uintptr_t)d_stored & 15u) return fail(GH_E_ARG, "stored arena not 16-byte aligned");
+  PlanesList pl;
+  if (int rc = planes_list(items, ntensors, d_stored, stored_len, pl)) return rc;
+  const uint32_t ns = pl.nstreams;
+  EBatchInPlan inp;
+  if (int rc = ebatch_load_plan(b, pl.n.data(), ns, inp)) return rc;
+  if (int rc = ebatch_load_reserve(b, pl.n.data(), ns, std::move(inp))) return rc;
+  if (pl.unit0[ntensors]) {
+    // the tensors' descriptors, then their unit prefix, in one upload
+    const size_t dbytes = sizeof(PlanesTensor) * (size_t)ntensors;
+    std::vector<uint8_t> up(dbytes + 4ull * (ntensors + 1));
+    PlanesTensor* d = (PlanesTensor*)up.data();
+    for (uint32_t t = 0; t < ntensors; ++t) {
+      d[t] = PlanesTensor{};
+      d[t].data = (uint8_t*)items[t].data;
+      d[t].nelem = items[t].nelem;
+      d[t].elem = items[t].elem_size;
+      d[t].mask = items[t].coded_mask;
+      for (uint32_t p = 0; p < items[t].elem_size; ++p) {
+        const gh_planes_slot& s = pl.slots[PLANES_MAX_E * t + p];
+        d[t].stream[p] = s.stream;
+        d[t].off[p] = s.stream != GH_PLANES_STORED ? b->inp.ext[s.stream].in_off : s.stored_off;
+      }
+    }
+    std::memcpy(up.data() + dbytes, pl.unit0.data(), 4ull * (ntensors + 1));
+    if (int rc = upload_at_least(b->items, up.data(), up.size())) return rc;
+    PlanesSplitParams sp{};
+    sp.desc = b->items.get<PlanesTensor>();
+    sp.unit0 = (const uint32_t*)(b->items.get<uint8_t>() + dbytes);
+    sp.in = b->in.get<uint8_t>();
+    sp.stored = (uint8_t*)d_stored;
+    sp.ntensors = ntensors;
+    sp.nunits = pl.unit0[ntensors];
+    // GH_PLANES_GRID=k (tests): k workgroups, so that one wave walks many units and tensors
+    const uint32_t grid = unit_grid("GH_PLANES_GRID", sp.nunits, PL_WAVES, b->q.num_cu);
+    // after what the producer's stream holds now, then one split kernel on the batch's stream
+    if (int rc = b->ev_split.create()) return rc;
+    if (int rc = b->q.follow(hip_stream)) return rc;
+    GH_HIP(hipEventRecord(b->ev_split.a, b->q.stream));
+    hipLaunchKernelGGL(gh_planes_split_kernel, dim3(grid), dim3(PL_TB), 0, b->q.stream, sp);
+    GH_HIP(hipGetLastError());
+    GH_HIP(hipEventRecord(b->ev_split.b, b->q.stream));
+    GH_HIP(hipStreamSynchronize(b->q.stream));
+    b->split_timed = true;
+  }
+  b->loaded = true;
+  return GH_OK;
+}
+
+extern "C" int gh_planes_load_times(gh_ebatch* b, float* kernel_ms) {
+  if (!b || !kernel_ms) return fail(GH_E_ARG, "null argument");
+  *kernel_ms = 0;
+  if (!b->loaded) return fail(GH_E_STATE, "gh_planes_load_times before a load");
+  return b->split_timed ? b->ev_split.elapsed(kernel_ms) : (int)GH_OK;
 }
 
 static EBatchParams ebatch_params(const gh_ebatch* b) {

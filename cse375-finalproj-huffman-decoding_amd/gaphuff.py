@@ -73,8 +73,12 @@ EXPORTED = (
     "gh_batchdec_gather_pieces", "gh_batchdec_plan", "gh_batchdec_kernel_shape", "gh_batchdec_kernel_shapes",
     "gh_batchraw_load", "gh_batchraw_load_device", "gh_batchraw_gaps", "gh_batchraw_report_get",
     "gh_batchraw_gaps_host", "gh_batchraw_kernel_shape", "gh_batchraw_kernel_shapes",
+    "gh_planes_layout", "gh_planes_split_host", "gh_planes_join_host", "gh_planes_load", "gh_planes_load_device",
+    "gh_planes_load_times", "gh_planes_join_device", "gh_planes_wait", "gh_planes_image_bytes", "gh_planes_image_write", "gh_planes_parse",
 )
 GH_EBATCH_UNIT_BYTES = 1024
+GH_PLANES_STORED = 0xFFFFFFFF
+GH_PLANES_MAGIC = 0x0000314E4C504847
 
 
 class GapHuffError(RuntimeError):
@@ -181,6 +185,25 @@ class gh_ebatch_report(ctypes.Structure):
     _fields_ = [("in_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("nstreams", ctypes.c_uint32),
                 ("status", ctypes.c_uint32), ("hist_ms", ctypes.c_float), ("plan_host_ms", ctypes.c_float),
                 ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
+
+
+class gh_planes_item(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("nelem", ctypes.c_uint64), ("elem_size", ctypes.c_uint32),
+                ("coded_mask", ctypes.c_uint32)]
+
+
+class gh_planes_slot(ctypes.Structure):
+    _fields_ = [("stream", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("stored_off", ctypes.c_uint64)]
+
+
+class gh_planes_report(ctypes.Structure):
+    _fields_ = [("out_bytes", ctypes.c_uint64), ("ntensors", ctypes.c_uint32), ("bad_tensors", ctypes.c_uint32),
+                ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
+
+
+class gh_planes_image(ctypes.Structure):
+    _fields_ = [("nelem", ctypes.c_uint64), ("elem_size", ctypes.c_uint32), ("coded_mask", ctypes.c_uint32),
+                ("plane", ctypes.c_void_p * 8), ("plane_bytes", ctypes.c_uint64 * 8), ("stream", gh_stream * 8)]
 
 
 class gh_sync_report(ctypes.Structure):
@@ -336,6 +359,18 @@ def lib() -> ctypes.CDLL:
             "gh_ebatch_items": ([P, ctypes.POINTER(gh_batch_item), U32], I),
             "gh_ebatch_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_ebatch_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_planes_layout": ([ctypes.POINTER(gh_planes_item), U32, ctypes.POINTER(gh_planes_slot),
+                                  ctypes.POINTER(U32), ctypes.POINTER(U64)], I),
+            "gh_planes_split_host": ([ctypes.POINTER(gh_planes_item), ctypes.POINTER(P)], I),
+            "gh_planes_join_host": ([ctypes.POINTER(gh_planes_item), ctypes.POINTER(P)], I),
+            "gh_planes_load": ([P, ctypes.POINTER(gh_planes_item), U32, P, U64], I),
+            "gh_planes_load_device": ([P, ctypes.POINTER(gh_planes_item), U32, P, U64, P], I),
+            "gh_planes_load_times": ([P, ctypes.POINTER(ctypes.c_float)], I),
+            "gh_planes_join_device": ([P, ctypes.POINTER(gh_planes_item), U32, P, U64, P, I], I),
+            "gh_planes_wait": ([P, ctypes.POINTER(gh_planes_report)], I),
+            "gh_planes_image_bytes": ([U32, P, ctypes.POINTER(U64)], I),
+            "gh_planes_image_write": ([ctypes.POINTER(gh_planes_item), ctypes.POINTER(P), P, P, U64], I),
+            "gh_planes_parse": ([P, ctypes.c_size_t, ctypes.POINTER(gh_planes_image)], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -1226,6 +1261,21 @@ class BatchDecoder(_Handle):
         """Name of the kernel instantiations the last load picked (gh_batch_kernel_shape)."""
         return _name(lib().gh_batch_kernel_shape, self._h)
 
+    def join_planes_device(self, items, stored_ptr: int = 0, stored_len: int = 0, hip_stream: int = 0,
+                           timed: bool = True) -> None:
+        """Enqueue the byte-plane join after a :meth:`decode` into the batch's own arena
+        (gh_planes_join_device): ``items`` are ``(device address, nelem, elem_size, coded_mask)``
+        destinations whose coded planes are the loaded streams in order; the stored planes are
+        read from the 16-byte-aligned device arena at ``stored_ptr``.  Returns without waiting."""
+        arr, n = _planes_items(items)
+        _check(lib().gh_planes_join_device(self._h, arr, n, ctypes.c_void_p(stored_ptr or None), stored_len,
+                                           ctypes.c_void_p(hip_stream or None), int(timed)))
+
+    def planes_wait(self) -> gh_planes_report:
+        """Wait for the decode and the join and return the join's report; raises
+        :class:`GapHuffError` (with the report as ``.report``) when a tensor was skipped."""
+        return self._wait(lib().gh_planes_wait, gh_planes_report())
+
 
 def decode_batch(images, device: int = 0) -> list:
     """Decode many compressed.huff images as one batch; returns their bytes in order."""
@@ -1286,6 +1336,36 @@ class BatchEncoder(_Handle):
             arr[i].d_in, arr[i].n = ptr or None, n
         _check(lib().gh_ebatch_load_device(self._h, arr, len(items), ctypes.c_void_p(hip_stream or None)))
         self.ns = [int(n) for _, n in items]
+
+    def load_planes(self, arrays, coded_masks=None) -> np.ndarray:
+        """Load typed tensors from host memory (gh_planes_load): ``arrays`` are numpy arrays of
+        1-, 2-, 4- or 8-byte elements, ``coded_masks`` one mask per tensor (default: the top
+        plane).  The coded planes are the batch's streams; returns the stored arena (np.uint8,
+        laid out by :func:`planes_layout`)."""
+        arrs, items = _planes_host_items(arrays, coded_masks)
+        arr, n = _planes_items(items)
+        _, nstreams, stored_bytes = planes_layout(items)
+        stored = np.zeros(stored_bytes, dtype=np.uint8)
+        _check(lib().gh_planes_load(self._h, arr, n, _ptr(stored) if stored.size else None, stored.size))
+        self.ns = [int(it[1]) for it in items for p in range(it[2]) if (it[3] >> p) & 1]
+        return stored
+
+    def load_planes_device(self, items, stored_ptr: int = 0, stored_len: int = 0, hip_stream: int = 0) -> None:
+        """Load typed tensors from device memory (gh_planes_load_device): ``items`` are
+        ``(device address, nelem, elem_size, coded_mask)``, any byte alignment; one split kernel
+        writes the coded planes into the batch and the stored planes into the 16-byte-aligned
+        device arena at ``stored_ptr`` (``stored_len`` >= :func:`planes_layout`'s size)."""
+        items = list(items)
+        arr, n = _planes_items(items)
+        _check(lib().gh_planes_load_device(self._h, arr, n, ctypes.c_void_p(stored_ptr or None), stored_len,
+                                           ctypes.c_void_p(hip_stream or None)))
+        self.ns = [int(it[1]) for it in items for p in range(it[2]) if (it[3] >> p) & 1]
+
+    def planes_load_ms(self) -> float:
+        """HIP-event time of the last :meth:`load_planes_device`'s split kernel (gh_planes_load_times)."""
+        ms = ctypes.c_float(0)
+        _check(lib().gh_planes_load_times(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def plan(self, force_version: int = 0, threads: int = 0) -> None:
         """Every stream's histogram (one launch) and host plan (gh_ebatch_plan); synchronous."""
@@ -1357,6 +1437,177 @@ def encode_batch(datas, device: int = 0, device_plan: bool = False) -> list:
         b.encode()
         b.wait()
         return b.download_all()
+
+
+# --------------------------------------------------------------------------- byte planes
+def _planes_items(items):
+    """``(address, nelem, elem_size, coded_mask)`` tuples as the C array of gh_planes_item."""
+    items = list(items)
+    arr = (gh_planes_item * max(1, len(items)))()
+    for i, (ptr, nelem, e, mask) in enumerate(items):
+        arr[i].data, arr[i].nelem, arr[i].elem_size, arr[i].coded_mask = ptr or None, nelem, e, mask
+    return arr, len(items)
+
+
+def default_planes_mask(elem_size: int) -> int:
+    """The top plane alone (sign and exponent of a float); the one plane of 1-byte elements."""
+    return 1 << (elem_size - 1)
+
+
+def _planes_host_items(arrays, coded_masks=None):
+    """Contiguous copies of ``arrays`` (kept alive by the caller) and their item tuples."""
+    arrs = [np.ascontiguousarray(a) for a in arrays]
+    masks = [None] * len(arrs) if coded_masks is None else list(coded_masks)
+    if len(masks) != len(arrs):
+        raise GapHuffError(-1, "one coded mask per tensor")
+    items = []
+    for a, m in zip(arrs, masks):
+        e = a.dtype.itemsize
+        items.append((a.ctypes.data if a.size else 0, a.size, e, default_planes_mask(e) if m is None else int(m)))
+    return arrs, items
+
+
+def planes_layout(items):
+    """The layout of a tensor list (gh_planes_layout; needs no device): ``items`` are
+    ``(address, nelem, elem_size, coded_mask)``; returns ``(slots, nstreams, stored_bytes)``
+    with ``slots[t][p] = (stream, stored_off)`` for all 8 plane slots of every tensor
+    (``stream == GH_PLANES_STORED`` for a stored or absent plane)."""
+    arr, n = _planes_items(items)
+    slots = (gh_planes_slot * max(1, 8 * n))()
+    ns, sb = ctypes.c_uint32(), ctypes.c_uint64()
+    _check(lib().gh_planes_layout(arr, n, slots, ctypes.byref(ns), ctypes.byref(sb)))
+    out = [[(int(slots[8 * t + p].stream), int(slots[8 * t + p].stored_off)) for p in range(8)] for t in range(n)]
+    return out, int(ns.value), int(sb.value)
+
+
+def planes_split_host(a, elem_size: Optional[int] = None) -> list:
+    """The byte planes of ``a`` by the CPU twin of the split kernel (gh_planes_split_host): a
+    list of ``elem_size`` np.uint8 arrays.  ``a``: a numpy array of 1/2/4/8-byte elements, or
+    bytes with ``elem_size`` given."""
+    raw = _u8(a) if elem_size is not None else np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    e = elem_size if elem_size is not None else np.asarray(a).dtype.itemsize
+    if e < 1 or raw.size % e:
+        raise GapHuffError(-1, "the tensor's bytes are no multiple of elem_size")
+    nelem = raw.size // e
+    planes = [np.empty(nelem, dtype=np.uint8) for _ in range(e)]
+    it = gh_planes_item(raw.ctypes.data if raw.size else None, nelem, e, 0)
+    ptrs = (ctypes.c_void_p * 8)(*[p.ctypes.data if p.size else None for p in planes])
+    _check(lib().gh_planes_split_host(ctypes.byref(it), ptrs))
+    return planes
+
+
+def planes_join_host(planes) -> np.ndarray:
+    """The tensor's bytes (np.uint8, ``nelem * len(planes)``) from its byte planes, by the CPU
+    twin of the join kernel (gh_planes_join_host)."""
+    pl = [_u8(p) for p in planes]
+    e, nelem = len(pl), (pl[0].size if pl else 0)
+    if any(p.size != nelem for p in pl):
+        raise GapHuffError(-1, "planes of different sizes")
+    out = np.empty(nelem * e, dtype=np.uint8)
+    it = gh_planes_item(out.ctypes.data if out.size else None, nelem, e, 0)
+    ptrs = (ctypes.c_void_p * 8)(*[p.ctypes.data if p.size else None for p in pl])
+    _check(lib().gh_planes_join_host(ctypes.byref(it), ptrs))
+    return out
+
+
+def planes_image(nelem: int, elem_size: int, coded_mask: int, planes) -> np.ndarray:
+    """The container of one tensor (gh_planes_image_write): ``planes[p]`` is a compressed.huff
+    image for a coded plane and the ``nelem`` raw bytes of a stored one."""
+    pl = [_u8(p) for p in planes]
+    if len(pl) != elem_size:
+        raise GapHuffError(-1, "one plane per byte of the element")
+    nb = np.asarray([p.size for p in pl], dtype=np.uint64)
+    total = ctypes.c_uint64()
+    _check(lib().gh_planes_image_bytes(elem_size, _ptr(nb), ctypes.byref(total)))
+    out = np.zeros(int(total.value), dtype=np.uint8)
+    it = gh_planes_item(None, nelem, elem_size, coded_mask)
+    ptrs = (ctypes.c_void_p * 8)(*[p.ctypes.data if p.size else None for p in pl])
+    _check(lib().gh_planes_image_write(ctypes.byref(it), ptrs, _ptr(nb), _ptr(out), out.size))
+    return out
+
+
+@dataclass
+class PlanesImage:
+    """A parsed byte-plane container (keeps the file bytes alive).  ``planes[p]``: a
+    :class:`Stream` for a coded plane, the raw bytes (np.uint8 view) for a stored one."""
+
+    raw: np.ndarray
+    nelem: int
+    elem_size: int
+    coded_mask: int
+    planes: list
+
+
+def parse_planes(image) -> PlanesImage:
+    """Parse a byte-plane container (gh_planes_parse); GH_E_FORMAT when it is not one."""
+    raw = _u8(image)
+    im = gh_planes_image()
+    _check(lib().gh_planes_parse(_ptr(raw), raw.size, ctypes.byref(im)))
+    planes = []
+    for p in range(im.elem_size):
+        off, nb = int(im.plane[p] or raw.ctypes.data) - raw.ctypes.data, int(im.plane_bytes[p])
+        view = raw[off: off + nb]
+        planes.append(parse(view) if (im.coded_mask >> p) & 1 else view)
+    return PlanesImage(raw, int(im.nelem), int(im.elem_size), int(im.coded_mask), planes)
+
+
+def encode_tensors(arrays, coded_masks=None, device: int = 0, device_plan: bool = False) -> list:
+    """Encode typed tensors (numpy arrays of 1/2/4/8-byte elements) as one batch on the GPU and
+    return their containers.  ``coded_masks``: one mask per tensor; default the top plane alone
+    (the one plane for 1-byte elements).  ``device_plan``: build the codes on the GPU."""
+    arrs, items = _planes_host_items(arrays, coded_masks)
+    slots, _, stored_bytes = planes_layout(items)
+    with BatchEncoder(device) as b:
+        bufs = [DeviceBuffer(max(a.nbytes, 16), device).upload(a.reshape(-1).view(np.uint8)) if a.size
+                else DeviceBuffer(16, device) for a in arrs]
+        with DeviceBuffer(max(stored_bytes, 16), device) as st:
+            try:
+                b.load_planes_device([(buf.addr, it[1], it[2], it[3]) for buf, it in zip(bufs, items)], st.addr,
+                                     stored_bytes)
+            finally:
+                for buf in bufs:
+                    buf.close()
+            stored = st.download(np.empty(stored_bytes, dtype=np.uint8)) if stored_bytes else np.zeros(0, np.uint8)
+        if device_plan:
+            b.plan_device()
+        else:
+            b.plan()
+        b.encode()
+        b.wait()
+        images = b.download_all()
+    out = []
+    for (_, nelem, e, mask), sl in zip(items, slots):
+        planes = [images[s] if s != GH_PLANES_STORED else stored[off: off + nelem] for s, off in sl[:e]]
+        out.append(planes_image(nelem, e, mask, planes))
+    return out
+
+
+def decode_tensors(images, device: int = 0) -> list:
+    """Decode byte-plane containers as one batch on the GPU; returns every tensor's bytes
+    (np.uint8, ``nelem * elem_size``)."""
+    with BatchDecoder(device) as b:
+        parsed = [im if isinstance(im, PlanesImage) else parse_planes(im) for im in images]
+        shapes = [(0, im.nelem, im.elem_size, im.coded_mask) for im in parsed]
+        slots, _, stored_bytes = planes_layout(shapes)
+        stored = np.zeros(stored_bytes, dtype=np.uint8)
+        streams = []
+        for im, sl in zip(parsed, slots):
+            for p in range(im.elem_size):
+                if sl[p][0] != GH_PLANES_STORED:
+                    streams.append(im.planes[p])
+                else:
+                    stored[sl[p][1]: sl[p][1] + im.nelem] = im.planes[p]
+        b.load(streams)
+        b.decode()
+        sizes = [im.nelem * im.elem_size for im in parsed]
+        offs = np.concatenate([[0], np.cumsum([-(-n // 16) * 16 for n in sizes])]).astype(np.int64)
+        with DeviceBuffer(max(int(offs[-1]), 16), device) as dst, DeviceBuffer(max(stored_bytes, 16), device) as st:
+            if stored_bytes:
+                st.upload(stored)
+            b.join_planes_device([(dst.addr + int(o), s[1], s[2], s[3]) for o, s in zip(offs, shapes)], st.addr, stored_bytes)
+            b.planes_wait()
+            whole = dst.download(np.empty(int(offs[-1]), dtype=np.uint8)) if offs[-1] else np.zeros(0, np.uint8)
+        return [whole[int(o): int(o) + n].copy() for o, n in zip(offs, sizes)]
 
 
 # --------------------------------------------------------------------------- random access

@@ -6,6 +6,9 @@
 // (gh_batch_*: one fixed set of launches however many streams) and writes every output.
 // When every input is a raw container the batch is loaded by gh_batchraw_load (the gap arrays
 // are built on the GPU); a list that mixes the two kinds is refused.
+// When every input is a byte-plane container (bin/encoder --batch LIST --planes E, GH_PLANES_MAGIC)
+// the coded planes of all tensors are the batch's streams and one join kernel after the decode
+// interleaves them with the stored planes (gh_planes_join_device); every output is a tensor's bytes.
 // --batch LIST --ranges FILE OUT (FILE: one `STREAM LO:HI` per line, STREAM the 0-based line
 // of LIST, blank lines not counted) indexes the batch without decoding it and gathers only the
 // named byte ranges (gh_batchdec_*); their concatenation in file order goes to OUT and the
@@ -148,6 +151,91 @@ static int gather_main(const char* input, const char* output, const char* index_
   return 0;
 }
 
+// A list of byte-plane containers (img[i], all read): their coded planes decoded as one batch,
+// joined with the stored planes on the device, every tensor written to out[i].  A corrupt
+// plane: exit code 1, its tensor's line named, no output written for it.
+static int planes_batch_main(const char* list_file, const std::vector<std::string>& in, const std::vector<std::string>& out,
+                             const std::vector<size_t>& line_of, const std::vector<std::vector<uint8_t>>& img) {
+  const size_t nt = in.size();
+  std::vector<gh_planes_image> im(nt);
+  std::vector<gh_planes_item> items(nt);
+  std::vector<gh_planes_slot> slots(8 * std::max<size_t>(nt, 1));
+  int rc;
+  for (size_t i = 0; i < nt; ++i) {
+    if ((rc = gh_planes_parse(img[i].data(), img[i].size(), &im[i]))) {
+      std::fprintf(stderr, "decoder: %s: line %zu: %s: ", list_file, line_of[i], in[i].c_str());
+      return die("bad byte-plane container", rc);
+    }
+    items[i] = gh_planes_item{nullptr, im[i].nelem, im[i].elem_size, im[i].coded_mask};
+  }
+  uint32_t ns = 0;
+  uint64_t stored_bytes = 0;
+  if ((rc = gh_planes_layout(items.data(), (uint32_t)nt, slots.data(), &ns, &stored_bytes))) return die("layout", rc);
+  std::vector<gh_stream> streams(ns);
+  std::vector<uint8_t> stored((size_t)stored_bytes, 0);
+  std::vector<uint64_t> dst_off(nt + 1, 0);
+  for (size_t i = 0; i < nt; ++i) {
+    for (uint32_t p = 0; p < im[i].elem_size; ++p) {
+      const gh_planes_slot& sl = slots[8 * i + p];
+      if (sl.stream != GH_PLANES_STORED) streams[sl.stream] = im[i].stream[p];
+      else if (im[i].nelem) std::memcpy(stored.data() + sl.stored_off, im[i].plane[p], (size_t)im[i].nelem);
+    }
+    dst_off[i + 1] = dst_off[i] + ((im[i].nelem * im[i].elem_size + 15) & ~15ull);
+  }
+  if (gh_device_count() < 1) return die("no HIP device", GH_E_NODEV);
+  gh_batch* b = nullptr;
+  void *d_dst = nullptr, *d_stored = nullptr;
+  auto done = [&](int r) {
+    if (d_dst) gh_dev_free(d_dst);
+    if (d_stored) gh_dev_free(d_stored);
+    gh_batch_destroy(b);
+    return r;
+  };
+  if ((rc = gh_batch_create(0, &b))) return die("device init", rc);
+  const double t0 = now_ms();
+  if ((rc = gh_batch_load(b, streams.data(), ns))) return done(die("batch load", rc));
+  const double t1 = now_ms();
+  if ((rc = gh_dev_alloc(0, std::max<uint64_t>(dst_off[nt], 16), &d_dst)) ||
+      (rc = gh_dev_alloc(0, std::max<uint64_t>(stored_bytes, 16), &d_stored)) ||
+      (stored_bytes && (rc = gh_dev_copy(d_stored, stored.data(), stored_bytes))))
+    return done(die("device allocation", rc));
+  for (size_t i = 0; i < nt; ++i) items[i].data = (uint8_t*)d_dst + dst_off[i];
+  gh_planes_report rep{};
+  if ((rc = gh_batch_decode(b, nullptr, 0, nullptr, 1)) ||
+      (rc = gh_planes_join_device(b, items.data(), (uint32_t)nt, d_stored, stored_bytes, nullptr, 1)))
+    return done(die("batch decode", rc));
+  rc = gh_planes_wait(b, &rep);
+  const double t2 = now_ms();
+  std::vector<uint32_t> status(std::max<uint32_t>(ns, 1), 0);
+  std::vector<bool> bad(nt, false);
+  if (rc == GH_E_CORRUPT && gh_batch_status(b, status.data(), nullptr, ns) == GH_OK) {
+    for (size_t i = 0; i < nt; ++i)
+      for (uint32_t p = 0; p < im[i].elem_size; ++p) {
+        const uint32_t sidx = slots[8 * i + p].stream;
+        if (sidx == GH_PLANES_STORED || !status[sidx]) continue;
+        bad[i] = true;
+        std::fprintf(stderr, "decoder: %s: line %zu: %s: plane %u: corrupt stream (status 0x%x)\n", list_file, line_of[i],
+                     in[i].c_str(), p, status[sidx]);
+      }
+  } else if (rc) {
+    return done(die("byte-plane join", rc));
+  }
+  std::vector<uint8_t> bytes;
+  for (size_t i = 0; i < nt; ++i) {
+    if (bad[i]) continue;
+    bytes.resize((size_t)(im[i].nelem * im[i].elem_size));
+    int r = bytes.empty() ? GH_OK : gh_dev_copy(bytes.data(), items[i].data, bytes.size());
+    if (r) return done(die("download", r));
+    FILE* f = std::fopen(out[i].c_str(), "wb");
+    bool okw = f && std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (f) okw = std::fclose(f) == 0 && okw;
+    if (!okw) { std::fprintf(stderr, "decoder: cannot write %s\n", out[i].c_str()); return done(1); }
+  }
+  std::printf("Planes batch: %u tensors, %u coded planes, %llu bytes; load %.3f ms, join kernel %.3f ms, call %.3f ms, %u bad\n",
+              rep.ntensors, ns, (unsigned long long)rep.out_bytes, t1 - t0, rep.kernel_ms, t2 - t1, rep.bad_tensors);
+  return done(rc ? 1 : 0);
+}
+
 // --batch LIST: every line of the text file is `input<TAB>output`; all inputs are decoded as
 // one batch (gh_batch_*) and every output file is written.  A corrupt stream: exit code 1,
 // its line named, no output written for it.
@@ -188,7 +276,7 @@ static int batch_main(const char* list_file, const char* ranges_file = nullptr, 
   std::vector<std::vector<uint8_t>> img(ns);
   std::vector<gh_stream> streams(ns);
   std::vector<gh_raw_stream> raws;  // a list of raw containers: the batch's gap arrays are built on the GPU
-  bool raw = false;
+  bool raw = false, planes = false;
   int rc;
   for (size_t i = 0; i < ns; ++i) {
     if (!read_file(in[i].c_str(), img[i])) {
@@ -197,8 +285,16 @@ static int batch_main(const char* list_file, const char* ranges_file = nullptr, 
     }
     uint64_t magic = 0;
     if (img[i].size() >= 8) std::memcpy(&magic, img[i].data(), 8);
-    const bool is_raw = magic == GH_RAW_MAGIC;
-    if (i == 0) raw = is_raw;
+    const bool is_raw = magic == GH_RAW_MAGIC, is_planes = magic == GH_PLANES_MAGIC;
+    if (i == 0) raw = is_raw, planes = is_planes;
+    if (is_planes != planes) {
+      std::fprintf(stderr, "decoder: %s: line %zu: %s is %s, the lines before it are %s: a batch is all byte-plane "
+                           "containers or none\n", list_file, line_of[i], in[i].c_str(),
+                   is_planes ? "a byte-plane container" : "no byte-plane container",
+                   planes ? "byte-plane containers" : "compressed streams");
+      return 1;
+    }
+    if (planes) continue;
     if (is_raw != raw) {
       std::fprintf(stderr, "decoder: %s: line %zu: %s is %s, the lines before it are %s: a batch is all raw containers or all "
                            "compressed.huff files\n", list_file, line_of[i], in[i].c_str(), is_raw ? "a raw container" : "a compressed.huff file",
@@ -217,6 +313,13 @@ static int batch_main(const char* list_file, const char* ranges_file = nullptr, 
       std::fprintf(stderr, "decoder: %s: line %zu: %s: ", list_file, line_of[i], in[i].c_str());
       return die("bad compressed stream", rc);
     }
+  }
+  if (planes) {
+    if (ranges_file) {
+      std::fprintf(stderr, "decoder: %s: --ranges takes no byte-plane containers (gather a plane's stream instead)\n", list_file);
+      return 1;
+    }
+    return planes_batch_main(list_file, in, out, line_of, img);
   }
   if (gh_device_count() < 1) return die("no HIP device", GH_E_NODEV);
   gh_batch* b = nullptr;

@@ -18,6 +18,10 @@
 // on the GPU (gh_ebatch_*: each input with its own code, a fixed set of launches however
 // many inputs) and writes every output.  --device-plan builds the codes on the GPU too
 // (gh_batchenc_plan_device): the same files.
+// bin/encoder --batch LIST --planes E[:MASK] [--gpu D] [--device-plan]
+// --planes E[:MASK] treats every input as a tensor of E-byte elements (E = 1, 2, 4, 8): the
+// byte planes MASK names (default: the top plane alone) are the batch's streams, the others
+// are stored, and every output is a byte-plane container (gaphuff.h "byte planes").
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -48,14 +52,16 @@ static bool read_file(const char* path, std::vector<uint8_t>& out) {
 // --batch LIST [--gpu D] [--device-plan]: every line of the text file is `input<TAB>output` (as bin/decoder
 // --batch reads it); all inputs are encoded as one batch (gh_ebatch_*), each with its own
 // code, and every output file is written.  device_plan: gh_batchenc_plan_device instead of
-// gh_ebatch_plan.
-static int batch_main(const char* list_file, int device, bool device_plan) {
+// gh_ebatch_plan.  planes_e != 0: every input is a tensor of planes_e-byte elements whose planes
+// in planes_mask are coded (gh_planes_load), and every output a byte-plane container.
+static int batch_main(const char* list_file, int device, bool device_plan, uint32_t planes_e, uint32_t planes_mask) {
   std::vector<uint8_t> text;
   if (!read_file(list_file, text)) {
     std::fprintf(stderr, "encoder: Could not open batch list %s\n", list_file);
     return 1;
   }
   std::vector<std::string> in, out;
+  std::vector<size_t> lines;
   {
     const std::string t(text.begin(), text.end());
     size_t at = 0, line = 0;
@@ -74,6 +80,7 @@ static int batch_main(const char* list_file, int device, bool device_plan) {
       }
       in.push_back(ln.substr(0, tab));
       out.push_back(ln.substr(tab + 1));
+      lines.push_back(line);
     }
   }
   const size_t ns = in.size();
@@ -87,6 +94,25 @@ static int batch_main(const char* list_file, int device, bool device_plan) {
     }
     ptr[i] = data[i].data();
     n[i] = data[i].size();
+    if (planes_e && n[i] % planes_e) {
+      std::fprintf(stderr, "encoder: %s: line %zu: %s holds %llu bytes, no multiple of the element size %u\n", list_file,
+                   lines[i], in[i].c_str(), (unsigned long long)n[i], planes_e);
+      return 1;
+    }
+  }
+  // --planes: the tensors, their layout and the stored planes
+  std::vector<gh_planes_item> items(planes_e ? ns : 0);
+  std::vector<gh_planes_slot> slots(planes_e ? 8 * std::max<size_t>(ns, 1) : 0);
+  std::vector<uint8_t> stored;
+  uint32_t nstreams = (uint32_t)ns;
+  if (planes_e) {
+    for (size_t i = 0; i < ns; ++i) items[i] = gh_planes_item{data[i].data(), n[i] / planes_e, planes_e, planes_mask};
+    uint64_t stored_bytes = 0;
+    if (gh_planes_layout(items.data(), (uint32_t)ns, slots.data(), &nstreams, &stored_bytes)) {
+      std::fprintf(stderr, "encoder: --planes: %s\n", gh_last_error());
+      return 1;
+    }
+    stored.resize((size_t)stored_bytes);
   }
   auto die = [](const char* what, gh_ebatch* b) {
     std::fprintf(stderr, "encoder: %s: %s\n", what, gh_last_error());
@@ -96,7 +122,9 @@ static int batch_main(const char* list_file, int device, bool device_plan) {
   gh_ebatch* b = nullptr;
   if (gh_ebatch_create(device, &b)) return die("device init", nullptr);
   const double t0 = now_ms();
-  if (gh_ebatch_load(b, ptr.data(), n.data(), (uint32_t)ns)) return die("batch load", b);
+  if (planes_e ? gh_planes_load(b, items.data(), (uint32_t)ns, stored.data(), stored.size())
+               : gh_ebatch_load(b, ptr.data(), n.data(), (uint32_t)ns))
+    return die("batch load", b);
   const double t1 = now_ms();
   if (device_plan ? gh_batchenc_plan_device(b, 0) : gh_ebatch_plan(b, 0, 0)) return die("batch plan", b);
   const double t2 = now_ms();
@@ -105,12 +133,37 @@ static int batch_main(const char* list_file, int device, bool device_plan) {
   gh_ebatch_report rep{};
   if (gh_ebatch_encode(b, nullptr, 1) || gh_ebatch_wait(b, &rep)) return die("batch encode", b);
   const double t3 = now_ms();
-  std::vector<uint64_t> sizes(ns);
-  if (gh_ebatch_sizes(b, sizes.data(), (uint32_t)ns)) return die("sizes", b);
+  std::vector<uint64_t> sizes(nstreams);
+  if (gh_ebatch_sizes(b, sizes.data(), nstreams)) return die("sizes", b);
   std::vector<uint8_t> img;
+  std::vector<std::vector<uint8_t>> coded(planes_e);
+  uint64_t out_total = 0;
   for (size_t i = 0; i < ns; ++i) {
-    img.resize((size_t)sizes[i]);
-    if (gh_ebatch_download(b, (uint32_t)i, img.data(), img.size())) return die("download", b);
+    if (!planes_e) {
+      img.resize((size_t)sizes[i]);
+      if (gh_ebatch_download(b, (uint32_t)i, img.data(), img.size())) return die("download", b);
+    } else {
+      // the tensor's container: its coded planes' images and its stored planes' bytes
+      const void* planes[8] = {};
+      uint64_t plane_bytes[8] = {};
+      for (uint32_t p = 0; p < planes_e; ++p) {
+        const gh_planes_slot& sl = slots[8 * i + p];
+        if (sl.stream == GH_PLANES_STORED) {
+          planes[p] = stored.data() + sl.stored_off;
+          plane_bytes[p] = items[i].nelem;
+          continue;
+        }
+        coded[p].resize((size_t)sizes[sl.stream]);
+        if (gh_ebatch_download(b, sl.stream, coded[p].data(), coded[p].size())) return die("download", b);
+        planes[p] = coded[p].data();
+        plane_bytes[p] = coded[p].size();
+      }
+      uint64_t total = 0;
+      if (gh_planes_image_bytes(planes_e, plane_bytes, &total)) return die("container", b);
+      img.resize((size_t)total);
+      if (gh_planes_image_write(&items[i], planes, plane_bytes, img.data(), img.size())) return die("container", b);
+    }
+    out_total += img.size();
     FILE* f = std::fopen(out[i].c_str(), "wb");
     bool okw = f && std::fwrite(img.data(), 1, img.size(), f) == img.size();
     if (f) okw = std::fclose(f) == 0 && okw;
@@ -123,6 +176,9 @@ static int batch_main(const char* list_file, int device, bool device_plan) {
   gh_ebatch_destroy(b);
   char code[48] = "";
   if (device_plan) std::snprintf(code, sizeof(code), "code kernel %.3f, ", code_ms);
+  if (planes_e)
+    std::printf("Planes: %zu tensors of %u-byte elements, mask 0x%x: %u coded planes, %zu stored bytes, %llu container "
+                "bytes\n", ns, planes_e, planes_mask, nstreams, stored.size(), (unsigned long long)out_total);
   std::printf("Batch: %u streams, %llu bytes -> %llu bytes; load %.3f ms, plan %.3f ms (histogram %.3f, %shost %.3f), "
               "kernel %.3f ms, call %.3f ms\n",
               rep.nstreams, (unsigned long long)rep.in_bytes, (unsigned long long)rep.out_bytes, t1 - t0, t2 - t1,
@@ -134,16 +190,24 @@ int main(int argc, char** argv) {
   if (argc >= 3 && !std::strcmp(argv[1], "--batch")) {
     int device = 0;
     bool device_plan = false, bad = false;
+    uint32_t planes_e = 0, planes_mask = 0;
     for (int i = 3; i < argc; ++i) {
       if (!std::strcmp(argv[i], "--gpu") && i + 1 < argc) device = std::atoi(argv[++i]);
       else if (!std::strcmp(argv[i], "--device-plan")) device_plan = true;
-      else bad = true;
+      else if (!std::strcmp(argv[i], "--planes") && i + 1 < argc) {
+        char* end = nullptr;
+        planes_e = (uint32_t)std::strtoul(argv[++i], &end, 0);
+        planes_mask = planes_e >= 1 && planes_e <= 8 ? 1u << (planes_e - 1) : 0u;
+        if (*end == ':') planes_mask = (uint32_t)std::strtoul(end + 1, &end, 0);
+        if (*end || (planes_e != 1 && planes_e != 2 && planes_e != 4 && planes_e != 8) || planes_mask >> planes_e) bad = true;
+      } else bad = true;
     }
     if (bad) {
-      std::fprintf(stderr, "Usage: bin/encoder --batch LIST [--gpu D] [--device-plan]   (LIST: one input<TAB>output per line)\n");
+      std::fprintf(stderr, "Usage: bin/encoder --batch LIST [--planes E[:MASK]] [--gpu D] [--device-plan]   (LIST: one "
+                           "input<TAB>output per line; E: 1, 2, 4 or 8; MASK < 1 << E)\n");
       return 2;
     }
-    return batch_main(argv[2], device, device_plan);
+    return batch_main(argv[2], device, device_plan, planes_e, planes_mask);
   }
   if (argc < 3) {
     std::printf("Usage: bin/encoder input output\n");

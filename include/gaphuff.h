@@ -911,6 +911,109 @@ int gh_batchraw_gaps_host(const gh_sym* syms, uint32_t nsyms, const uint32_t* wo
 int gh_batchraw_kernel_shape(gh_batch* b, char* buf, size_t cap);
 int gh_batchraw_kernel_shapes(char* buf, size_t cap);
 
+/* ---- byte planes: typed tensors split, coded and joined on the GPU ---------------------- */
+/* The batch family for tensors of E-byte elements, E in {1, 2, 4, 8}.  Plane p of a tensor of
+ * nelem elements is the nelem bytes src[i * E + p]; the bytes of a float interleave one
+ * compressible plane (sign and exponent) with mantissa planes a byte code only enlarges.  A
+ * tensor's coded_mask says which planes are Huffman-coded: each is one ordinary stream of a
+ * gh_ebatch / gh_batch with its own canonical code; the other planes are stored as they are.
+ * One split kernel stands where gh_ebatch_load_device's copy kernel stands, one join kernel
+ * after gh_batch_decode; everything between is the batched encode and decode unchanged.  No
+ * reference counterpart.  (The gh_batch_*, gh_batchdec_*, gh_batchraw_* and gh_ebatch_* names
+ * are closed sets pinned by tests; these carry gh_planes_.)
+ *
+ * Layout of a tensor list: coded planes are numbered in tensor order, then plane order, and
+ * stream s has n = nelem of its tensor.  Stored planes lie in one "stored arena" by
+ * gh_batch_layout's rule: each starts on a 16-byte boundary and owns round_up(nelem, 16)
+ * bytes, zero past nelem. */
+#define GH_PLANES_STORED 0xFFFFFFFFu
+#define GH_PLANES_MAX_ELEM 8
+/* "GHPLN1\0\0" little-endian */
+#define GH_PLANES_MAGIC 0x0000314E4C504847ull
+typedef struct gh_planes_item {
+  void* data;           /* nelem * elem_size bytes, any byte alignment; host or device as the call says */
+  uint64_t nelem;
+  uint32_t elem_size;   /* 1, 2, 4, 8 */
+  uint32_t coded_mask;  /* bit p: plane p is a coded stream; clear: stored */
+} gh_planes_item;
+typedef struct gh_planes_slot { uint32_t stream, pad; uint64_t stored_off; } gh_planes_slot;
+typedef struct gh_planes_report {
+  uint64_t out_bytes;    /* sum of nelem * elem_size                                        */
+  uint32_t ntensors;
+  uint32_t bad_tensors;  /* tensors with a flagged coded plane: not one byte of them written */
+  float kernel_ms;       /* HIP-event time of the last timed join (the join alone)           */
+  uint32_t launches;     /* what one join enqueues: a constant                               */
+} gh_planes_report;
+/* slots[8 * t + p] for plane p of tensor t: a coded plane's stream number and stored_off 0; a
+ * stored plane's GH_PLANES_STORED and its offset in the stored arena; planes >= elem_size:
+ * GH_PLANES_STORED and 0.  *nstreams: coded planes; *stored_bytes: the stored arena's size.
+ * Host arithmetic only, no device.  GH_E_ARG: null pointers (items and slots may be NULL when
+ * ntensors = 0), an elem_size outside {1, 2, 4, 8}, a mask >= 1 << elem_size, more than 2^24
+ * coded planes, a sum that overflows 64 bits. */
+int gh_planes_layout(const gh_planes_item* items, uint32_t ntensors, gh_planes_slot* slots, uint32_t* nstreams,
+                     uint64_t* stored_bytes);
+/* The CPU twins of the kernels: item->data is host memory, planes[p] (p < elem_size) a buffer
+ * of nelem bytes.  Split reads the tensor and writes the planes, join the reverse.  GH_E_ARG:
+ * null pointers (with nelem > 0), a bad elem_size.  No device. */
+int gh_planes_split_host(const gh_planes_item* item, void* const* planes);
+int gh_planes_join_host(const gh_planes_item* item, const void* const* planes);
+/* gh_ebatch_load for tensors in host memory: a host split, then the host load of the coded
+ * planes as nstreams streams; the stored planes go to `stored` (host memory, stored_len >=
+ * stored_bytes: GH_E_SMALL otherwise) by the layout, zero padded.  Synchronous. */
+int gh_planes_load(gh_ebatch* b, const gh_planes_item* items, uint32_t ntensors, void* stored, uint64_t stored_len);
+/* gh_ebatch_load_device for tensors in device memory: one launch of the split kernel writes
+ * every coded plane into the batch's padded input arena (zero past nelem, as the copy kernel
+ * leaves it) and every stored plane into d_stored (device memory, 16-byte aligned: GH_E_ARG
+ * otherwise; stored_len >= stored_bytes: GH_E_SMALL otherwise), zero in [nelem,
+ * round_up(nelem, 16)); it reads exactly nelem * elem_size bytes per tensor.  Follows
+ * hip_stream as gh_ebatch_load_device.  Synchronous.  After either load gh_ebatch_plan,
+ * gh_batchenc_plan_device, encode, wait, download and items run unchanged on nstreams
+ * streams.  GH_E_ARG also when the tensors have 2^31 or more work units (1024 elements). */
+int gh_planes_load_device(gh_ebatch* b, const gh_planes_item* items, uint32_t ntensors, void* d_stored,
+                          uint64_t stored_len, void* hip_stream);
+/* HIP-event time of the split kernel of the last load when it was gh_planes_load_device (0
+ * after any other load, or when the tensors had no elements).  GH_E_STATE before a load. */
+int gh_planes_load_times(gh_ebatch* b, float* kernel_ms);
+/* Enqueue one join kernel on hip_stream (NULL = the batch's stream) and return: it runs after
+ * every earlier decode of the batch, reads the coded planes from the batch's own output arena
+ * and the stored planes from d_stored, and writes exactly nelem * elem_size bytes at every
+ * item's data (device memory, any alignment).  A tensor with a flagged coded plane (a nonzero
+ * gh_batch_status word) is not written at all and counted; every other tensor is exact.
+ * items, d_stored and the destinations must stay untouched until the wait.  GH_E_STATE unless
+ * the last decode since the load wrote the batch's own arena (d_dst == NULL); GH_E_ARG: null
+ * pointers, a layout whose nstreams or any n differs from the loaded batch's, a misaligned
+ * d_stored; GH_E_SMALL: stored_len < stored_bytes. */
+int gh_planes_join_device(gh_batch* b, const gh_planes_item* items, uint32_t ntensors, const void* d_stored,
+                          uint64_t stored_len, void* hip_stream, int timed);
+/* Wait for the decode and the join and report (rep may be NULL; it is filled before an error
+ * is returned).  GH_E_CORRUPT when bad_tensors > 0; GH_E_STATE when no join was enqueued
+ * since the load. */
+int gh_planes_wait(gh_batch* b, gh_planes_report* rep);
+
+/* The container, one tensor per image, little-endian: u64 GH_PLANES_MAGIC, u32 elem_size, u32
+ * coded_mask, u64 nelem, elem_size x u64 plane_bytes; then the planes in order, each at the
+ * next 8-byte aligned offset.  A coded plane is a whole compressed.huff image, a stored plane
+ * nelem raw bytes. */
+typedef struct gh_planes_image {
+  uint64_t nelem;
+  uint32_t elem_size, coded_mask;
+  const void* plane[GH_PLANES_MAX_ELEM];        /* views into the file                        */
+  uint64_t plane_bytes[GH_PLANES_MAX_ELEM];
+  gh_stream stream[GH_PLANES_MAX_ELEM];         /* coded planes: gh_stream_parse's output     */
+} gh_planes_image;
+/* *total: the container's size for planes of plane_bytes[0 .. elem_size).  GH_E_ARG: nulls, a
+ * bad elem_size, a sum that overflows. */
+int gh_planes_image_bytes(uint32_t elem_size, const uint64_t* plane_bytes, uint64_t* total);
+/* Write the container of item (nelem, elem_size, coded_mask; data is not read) from
+ * planes[p] / plane_bytes[p]; gaps between planes are zero.  GH_E_ARG: nulls, a bad elem_size
+ * or mask, a stored plane whose plane_bytes is not nelem; GH_E_SMALL: out_len too small. */
+int gh_planes_image_write(const gh_planes_item* item, const void* const* planes, const uint64_t* plane_bytes,
+                          void* out, uint64_t out_len);
+/* Parse a container (views into `file`).  GH_E_FORMAT unless: the magic, elem_size and the
+ * mask are right, every plane lies inside the file, a stored plane has exactly nelem bytes
+ * and every coded plane passes gh_stream_parse with n == nelem. */
+int gh_planes_parse(const void* file, size_t file_len, gh_planes_image* out);
+
 /* One-shot decode of a whole stream into host memory `out` (out_len >= N):
  * mirrors decoder_l1_l2 (decoder.cu:732-815) without its 200-iteration loop.
  * ngpus <= 0 or 1: device `devices ? devices[0] : 0`; ngpus > 1 shards the
