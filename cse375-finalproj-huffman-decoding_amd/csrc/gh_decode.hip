@@ -189,9 +189,10 @@ static std::string all_kernel_shapes() {
   return s;
 }
 
-// The lane-major load of the tile kernel reads U segments past the shard end (word
-// 4 * (nseg - 1 + U), gh_tile.hip); gh_ctx_load / gh_ctx_load_device pad the payload with
-// 16 zero words, which covers U <= 4.
+// The lane-major load of the tile kernel reads U segments past the shard end (a lane
+// clamped to segment nseg: words up to 4 * (nseg + U) - 1, gh_tile.hip); gh_ctx_load /
+// gh_ctx_load_device allocate 4 * nseg + 16 words, the tail zeroed, which covers U <= 4
+// with no word to spare.  Its gap load reads dword gwords at most of gwords + 4.
 static_assert(TILE_U <= 4 && TILE_U3 <= 4, "payload padding (16 words) covers at most 4 segments per lane");
 
 // ---- the context, by parts ---------------------------------------------------------

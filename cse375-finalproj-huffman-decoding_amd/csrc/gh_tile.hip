@@ -894,25 +894,44 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   constexpr int NSET = GH_TILE_PF2 ? 2 : 1;  // register sets of prefetched words
   static_assert(!(GH_TILE_PF2 && (GH_TILE_DYN || GH_TILE_HOLD)), "PF2: static schedule, no hold");
   uint4 wset[NSET][U];
-  uint32_t w4set[NSET][U], gwset[NSET][U];
+  uint32_t w4set[NSET][U], gwset[NSET][U];  // (chain-major) look-ahead and gap dword per chain
+  uint32_t w63set[NSET], gpset[NSET][2];    // (lane-major) lane 63's look-ahead word; the lane's gap dword pair
   auto load = [&](auto SS, uint32_t t) {
     constexpr int SI = decltype(SS)::value;
     uint4 (&w)[U] = wset[SI];
     uint32_t (&w4)[U] = w4set[SI];
     uint32_t (&gw)[U] = gwset[SI];
+    uint32_t& w63 = w63set[SI];
+    uint32_t (&gpair)[2] = gpset[SI];
     const uint32_t seg0 = min(t, p.ntiles - 1) * (uint32_t)(U * TB) + lseg;
     if constexpr (GH_TILE_LMAJ) {
-      // one lane's U consecutive segments: their 16 U bytes and the next segment's first
-      // word (chain u's look-ahead word is chain u + 1's first word); past the shard end
-      // the lane reads the zero padding (inactive)
-      const uint32_t sb = min(seg0, nseg - 1);
+      // one lane's U consecutive segments: their 16 U bytes (chain u's look-ahead word is
+      // chain u + 1's first word, chain U - 1's the next lane's first word: taken from that
+      // lane's registers when the windows are made).  A lane past the shard end is clamped
+      // to segment nseg, not nseg - 1: the last segment's look-ahead is word 4 nseg, which
+      // the lane after the last active one must hold; it reads the zero padding (4 nseg + 16
+      // words are allocated: payload word 4 (nseg + U) - 1 at most, the last one when U = 4;
+      // gh_decode.hip asserts U <= 4 beside the allocation's size).
+      const uint32_t sb = min(seg0, nseg);
 #pragma unroll
       for (int u = 0; u < U; ++u) w[u] = *(const uint4*)(p.payload + 4ull * (sb + (uint32_t)u));
-      w4[U - 1] = p.payload[4ull * (sb + (uint32_t)U)];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const uint32_t sc = sb + (uint32_t)u;
-        gw[u] = p.gaps[(p.gap_nib0 + (sc ? sc - 1u : 0u)) >> 3];
+      // lane 63 has no next lane: its look-ahead word, the first word after the wave's 64 U
+      // segments, is loaded by every lane from that one address (a single request; no branch
+      // and the same number of loads on every path: see the copy-out's fixed store count).
+      // Word 4 nseg is the last one the shard holds.
+      const uint32_t s63 = (uint32_t)__builtin_amdgcn_readlane((int)seg0, 63);
+      w63 = p.payload[4ull * min(s63 + (uint32_t)U, nseg)];
+      // the U gap nibbles gap_nib0 + sb - 1 .. + U - 1 (the first one unused when sb = 0) lie in
+      // one gap dword or in two neighbours: both, as one 8-byte load at the first one's dword
+      // (at most dword gwords of the gwords + 4 allocated).  That makes U + 2 loads per lane
+      // and tile (U + 1 + U before), followed by the copy-out's TILE_NS + 1 stores: the loop
+      // top waits vmcnt(TILE_NS + 1) once for all of them, where it used to count the U gap
+      // dwords down one by one.
+      {
+        struct __attribute__((packed, aligned(4))) gap2 { uint32_t lo, hi; };
+        const gap2 g = *(const gap2*)(p.gaps + ((p.gap_nib0 + (sb ? sb - 1u : 0u)) >> 3));
+        gpair[0] = g.lo;
+        gpair[1] = g.hi;
       }
     } else {
 #pragma unroll
@@ -984,6 +1003,8 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     uint4 (&w)[U] = wset[SI];
     uint32_t (&w4)[U] = w4set[SI];
     uint32_t (&gw)[U] = gwset[SI];
+    const uint32_t w63 = w63set[SI];
+    const uint32_t (&gpair)[2] = gpset[SI];
     TSTAMP(0);
     const bool have_cur = cur < p.ntiles;
     const uint32_t t2 = th[TILE_LAG - 1];  // the piece copied out this iteration (tile k - LAG)
@@ -1030,12 +1051,30 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
       int start[U];
       bool act[U];
       uint32_t e[U][5];
+      // (lane-major) chain u's gap nibble at bits [4u, +4) of gnib: the dword pair starts at
+      // the dword of nibble n0 = gap_nib0 + seg0 - 1 (seg0 = 0: of nibble gap_nib0, chain 1's,
+      // and chain 0 starts at first_start); an inactive lane gets any nibble.  wla: the
+      // last chain's look-ahead word, the next lane's first payload word (wave_shl:1; lane 63
+      // keeps the word loaded for it)
+      uint32_t gnib = 0, wla = 0;
+      if constexpr (GH_TILE_LMAJ) {
+        const uint32_t n0 = p.gap_nib0 + (seg0 ? seg0 - 1u : 0u);
+        const unsigned long long g2 = ((unsigned long long)gpair[1] << 32) | gpair[0];
+        gnib = (uint32_t)(g2 >> (4u * (n0 & 7u)));
+        gnib = seg0 ? gnib : gnib << 4;
+        wla = (uint32_t)__builtin_amdgcn_update_dpp((int)w63, (int)w[0].x, 0x130, 0xf, 0xf, false);
+      }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint32_t seg = seg0 + (uint32_t)u * CSTR;
         act[u] = have_cur && seg < nseg;
-        start[u] = seg == 0 ? (int)p.first_start : (int)gap_nib(gw[u], p.gap_nib0 + seg - 1u);
-        make_ewin(w[u], (GH_TILE_LMAJ && u + 1 < U) ? w[u + 1 < U ? u + 1 : u].x : w4[u], start[u], S, e[u]);
+        if constexpr (GH_TILE_LMAJ) {
+          start[u] = seg == 0 ? (int)p.first_start : (int)((gnib >> (4 * u)) & 15u);
+          make_ewin(w[u], u + 1 < U ? w[u + 1 < U ? u + 1 : u].x : wla, start[u], S, e[u]);
+        } else {
+          start[u] = seg == 0 ? (int)p.first_start : (int)gap_nib(gw[u], p.gap_nib0 + seg - 1u);
+          make_ewin(w[u], w4[u], start[u], S, e[u]);
+        }
       }
       TSTAMP(1);
       if (GH_TILE_ABLATE & 1) {  // diagnostic build: no decode, 16 bytes per segment (wrong output)
