@@ -75,6 +75,8 @@ static uint32_t tile_u_for(uint32_t minlen) { return minlen >= 4 ? (uint32_t)TIL
 struct Kern {
   const void* fn;
   const char* name;
+  const void* fn_known = nullptr;  // tile kernel: its known-offsets instantiation (same name: a
+                                   // shape names U / G / OW / MINL, not the mode of one decode)
 };
 template <class... A>
 static std::string kern_name(const char* fmt, A... a) {
@@ -85,7 +87,8 @@ static std::string kern_name(const char* fmt, A... a) {
 template <int TB, int U, int G, int OW, int MINL>
 static Kern tile_kern() {
   static const std::string n = kern_name("tile<%d,%d,%d,%d,%d>", TB, U, G, OW, MINL);
-  return {(const void*)gh_tile_kernel<TB, U, G, OW, MINL>, n.c_str()};
+  return {(const void*)gh_tile_kernel<TB, U, G, OW, MINL, false>, n.c_str(),
+          (const void*)gh_tile_kernel<TB, U, G, OW, MINL, true>};
 }
 template <int TB, int GL, int NS, bool FB, int NP = 1>
 static Kern mtile_kern() {
@@ -226,6 +229,19 @@ struct TilePlan {
   DevBuf lut;     // the tables as they lie in LDS (one copy each)
   DevBuf gran;    // granules, within-round prefixes, round starts
   DevBuf stamps;  // GH_TILE_STAMPS builds only
+  // Known piece offsets (tile kernel only, gh_tile.hip): piece_off holds 16 ntiles + 1 u64,
+  // entry 16 t + w the output offset of wave w's piece of tile t, the last one the shard's
+  // total.  They are a function of the loaded shard alone, so they live as long as the load:
+  //   GH_OFFS_NONE      after a load (and after a decode that reported a status);
+  //   GH_OFFS_RECORDED  a chained decode, which writes the table, has been launched;
+  //   GH_OFFS_READY     the host has seen that decode finished with status 0 (at a wait it
+  //                     makes anyway: offsets_settle): later decodes run the known-offsets
+  //                     instantiation, which reads the table.
+  DevBuf piece_off;
+  int offs_state = GH_OFFS_NONE;
+  bool offs_on = false;   // the table exists and GH_TILE_OFFS=0 is not set
+  size_t lds_known = 0;   // dynamic LDS of the known-offsets instantiation
+  uint32_t lgr_known = 0; // its log2 LUT copies (lut_lgr unless GH_TILE_KLGR)
 };
 
 // Wave split (every other code): count, scan and write kernels.
@@ -354,7 +370,16 @@ static int tile_grid_and_granules(Plan& p, uint64_t resident) {
   p.grid = tile_grid_cap(p.grid);
   if (p.grid < 2) return GH_OK;
   p.tile.gran_words = 2ull * p.tile.ntiles + 2;
-  return p.tile.gran.alloc(8ull * p.tile.gran_words, true);
+  if (int rc = p.tile.gran.alloc(8ull * p.tile.gran_words, true)) return rc;
+  // the piece-offset table of a kernel with a known-offsets instantiation (the tile kernel;
+  // GH_TILE_OFFS=0 keeps every decode chained: tests, A/B timing).  The chained kernel
+  // writes it in either case.
+  if (p.kern.fn_known) {
+    if (int rc = p.tile.piece_off.alloc(8ull * (16ull * p.tile.ntiles + 1), true)) return rc;
+    const char* e = getenv("GH_TILE_OFFS");
+    p.tile.offs_on = !(e && e[0] == '0');
+  }
+  return GH_OK;
 }
 
 // ---- tile kernel setup -----------------------------------------------------------
@@ -371,10 +396,13 @@ static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
   t.ntiles = (uint32_t)ceil_div(c->shard.nseg, (uint64_t)tile_u * TILE_TB);
   // Staging is sized for the typical piece, not the worst case (128 / minlen bytes per
   // segment): TILE_SCAP = 20 bytes per segment for grouped codes (r = 0.1: 16.5), the
-  // stream's mean + 12 % for minlen-3 codes (r = 0.5: 21.5 -> 25), so that two
-  // workgroups fit a CU.  A wave's piece is the sum of 128-192 segments, so it stays near
-  // its mean; a larger one stores straight from registers (gh_tile_kernel).  The
-  // copy-out's TILE_NS * 64 chunks cover a region.  GH_TILE_SCAP overrides (tests).
+  // stream's mean + 12 % for minlen-3 codes (r = 0.5: 21.5 -> 25), so that the LUT's
+  // copies and TILE_LAG regions per wave fit a CU's LDS.  A wave's piece is the sum of
+  // 128-192 segments, so it stays near its mean; a larger one stores straight from
+  // registers (gh_tile_kernel).  The copy-out's TILE_NS * 64 chunks cover a region.  The
+  // known-offsets instantiation stages a piece up to 15 bytes further into the same region
+  // (at the phase of its output offset), so its longest staged piece is 16 bytes shorter,
+  // and it uses one region per wave.  GH_TILE_SCAP overrides (tests).
   double scapf = 1.12;
   if (const char* e = getenv("GH_TILE_SCAPF")) scapf = std::clamp(atof(e), 0.5, 4.0);
   uint64_t per_seg = std::min<uint64_t>(
@@ -401,15 +429,27 @@ static int tile_setup(gh_ctx* c, uint32_t K, double avg_seg_bytes) {
     }
     if (envr) break;
   }
-  // The kernel is compiled for two workgroups per CU (4 waves per SIMD).  The occupancy
-  // query can answer one more than the hardware admits at these SGPR counts (MI355X guide,
-  // "Occupancy API one block/CU high"); a grid that is not resident at once never finishes
-  // (its bounded polls then report GH_ST_TIMEOUT), so never plan more than two.
+  // The kernel is compiled for 4 waves per SIMD: one 1024-thread workgroup per CU (two
+  // of a GH_TILE_TB=512 build).  The occupancy query can answer one more than the hardware
+  // admits at these SGPR counts (MI355X guide, "Occupancy API one block/CU high"); a grid
+  // that is not resident at once never finishes (its bounded polls then report
+  // GH_ST_TIMEOUT), so never plan more than two.
   best = std::min(best, 2);
   if (best < 1) return GH_OK;
   t.lut_lgr = (uint32_t)best_lg;
   t.lut_bytes = (uint32_t)(4ull << (K + best_lg));
   p.lds = tile_lds_bytes(t.lut_bytes, t.stage_bytes);
+  // the known-offsets instantiation: same grid, LUT copies and regions (its freed LDS is
+  // left free), so whatever holds the chained grid resident holds this one
+  // (GH_TILE_KLGR=n, experiments: 2^n times the LUT copies in its freed LDS, where they
+  // fit; measured no faster on cfg4)
+  t.lgr_known = t.lut_lgr;
+  if (const char* e = getenv("GH_TILE_KLGR")) {
+    const uint32_t want = std::min<uint32_t>(t.lut_lgr + (uint32_t)std::clamp(atoi(e), 0, 5), 14 - K);
+    if (tile_lds_bytes_known(4ull << (K + want), t.stage_bytes) <= 160 * 1024) t.lgr_known = want;
+  }
+  t.lds_known = tile_lds_bytes_known(4ull << (K + t.lgr_known), t.stage_bytes);
+  if (int rc = allow_lds(p.kern.fn_known, 160 * 1024)) return rc;
   if (int rc = tile_grid_and_granules(p, (uint64_t)best * c->num_cu)) return rc;
   if (p.grid < 2) return GH_OK;
   if (const char* e = getenv("GH_TILE_IDLE"))  // experiment: block grid / 2 (the leader's CU partner) idles
@@ -712,6 +752,12 @@ extern "C" int gh_ctx_kernel_shape(gh_ctx* c, char* buf, size_t cap) {
   return copy_name(c->plan.shape, buf, cap);
 }
 
+extern "C" int gh_ctx_offsets_state(gh_ctx* c, int* state) {
+  if (!c || !state) return fail(GH_E_ARG, "null argument");
+  *state = (c->loaded && c->plan.mode == Mode::TILE) ? c->plan.tile.offs_state : GH_OFFS_NONE;
+  return GH_OK;
+}
+
 extern "C" int gh_kernel_shapes(char* buf, size_t cap) { return copy_name(all_kernel_shapes(), buf, cap); }
 
 extern "C" int gh_ctx_device(gh_ctx* c, int* device) {
@@ -1001,7 +1047,13 @@ extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
     GH_HIP(hipLaunchKernel((const void*)gh_ws_scan_kernel, dim3(1), dim3(WS_SCAN_TB), ac, 0, st));
     GH_HIP(hipLaunchKernel(p.kern.fn, dim3(p.grid), dim3(p.block), aw, p.lds, st));
   } else {
-    const TilePlan& tp = p.tile;
+    TilePlan& tp = p.tile;
+    // known piece offsets: the table of this load is READY -> the known-offsets
+    // instantiation; otherwise the chained kernel, which records the table
+    const bool known = p.mode == Mode::TILE && tp.offs_on && tp.offs_state == GH_OFFS_READY;
+    if (p.mode == Mode::TILE && tp.offs_on && tp.offs_state == GH_OFFS_NONE) tp.offs_state = GH_OFFS_RECORDED;
+    const void* fn = known ? p.kern.fn_known : p.kern.fn;
+    const size_t lds = known ? tp.lds_known : p.lds;
     unsigned long long* gran = tp.gran.get<unsigned long long>();
     TileParams t{};
     t.payload = sh.payload.get<uint32_t>();
@@ -1013,7 +1065,7 @@ extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
     t.status = c->misc_at(1);
     t.total = (unsigned long long*)c->misc_at(2);
     t.stats = (unsigned long long*)c->misc_at(4);
-    t.tickets = (unsigned int*)(gran + 2ull * tp.ntiles);  // the two spare granule words
+    t.piece_off = tp.piece_off.get<unsigned long long>();
     t.out_cap = sh.out_cap;
     t.nseg = sh.nseg;
     t.gap_nib0 = sh.gap_nib0;
@@ -1029,14 +1081,18 @@ extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
     t.stamps = tp.stamps.get<uint4>();
     t.tstamps = tp.stamps ? (unsigned long long*)(tp.stamps.get<uint8_t>() + 32ull * p.grid * 2 * 128) : nullptr;
     t.idle_block = tp.idle_block;
+    if (known) {
+      t.lgr = tp.lgr_known;
+      t.lut_bytes = (uint32_t)(4ull << (tp.kbits + tp.lgr_known));
+    }
     void* ta[1] = {&t};
     // timed: the start and stop timestamps are taken by the dispatch packet itself
     // (hipExtLaunchKernel), not by marker packets around it, so back-to-back decodes
     // have no extra packets between them
     if (timed)
-      GH_HIP(hipExtLaunchKernel(p.kern.fn, dim3(p.grid), dim3(p.block), ta, p.lds, st, ev.a, ev.b, 0));
+      GH_HIP(hipExtLaunchKernel(fn, dim3(p.grid), dim3(p.block), ta, lds, st, ev.a, ev.b, 0));
     else
-      GH_HIP(hipLaunchKernel(p.kern.fn, dim3(p.grid), dim3(p.block), ta, p.lds, st));
+      GH_HIP(hipLaunchKernel(fn, dim3(p.grid), dim3(p.block), ta, lds, st));
   }
   GH_HIP(hipGetLastError());
   // one event after the kernel(s): the timed decode's end event, or `done` (each marker
@@ -1060,10 +1116,27 @@ extern "C" int gh_ctx_decode(gh_ctx* c, void* hip_stream, int timed) {
 }
 
 // Waits for the context's last decode, whatever stream it was launched on.
+// Known piece offsets: every decode of the context has finished (wait_decode).  A table
+// that was being RECORDED is READY if the decodes left status 0, else dropped; the one
+// status read per load that this costs happens only in that state.
+static int offsets_settle(gh_ctx* c, const unsigned int* status_seen = nullptr) {
+  TilePlan& tp = c->plan.tile;
+  if (c->plan.mode != Mode::TILE || tp.offs_state == GH_OFFS_NONE) return GH_OK;
+  unsigned int status = 0;
+  if (status_seen) {
+    status = *status_seen;
+  } else {
+    if (tp.offs_state != GH_OFFS_RECORDED) return GH_OK;
+    GH_HIP(hipMemcpy(&status, c->misc_at(1), 4, hipMemcpyDeviceToHost));
+  }
+  tp.offs_state = status ? GH_OFFS_NONE : GH_OFFS_READY;
+  return GH_OK;
+}
+
 static int wait_decode(gh_ctx* c) {
   GH_HIP(hipStreamSynchronize(c->stream));
   if (c->done_rec) GH_HIP(hipEventSynchronize(c->done_ev));
-  return GH_OK;
+  return offsets_settle(c);
 }
 
 extern "C" int gh_ctx_report(gh_ctx* c, void* hip_stream, gh_report* rep) {
@@ -1094,6 +1167,9 @@ extern "C" int gh_ctx_report(gh_ctx* c, void* hip_stream, gh_report* rep) {
   }
   unsigned int misc[6] = {};
   GH_HIP(hipMemcpy(misc, c->misc.get(), sizeof(misc), hipMemcpyDeviceToHost));
+  // a decode that reports a status (GH_ST_OFFSETS: a piece disagreed with the table; any
+  // other) drops the piece offsets: the next decode is chained again
+  if (int rc = offsets_settle(c, &misc[1])) return rc;
   if (rep) {
     std::memset(rep, 0, sizeof(*rep));
     uint64_t tot;
@@ -2342,6 +2418,7 @@ extern "C" int gh_decode(const gh_stream* s, uint8_t* out, uint64_t out_len, con
     rep->kernel_ms = dec_ms;
   }
   if (status & GH_ST_TIMEOUT) return fail(GH_E_HIP, "look-back timed out");
+  if (status & GH_ST_OFFSETS) return fail(GH_E_HIP, "a piece disagreed with the recorded piece offsets");
   if (offset < s->n) return fail(GH_E_CORRUPT, "stream decoded to fewer than N symbols");
   if (status & GH_ST_BADCODE) return fail(GH_E_CORRUPT, "invalid code in stream");
   return GH_OK;

@@ -32,12 +32,28 @@
 // Issue priority by arrival rank: the waves that arrived last at their previous tile gate
 // the next aggregate, so they take priority 3, the first arrivals 0.
 //
+// Known piece offsets: the output offset of every wave's piece is a pure function of the
+// loaded shard.  The kernel above (the chained one) records each of them in the plan's
+// piece_off table where it copies the piece out.  Once the host has seen such a decode
+// finish with status 0, later decodes of the same load run the KNOWN instantiation of the
+// same template: no leader (all `grid` workgroups decode), no granules, prefixes, arrival
+// counters or polls.  A wave loads its piece's offset and the next one with the tile's
+// words, stages the piece at the 16-byte phase of its output offset, so that LDS chunk c is
+// output chunk c, and copies it out with one aligned LDS read per chunk.  Its own scanned
+// total must equal the difference of the two offsets (GH_ST_OFFSETS otherwise, and nothing
+// is written for that piece).  The one thing its waves still share is an LDS word, the
+// furthest iteration any of them has reached: a wave issues at the priority of its lag
+// behind it (without that the waves drift apart and the kernel is 9 % slower than the
+// chained one on cfg4, with it 7 % faster).
+//
 // The alternatives of the round-3/4 build knobs (copy-out interleaving, batched reads,
-// early loads, priority rotations, ...) measured slower and were removed.  The round-5/6
-// alternatives are still compiled in behind the knobs below, all at their measured-best
-// defaults (DYN, HOLD, PF2, W2, LATEP, CLDS, POLLDIV, LMAJ, ALRD: DESIGN.md, tile-kernel
-// section, records each measurement); the C-coded borrow count (CSUB) and the per-codeword
-// placement barrier (EPERM) are gone.
+// early loads, priority rotations, ...) and of the round-5/6 ones (tiles by ticket with a
+// frontier leader, a held tile, a second prefetched tile, a late prefix load, sparser
+// polls, paired staging stores, compiler-waited LUT reads, unaligned or DPP-shared
+// copy-out reads: DESIGN.md, tile-kernel section, records each measurement) measured
+// slower or no better and were removed, as were the C-coded borrow count and the
+// per-codeword placement barrier.  Build knobs left: TB, U, LAG, LMAJ (the chain-major
+// segment order, for comparison) and KLAG (the known-offsets copy-out's placement).
 // Diagnostic builds only: GH_TILE_STAMPS, GH_TILE_ABLATE.
 
 #ifndef GH_TILE_TB
@@ -66,35 +82,15 @@ constexpr int TILE_SLOTS = 16;  // per-tile wave totals / offsets / arrival coun
 #else
 #define TSTAMP(i) ((void)0)
 #endif
-#ifndef GH_TILE_CLDS
-#define GH_TILE_CLDS 0  // the decode's LUT reads as plain LDS loads (the compiler's own lgkmcnt waits)
-#endif
 #ifndef GH_TILE_LMAJ
 #define GH_TILE_LMAJ 1  // lane-major segments: lane l of a wave decodes its segments U*l .. U*l + U - 1
 #endif
-#ifndef GH_TILE_POLLDIV
-#define GH_TILE_POLLDIV 1  // a waiting wave re-polls the prefix granule every N-th spin (staggered by wave)
+#ifndef GH_TILE_KLAG
+#define GH_TILE_KLAG 0  // known offsets: a piece is copied out in the iteration that stages it (0) or
+                        // in the next one, before that one's staging (1); one buffer per wave either way
 #endif
-#ifndef GH_TILE_DYN
-#define GH_TILE_DYN 0  // tiles by ticket (one counter per launch parity) and a frontier leader
-#endif
-constexpr int TILE_TAHEAD = 5;  // (GH_TILE_DYN) a tile index is posted this many iterations ahead
-#ifndef GH_TILE_LATEP
-#define GH_TILE_LATEP 0  // a third prefix load right before the prefetch (see the loop)
-#endif
-#ifndef GH_TILE_HOLD
-#define GH_TILE_HOLD 0  // a decoded tile is held in registers one iteration and staged the next:
-                        // copy-out three iterations after the decode with two staging buffers
-#endif
-#ifndef GH_TILE_ALRD
-#define GH_TILE_ALRD 1  // copy-out: aligned LDS reads realigned in registers (see copy_out_piece)
-#endif
-#ifndef GH_TILE_W2
-#define GH_TILE_W2 0  // staging rounds in dword pairs (ds_write2_b32)
-#endif
-#ifndef GH_TILE_PF2
-#define GH_TILE_PF2 0  // the tile after next prefetched (two register sets, the loop body unrolled twice)
-#endif
+constexpr int TILE_KLAG = GH_TILE_KLAG;
+static_assert(TILE_KLAG == 0 || TILE_KLAG == 1, "GH_TILE_KLAG: 0 or 1");
 #ifndef GH_TILE_ABLATE
 #define GH_TILE_ABLATE 0  // diagnostic builds only (make variant), bits: 1 no decode, 2 no staging
                           // stores, 4 no prefix wait (a fake offset), 8 no copy-out, 16 even LUT
@@ -126,8 +122,10 @@ struct TileParams {
   unsigned int stage_bytes;      // one wave's staging region (16 + its piece + margin, a multiple of 16)
   unsigned int kbits_c;          // (gh_mtile.hip) the count table's width
   unsigned int fb_hi;            // (gh_mtile.hip, codes longer than the tables) the longest codeword
-  unsigned int* tickets;         // (GH_TILE_DYN) tile counters by launch parity, 8 bytes apart
-  uint4* stamps;                 // GH_TILE_STAMPS builds: [grid][2 waves][128 iterations][2] phase deltas
+  unsigned long long* piece_off;  // (tile kernel) [16 ntiles + 1] output offset of wave w's piece of tile t at
+                                  // 16 t + w, then the shard's total: written by the chained kernel,
+                                  // read by the known-offsets one
+  uint4* stamps;                // GH_TILE_STAMPS builds: [grid][2 waves][128 iterations][2] phase deltas
   unsigned long long* tstamps;   // GH_TILE_STAMPS builds: 100 MHz times: [ntiles] aggregate left, [ntiles]
                                  // prefix obtained by wave 0 (bit 63: polled), [rounds] round published
 };
@@ -138,6 +136,10 @@ struct TileParams {
 inline size_t tile_lds_bytes(size_t lut_bytes, size_t stage_bytes) {
   return lut_bytes + TILE_LAG * (TILE_TB / 64) * stage_bytes + TILE_SLOTS * (2 * (TILE_TB / 64) + 1) * 4 +
          TILE_SLOTS * 12 + 4 * (TILE_TB / 64) + 4 * TILE_SLOTS + 32;
+}
+// ... of its known-offsets instantiation: the LUT and one staging region per wave.
+inline size_t tile_lds_bytes_known(size_t lut_bytes, size_t stage_bytes) {
+  return lut_bytes + (TILE_TB / 64) * stage_bytes + 32;
 }
 
 // v_perm selectors of the symbol placement (a LUT entry carries its symbol in byte 1;
@@ -182,7 +184,6 @@ __device__ __forceinline__ uint32_t q_init(bool act, int start) {
 template <int N>
 __device__ __forceinline__ void lds_wait_n(uint32_t& v) {
   static_assert(N >= 0 && N <= 3, "lgkmcnt 0..3");
-  if constexpr (GH_TILE_CLDS) return;  // (the compiler's own waits for plain LDS loads)
   if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)::"memory");
   else if constexpr (N == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(v)::"memory");
   else if constexpr (N == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(v)::"memory");
@@ -234,12 +235,7 @@ __device__ __forceinline__ int decode_tile_rolling(uint32_t (&e)[U][5], const in
   // live and spilled; placed per group instead)
   constexpr bool PLACE = G >= 4;
   uint32_t q[U], ent[U], hold[U], pair[U];
-#if GH_TILE_CLDS
-  const __attribute__((address_space(3))) uint8_t* const lds0 = (const __attribute__((address_space(3))) uint8_t*)nullptr;
-  auto lut_rd = [&](uint32_t a) -> uint32_t { return *(const __attribute__((address_space(3))) uint32_t*)(lds0 + a); };
-#else
   auto lut_rd = [&](uint32_t a) -> uint32_t { return lds_u32_nowait(a); };
-#endif
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     q[u] = q_init(act[u], start[u]);
@@ -399,33 +395,11 @@ __device__ __forceinline__ void stage_wave(const uint32_t (&ow)[U][OW], const ui
     sh[u] = 4u - ap;  // v_alignbyte amount: dword m = bytes [4m - ap, +4) of the segment
   }
   auto dw = [&](int u, int m) { return __builtin_amdgcn_alignbyte(m < OW ? ow[u][m] : 0u, ow[u][m - 1], sh[u]); };
-  if constexpr (GH_TILE_W2) {
-    // dwords m and m - 1 of a segment in one ds_write2_b32 (rounds still descend; a
-    // segment holds >= 8 bytes, so no store of one instruction lands on another's dword)
 #pragma unroll
-    for (int m = OW; m >= 1; m -= 2) {
-      if (m - 1 >= 1) {
-        if (m <= mmax) {
+  for (int m = OW; m >= 1; --m) {
+    if (m > mmax) continue;  // wave-uniform: no segment of the wave reaches dword m
 #pragma unroll
-          for (int u = 0; u < U; ++u)
-            asm volatile("ds_write2_b32 %0, %1, %2 offset0:%3 offset1:%4" ::"v"(base[u]), "v"(dw(u, m)),
-                         "v"(dw(u, m - 1)), "i"(m), "i"(m - 1) : "memory");
-        } else if (m - 1 <= mmax) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) lds_st32_m(base[u], dw(u, m - 1), m - 1);
-        }
-      } else if (m <= mmax) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) lds_st32_m(base[u], dw(u, m), m);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int m = OW; m >= 1; --m) {
-      if (m > mmax) continue;  // wave-uniform: no segment of the wave reaches dword m
-#pragma unroll
-      for (int u = 0; u < U; ++u) lds_st32_m(base[u], dw(u, m), m);
-    }
+    for (int u = 0; u < U; ++u) lds_st32_m(base[u], dw(u, m), m);
   }
   // head dwords: read back (the previous segment's tail + garbage), merge, store; the
   // reads are unconditional, the stores are not (a segment at an aligned offset, and the
@@ -446,8 +420,10 @@ __device__ __forceinline__ void stage_wave(const uint32_t (&ow)[U][OW], const ui
 
 // Copy one wave's piece of a tile, staged at LDS byte stg + 16 + i = piece byte i, to
 // out[goff, goff + n) (n already clamped at out_cap).  Output chunk c (16 bytes, aligned
-// to the global address) is staging bytes [16c + 16 - lb, +16), lb = goff & 15: one
-// unaligned ds_read_b128 (gfx950 LDS runs in unaligned mode).  Every lane issues exactly
+// to the global address) is staging bytes [16c + 16 - lb, +16), lb = goff & 15: read as
+// its two aligned LDS chunks and shifted in registers (below).  PHASED (the known-offsets
+// kernel): the piece was staged at stg + 16 + lb instead, so output chunk c is the aligned
+// LDS chunk at stg + 16 + 16c: one ds_read_b128, no shift.  Every lane issues exactly
 // NS 16-byte buffer stores and one byte store (the partial head and tail chunks' bytes,
 // one per lane): a lane with no chunk (byte) stores at an offset past the buffer's range,
 // which the hardware drops, so no padding bytes reach memory and the store count is
@@ -461,7 +437,7 @@ constexpr uint32_t OOB_OFF = 0x80000000u;  // a buffer offset past every range: 
 // handing them to other values while the stores are in flight: the compiler waits for
 // an outstanding store before its data registers are overwritten (vmcnt), so a reuse
 // right after the copy-out stalled the next iteration on the stores.
-template <int NS, bool PIN = true>
+template <int NS, bool PIN = true, bool PHASED = false>
 __device__ __forceinline__ void copy_out_piece(uint8_t* out, uint32_t stg, unsigned long long goff, uint32_t n,
                                                int lane, tile_v4u (&v)[NS], uint32_t& b, uint32_t c0 = 0) {
   // (c0: the first chunk of this call; a piece copied in parts, 64 * NS chunks each, has
@@ -474,7 +450,7 @@ __device__ __forceinline__ void copy_out_piece(uint8_t* out, uint32_t stg, unsig
   const uint32_t lb = (uint32_t)(goff & 15);
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(out + (goff - lb), 0, 0x7FFFFFF0, 0x00020000);
   // (GH_TILE_ABLATE & 128, diagnostic: 16-byte aligned LDS reads, wrong bytes)
-  const uint32_t src = (stg + 16u - ((GH_TILE_ABLATE & 128) ? 0u : lb)) & ((GH_TILE_ABLATE & 256) ? ~3u : ~0u);    // staging address of output chunk 0 (diagnostic 256: dword-aligned)
+  const uint32_t src = PHASED ? stg + 16u : (stg + 16u - ((GH_TILE_ABLATE & 128) ? 0u : lb)) & ((GH_TILE_ABLATE & 256) ? ~3u : ~0u);    // staging address of output chunk 0 (diagnostic 256: dword-aligned)
   const uint32_t cf = lb ? 1u : 0u;       // interior chunks [cf, ce)
   const uint32_t ce = n ? (lb + n) >> 4 : 0u;
   uint32_t off[NS];
@@ -494,7 +470,7 @@ __device__ __forceinline__ void copy_out_piece(uint8_t* out, uint32_t stg, unsig
     if (t < nh) k = lb + t;
     else if (t < nh + nt) k = 16u * ce + (t - nh);
   }
-  if constexpr (GH_TILE_ALRD) {
+  if constexpr (!PHASED) {
     // Output chunk c is staging bytes [src + 16c, +16): the last 16 - lb bytes of the
     // aligned chunk at stg + 16c and the first lb of the next.  Both aligned chunks are read
     // (an unaligned ds_read_b128 costs the copy-out several times its aligned pair: cfg4
@@ -504,53 +480,6 @@ __device__ __forceinline__ void copy_out_piece(uint8_t* out, uint32_t stg, unsig
     // (registers), each group stored as soon as it is shifted; the store count is fixed.
     constexpr int CG = NS % 2 == 0 ? 2 : 1;
     const uint32_t sh = (16u - lb) & 15u, r = sh & 3u, m = lb ? sh >> 2 : 4u;
-    if constexpr (GH_TILE_ALRD == 2) {
-      // (variant) one aligned read per chunk: P_i = aligned chunk c_i of every lane (and
-      // P_NS for lane 0), Q_i = the next lane's P_i (lane 63: P_{i+1} of lane 0) by DPP
-      tile_v4u P[NS + 1];
-#pragma unroll
-      for (int i = 0; i <= NS; ++i) {
-        const uint32_t c = c0 + cf + (uint32_t)lane + 64u * (uint32_t)i;
-        const uint32_t a = stg + 16u * (c < ce + 1u ? c : cf);
-        asm volatile("ds_read_b128 %0, %1" : "=v"(P[i]) : "v"(a) : "memory");
-      }
-      if (PIN) asm volatile("ds_read_u8 %0, %1" : "+v"(b) : "v"(src + (k == OOB_OFF ? 0u : k)) : "memory");
-      else asm volatile("ds_read_u8 %0, %1" : "=v"(b) : "v"(src + (k == OOB_OFF ? 0u : k)) : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i <= NS; ++i) asm volatile("" : "+v"(P[i]));
-#pragma unroll
-      for (int i = 0; i < NS; ++i) {
-        tile_v4u Q;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          const int nx = __builtin_amdgcn_update_dpp(0, (int)P[i + 1][d], 0x134, 0xf, 0xf, false);  // wave_rol:1
-          Q[d] = (uint32_t)__builtin_amdgcn_update_dpp(nx, (int)P[i][d], 0x130, 0xf, 0xf, false);    // wave_shl:1
-        }
-        auto W = [&](int q) -> uint32_t { return q < 4 ? P[i][q] : Q[q - 4]; };
-        switch (m) {
-          case 0:
-            for (int d = 0; d < 4; ++d) v[i][d] = __builtin_amdgcn_alignbyte(W(d + 1), W(d), r);
-            break;
-          case 1:
-            for (int d = 0; d < 4; ++d) v[i][d] = __builtin_amdgcn_alignbyte(W(d + 2), W(d + 1), r);
-            break;
-          case 2:
-            for (int d = 0; d < 4; ++d) v[i][d] = __builtin_amdgcn_alignbyte(W(d + 3), W(d + 2), r);
-            break;
-          case 3:
-            for (int d = 0; d < 4; ++d) v[i][d] = __builtin_amdgcn_alignbyte(W(d + 4), W(d + 3), r);
-            break;
-          default:
-            v[i] = Q;
-            break;
-        }
-        __builtin_amdgcn_raw_buffer_store_b128(v[i], rs, (int)off[i], 0, 2);  // nt
-      }
-      if (PIN) asm volatile("" : "+v"(b));
-      __builtin_amdgcn_raw_buffer_store_b8((uint8_t)b, rs, (int)k, 0, 2);
-      return;
-    }
 #pragma unroll
     for (int g0 = 0; g0 < NS; g0 += CG) {
       tile_v4u pq[CG][2];
@@ -596,6 +525,7 @@ __device__ __forceinline__ void copy_out_piece(uint8_t* out, uint32_t stg, unsig
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)b, rs, (int)k, 0, 2);
     return;
   }
+  // PHASED: output chunk c is the aligned LDS chunk at src + 16c
 #pragma unroll
   for (int i = 0; i < NS; ++i) {
     const uint32_t c = c0 + cf + (uint32_t)lane + 64u * (uint32_t)i;
@@ -711,77 +641,6 @@ __device__ __forceinline__ void tile_round_leader(const TileParams& p, uint32_t 
   }
 }
 
-// (GH_TILE_DYN) The frontier leader: tiles are handed out by ticket, so a round of D
-// consecutive tiles may hold a tile whose workgroup waits on another tile of that round;
-// instead each tile's prefix is published as soon as every tile before it has published
-// its aggregate (a workgroup waits only on tiles older than every tile it holds, so no
-// wait cycle exists).  Per pass, thread i looks at tile F + i: the leading run of
-// aggregates already in is scanned and published, F moves past it.  Bounded like
-// poll_granule (4 s of the 100 MHz clock without progress).
-template <int TB>
-__device__ __forceinline__ void tile_frontier_leader(const TileParams& p, uint32_t* s_w, int tid, int lane, int wid) {
-  constexpr int NW = TB / 64;
-  uint32_t F = 0;
-  unsigned long long R = 0, t0 = 0;
-  uint32_t* const s_first = s_w;       // [2][NW] first tile not in, per wave (double-buffered by pass)
-  uint32_t* const s_sum = s_w + 2 * NW;  // [2][NW] wave sums
-  for (uint32_t pass = 0; F < p.ntiles; ++pass) {
-    const uint32_t t = F + (uint32_t)tid, pb = (pass & 1u) * NW;
-    bool in = false;
-    uint32_t v = 0;
-    if (t < p.ntiles) {
-      const unsigned long long g = __hip_atomic_load(&p.granules[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      in = granule_ok(p, g, 1);
-      v = (uint32_t)(g & GRAN_VMASK);
-    }
-    const unsigned long long out = __ballot(!in);
-    if (lane == 0) s_first[pb + wid] = out ? (uint32_t)__builtin_ctzll(out) : 64u;
-    __syncthreads();
-    uint32_t m = (uint32_t)TB;
-#pragma unroll
-    for (int q = NW - 1; q >= 0; --q) {
-      const uint32_t f = s_first[pb + q];
-      m = f < 64u ? 64u * (uint32_t)q + f : m;
-    }
-    const uint32_t vv = (uint32_t)tid < m ? v : 0u;
-    const uint32_t incl = wave_incl_scan(vv);
-    if (lane == 63) s_sum[pb + wid] = incl;
-    __syncthreads();
-    unsigned long long before = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < NW; ++q) {
-      const uint32_t x = s_sum[pb + q];
-      before += (q < wid) ? x : 0u;
-      total += x;
-    }
-    if ((uint32_t)tid < m) {
-      __hip_atomic_store(&p.prefix[t], granule(p.epoch, 2, R + before + incl - vv), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-#if GH_TILE_STAMPS
-      p.tstamps[2 * p.ntiles + t] = __builtin_amdgcn_s_memrealtime();  // tile t's prefix published
-#endif
-    }
-    R += total;
-    F += m;
-    if (m == 0u) {
-      if (tid == 0) atomicAdd(p.stats + 1, 1ull);
-      if ((pass & 63u) == 0u) {  // no progress: bounded (every thread reads the same clock)
-        if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & GH_ST_TIMEOUT) return;
-        const unsigned long long tw = wall_clock64();
-        if (t0 == 0) {
-          t0 = tw;
-        } else if (tw - t0 > 400000000ull) {
-          if (tid == 0) atomicOr(p.status, (unsigned)GH_ST_TIMEOUT);
-          return;
-        }
-      }
-      __builtin_amdgcn_s_sleep(2);
-    } else {
-      t0 = 0;
-    }
-  }
-}
-
 // TB threads, U segments per lane, GRP codewords per window shift, OW output words per
 // segment, codewords of at least MINL bits.  Compiled for 4 waves per SIMD (128 VGPRs):
 // one 1024-thread workgroup per CU, which its LUT copies and staging buffers (~157 KB of
@@ -794,53 +653,60 @@ __device__ __forceinline__ void tile_frontier_leader(const TileParams& p, uint32
 // after its global prefix has arrived, which the aggregate (so every wave's arrival)
 // precedes.  A wave can thus run at most about three tiles ahead of the slowest wave of
 // its workgroup (it needs tile k-3's prefix at iteration k-1), within the TILE_SLOTS
-// slots.
-template <int TB, int U, int GRP, int OW, int MINL>
+// slots.  Where a wave copies its piece out it also records the piece's output offset in
+// p.piece_off (the direct-store path too), one more store per wave and tile.
+//
+// KNOWN: the instantiation for a shard whose p.piece_off a chained decode has filled (the
+// file header).  No leader: D = grid, workgroup b takes tiles b, b + D, ...  Its waves
+// share nothing but the LUT: a wave's iteration is decode, wave scan, staging into its one
+// region at the phase of its output offset, and the copy-out (TILE_KLAG: in the same
+// iteration or in the next one); LDS holds the LUT and NW regions only.
+typedef unsigned int tile_v2u __attribute__((ext_vector_type(2)));
+template <int TB, int U, int GRP, int OW, int MINL, bool KNOWN = false>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void gh_tile_kernel(const TileParams p) {
   static_assert(4 * OW >= (128 + MINL - 1) / MINL, "OW words hold every codeword a segment can start");
   static_assert(U <= TILE_U, "shapes of at most TILE_U segments per lane");
   constexpr int NW = TB / 64;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const uint32_t stage_lds = p.lut_bytes;                                  // [2][NW] regions
+  const uint32_t stage_lds = p.lut_bytes;                                  // [LAG][NW] regions (KNOWN: [NW])
+  // (the chained kernel's hand-off words; KNOWN has none)
   uint32_t* s_tot = (uint32_t*)(smem + p.lut_bytes + TILE_LAG * NW * p.stage_bytes);  // [SLOTS][NW] wave totals
   uint32_t* s_off = s_tot + TILE_SLOTS * NW;                                // [SLOTS][NW] wave offsets
   uint32_t* s_cnt = s_off + TILE_SLOTS * NW;                                // [SLOTS] arrivals
   unsigned long long* s_pfx = (unsigned long long*)(s_cnt + TILE_SLOTS);   // [SLOTS] prefixes (wave 0)
   uint32_t* s_ptile = (uint32_t*)(s_pfx + TILE_SLOTS);                      // [SLOTS] their tiles
   uint32_t* s_lead = s_ptile + TILE_SLOTS;                                  // [NW] (leader)
-  uint32_t* s_ring = s_lead + NW;                                           // [SLOTS] (GH_TILE_DYN) tile of iteration k
   const uint32_t cnt_lds = (uint32_t)((uint8_t*)s_cnt - smem);
   const uint32_t ptile_lds = (uint32_t)((uint8_t*)s_ptile - smem);
-  const uint32_t ring_lds = (uint32_t)((uint8_t*)s_ring - smem);
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
 #if GH_TILE_STAMPS
   // per launch (ring of 1024 by epoch): shader-clock and 100 MHz times at the leader's start
   // and end, to read the clock the kernel ran at
   unsigned long long* const lring = p.tstamps + 3ull * p.ntiles + 64 + 4ull * (p.epoch & 1023u);
-  if (blockIdx.x == 0 && tid == 0) {
+  if (!KNOWN && blockIdx.x == 0 && tid == 0) {
     lring[0] = __builtin_amdgcn_s_memtime();
     lring[1] = __builtin_amdgcn_s_memrealtime();
   }
 #endif
-  // decoding workgroups: every block but 0 (the leader) and p.idle_block (if < grid)
-  const uint32_t D = gridDim.x - 1 - (p.idle_block < gridDim.x ? 1u : 0u);
-  if (blockIdx.x == 0) {
-    if constexpr (GH_TILE_DYN) {
-      if (tid == 0) p.tickets[2u * ((p.epoch + 1u) & 1u)] = 0u;  // the next launch's counter
-      tile_frontier_leader<TB>(p, (uint32_t*)smem, tid, lane, wid);
-    } else {
+  // decoding workgroups: every block but 0 (the leader) and p.idle_block (if < grid);
+  // KNOWN: every block
+  uint32_t D = gridDim.x, b = blockIdx.x;
+  if constexpr (!KNOWN) {
+    D = gridDim.x - 1 - (p.idle_block < gridDim.x ? 1u : 0u);
+    b = blockIdx.x - 1 - (blockIdx.x > p.idle_block ? 1u : 0u);
+    if (blockIdx.x == 0) {
       tile_round_leader<TB>(p, D, s_lead, tid, lane, wid);
-    }
 #if GH_TILE_STAMPS
-    if (tid == 0) {
-      lring[2] = __builtin_amdgcn_s_memtime();
-      lring[3] = __builtin_amdgcn_s_memrealtime();
-    }
+      if (tid == 0) {
+        lring[2] = __builtin_amdgcn_s_memtime();
+        lring[3] = __builtin_amdgcn_s_memrealtime();
+      }
 #endif
-    return;
+      return;
+    }
+    if (blockIdx.x == p.idle_block) return;  // the leader's CU partner (GH_TILE_IDLE): no decoding
   }
-  if (blockIdx.x == p.idle_block) return;  // the leader's CU partner (GH_TILE_IDLE): no decoding
 #if GH_TILE_STAMPS
   // per workgroup: shader-clock and 100 MHz times at its start and end (its clock)
   unsigned long long* const wring = p.tstamps + 3ull * p.ntiles + 64 + 4ull * 1024 + 4ull * blockIdx.x;
@@ -854,15 +720,19 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const uint32_t nd = p.lut_bytes >> 2;
     uint32_t* sl = (uint32_t*)smem;
     for (uint32_t i = tid; i < nd; i += TB) sl[i] = p.lut[i >> p.lgr];
-    if (tid < TILE_SLOTS) {
+    if (!KNOWN && tid < TILE_SLOTS) {
       s_cnt[tid] = 0;
       s_ptile[tid] = 0xFFFFFFFFu;
     }
-    if (GH_TILE_DYN && tid <= TILE_TAHEAD) {  // iterations 0 .. TAHEAD: static tiles
-      const uint32_t b0 = blockIdx.x - 1 - (blockIdx.x > p.idle_block ? 1u : 0u);
-      const uint32_t tt = b0 + (uint32_t)tid * D;
-      s_ring[tid] = tt < p.ntiles ? tt : 0xFFFFFFFFu;
-    }
+    if (KNOWN && tid == 0) *(uint32_t*)(smem + p.lut_bytes + NW * p.stage_bytes) = 0u;  // the front (below)
+  }
+  // (KNOWN) the front: the iteration the furthest wave of the workgroup has reached.  The
+  // waves share no hand-off any more, and left alone they drift apart (wave 0 ran its
+  // iteration in 7.4 K cycles, wave 4 in 9.0 K: the kernel then ends with a few waves per CU
+  // still working); a wave issues at the priority of its lag behind the front, as the chained
+  // kernel's waves do by their arrival rank.
+  const uint32_t front_lds = p.lut_bytes + (uint32_t)NW * p.stage_bytes;
+  {
   }
   const uint32_t S = 30u - p.kbits - p.lgr;
   // (GH_TILE_ABLATE & 16, diagnostic: even LUT entries only, so a read's lanes never
@@ -871,39 +741,24 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   const uint32_t laneoff = ((uint32_t)lane & ((1u << p.lgr) - 1u)) << 2;
   check_lds_base(smem, p.status);
 
-  const uint32_t G = D, b = blockIdx.x - 1 - (blockIdx.x > p.idle_block ? 1u : 0u);  // decoders, this one
+  const uint32_t G = D;                                    // decoders (b: this one)
   const uint32_t nseg = (uint32_t)p.nseg;                 // < 2^31 (checked by the host)
   constexpr uint32_t NONE = 0xFFFFFFFFu;
   __syncthreads();  // the LUT and the counters (the last barrier of a decoding workgroup)
-  // (GH_TILE_DYN: the static bound below does not hold; every iteration then either
-  // decodes a tile or drains a staged one, so 2 * ntiles iterations bound a sound run)
-  const uint32_t last_tile_k = GH_TILE_DYN ? p.ntiles + 2u * TILE_SLOTS
-                               : b < p.ntiles ? (p.ntiles - 1 - b) / G : NONE;
+  const uint32_t last_tile_k = b < p.ntiles ? (p.ntiles - 1 - b) / G : NONE;
   uint32_t cur = b, nxt = b + G;
-  // (GH_TILE_DYN) wave 0 lane 0 holds the ticket taken one iteration earlier; tickets
-  // count tiles from (TAHEAD + 1) * D on
-  const uint32_t dyn_base = (uint32_t)(TILE_TAHEAD + 1) * D;
-  uint32_t tk = 0;
-  bool tk_live = GH_TILE_DYN && dyn_base < p.ntiles;
-  unsigned int* const tctr = GH_TILE_DYN ? p.tickets + 2u * (p.epoch & 1u) : nullptr;
   // the lane's segments in a tile: wave-contiguous, 64 per chain (chain u lane l: segment
   // 64u + l of the wave's 64U); lane-major (GH_TILE_LMAJ): lane l's U consecutive segments
   // Ul .. Ul + U - 1, so the staging stores of one instruction land ~U segments apart
   constexpr uint32_t CSTR = GH_TILE_LMAJ ? 1u : 64u;  // segment stride between chains
   const uint32_t lseg = (uint32_t)(wid * 64 * U) + (uint32_t)lane * (GH_TILE_LMAJ ? (uint32_t)U : 1u);
-  constexpr int NSET = GH_TILE_PF2 ? 2 : 1;  // register sets of prefetched words
-  static_assert(!(GH_TILE_PF2 && (GH_TILE_DYN || GH_TILE_HOLD)), "PF2: static schedule, no hold");
-  uint4 wset[NSET][U];
-  uint32_t w4set[NSET][U], gwset[NSET][U];  // (chain-major) look-ahead and gap dword per chain
-  uint32_t w63set[NSET], gpset[NSET][2];    // (lane-major) lane 63's look-ahead word; the lane's gap dword pair
-  auto load = [&](auto SS, uint32_t t) {
-    constexpr int SI = decltype(SS)::value;
-    uint4 (&w)[U] = wset[SI];
-    uint32_t (&w4)[U] = w4set[SI];
-    uint32_t (&gw)[U] = gwset[SI];
-    uint32_t& w63 = w63set[SI];
-    uint32_t (&gpair)[2] = gpset[SI];
-    const uint32_t seg0 = min(t, p.ntiles - 1) * (uint32_t)(U * TB) + lseg;
+  uint4 w[U];
+  uint32_t w4[U], gw[U];   // (chain-major) look-ahead and gap dword per chain
+  uint32_t w63, gpair[2];  // (lane-major) lane 63's look-ahead word; the lane's gap dword pair
+  unsigned long long po[2] = {0, 0};  // (KNOWN) the wave's piece's output offset and the next piece's
+  auto load = [&](uint32_t t) {
+    const uint32_t tc = min(t, p.ntiles - 1);
+    const uint32_t seg0 = tc * (uint32_t)(U * TB) + lseg;
     if constexpr (GH_TILE_LMAJ) {
       // one lane's U consecutive segments: their 16 U bytes (chain u's look-ahead word is
       // chain u + 1's first word, chain U - 1's the next lane's first word: taken from that
@@ -924,9 +779,9 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
       // the U gap nibbles gap_nib0 + sb - 1 .. + U - 1 (the first one unused when sb = 0) lie in
       // one gap dword or in two neighbours: both, as one 8-byte load at the first one's dword
       // (at most dword gwords of the gwords + 4 allocated).  That makes U + 2 loads per lane
-      // and tile (U + 1 + U before), followed by the copy-out's TILE_NS + 1 stores: the loop
-      // top waits vmcnt(TILE_NS + 1) once for all of them, where it used to count the U gap
-      // dwords down one by one.
+      // and tile (U + 1 + U before), followed by the copy-out's stores: the loop top waits
+      // with one counted vmcnt for all of them, where it used to count the U gap dwords down
+      // one by one.
       {
         struct __attribute__((packed, aligned(4))) gap2 { uint32_t lo, hi; };
         const gap2 g = *(const gap2*)(p.gaps + ((p.gap_nib0 + (sb ? sb - 1u : 0u)) >> 3));
@@ -942,103 +797,101 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         gw[u] = p.gaps[(p.gap_nib0 + (sc ? sc - 1u : 0u)) >> 3];
       }
     }
-  };
-  // (GH_TILE_DYN) the ticket operation after every prefetch: wave 0 lane 0 takes the next
-  // ticket (its tile posted one iteration later), every other wave, and wave 0 once the
-  // tiles are out, issues a dropped store instead, so each wave has the same VMEM
-  // operations after its loads on every path (a counted vmcnt that never waits for the
-  // ticket, whose counter is contended: it is read a whole iteration later)
-  const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, 0x7FFFFFF0, 0x00020000);
-  auto ticket_op = [&]() {
-    if constexpr (GH_TILE_DYN) {
-      if (wid == 0 && tk_live) {
-        if (lane == 0) tk = atomicAdd(tctr, 1u);
-      } else {
-        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, rs_out, (int)(OOB_OFF + 64u), 0, 2);
-      }
+    if constexpr (KNOWN) {
+      // entries 16 t + wid and the one after it (the next wave's, the next tile's first or
+      // the shard's total), with the tile's words: every lane loads the same 16 bytes (one
+      // request), on every path (a clamped tile in the drain: entry <= 16 ntiles)
+      struct __attribute__((packed, aligned(8))) off2 { unsigned long long at, next; };
+      const off2 o2 = *(const off2*)(p.piece_off + (16ull * tc + (uint32_t)wid));
+      po[0] = o2.at;
+      po[1] = o2.next;
     }
   };
+  const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, 0x7FFFFFF0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_po = __builtin_amdgcn_make_buffer_rsrc(p.piece_off, 0, 0x7FFFFFF0, 0x00020000);
   auto junk_stores = [&]() {  // as many stores after these loads as every iteration issues
-     // after its prefetch (the copy-out's TILE_NS + 1, dropped here: out of range): the
-     // loop's entry then matches its back edge, and the compiler waits for the loads with
-     // a counted vmcnt
+     // after its prefetch (the copy-out's TILE_NS + 1 and, chained, the recorded offset;
+     // dropped here: out of range): the loop's entry then matches its back edge, and the
+     // compiler waits for the loads with a counted vmcnt
     const __amdgpu_buffer_rsrc_t rs = rs_out;
 #pragma unroll
     for (int i = 0; i < TILE_NS; ++i)
       __builtin_amdgcn_raw_buffer_store_b128(tile_v4u{0, 0, 0, 0}, rs, (int)(OOB_OFF + 16u * (uint32_t)i), 0, 2);  // (distinct: not merged)
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, rs, (int)OOB_OFF, 0, 2);
+    if constexpr (!KNOWN) __builtin_amdgcn_raw_buffer_store_b64(tile_v2u{0, 0}, rs_po, (int)OOB_OFF, 0, 0);
   };
-  load(std::integral_constant<int, 0>{}, cur);
-  ticket_op();
+  load(cur);
   junk_stores();
-  if constexpr (GH_TILE_PF2) {
-    // (the iteration's two prefix loads, then the next tile's words: the back edge's order)
-    (void)__hip_atomic_load(&p.prefix[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    (void)__hip_atomic_load(&p.prefix[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    load(std::integral_constant<int, NSET - 1>{}, nxt);
-    junk_stores();
-  }
   if (cur >= p.ntiles) cur = NONE;
   uint32_t th[TILE_LAG];          // this wave's pieces of iterations k-1 .. k-LAG (NONE: not staged)
 #pragma unroll
   for (int i = 0; i < TILE_LAG; ++i) th[i] = NONE;
-  // (GH_TILE_HOLD) the previous iteration's tile, held in registers until it is staged
-  uint32_t owp[U][OW], cntp[U], bposp[U], wtp = 0, prevt = NONE;
-  int gdp = 1;
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    cntp[u] = 0;
-    bposp[u] = 0;
-#pragma unroll
-    for (int k2 = 0; k2 < OW; ++k2) asm volatile("" : "=v"(owp[u][k2]));
-  }
   uint32_t rank = 0;              // the wave's arrival rank at its last tile, in quarters
   const uint32_t region0 = stage_lds + (uint32_t)wid * p.stage_bytes;  // buffer 0; buffer 1 at + NW * stage_bytes
-  const uint32_t piece_cap = p.stage_bytes - (uint32_t)(STAGE_PAD + 4 * OW + 4);
+  // the longest piece a region holds; KNOWN stages up to 15 bytes further in
+  const uint32_t piece_cap = p.stage_bytes - (uint32_t)(STAGE_PAD + 4 * OW + 4) - (KNOWN ? 16u : 0u);
+  // (KNOWN, TILE_KLAG = 1) the piece staged by the previous iteration: offset, clamped length
+  unsigned long long pgoff = 0;
+  uint32_t pn = 0;
+  bool phave = false;
 #if GH_TILE_STAMPS
   unsigned long long ts[9];
 #endif
-  auto body = [&](auto SS, uint32_t k) -> bool {
-    constexpr int SI = decltype(SS)::value;  // the register set holding this tile's words
-    uint4 (&w)[U] = wset[SI];
-    uint32_t (&w4)[U] = w4set[SI];
-    uint32_t (&gw)[U] = gwset[SI];
-    const uint32_t w63 = w63set[SI];
-    const uint32_t (&gpair)[2] = gpset[SI];
+  auto body = [&](uint32_t k) -> bool {
     TSTAMP(0);
     const bool have_cur = cur < p.ntiles;
-    const uint32_t t2 = th[TILE_LAG - 1];  // the piece copied out this iteration (tile k - LAG)
+    const uint32_t t2 = th[TILE_LAG - 1];  // (chained) the piece copied out this iteration (tile k - LAG)
     const bool have2 = t2 < p.ntiles;
-    bool pending = have_cur || (GH_TILE_HOLD && prevt < p.ntiles);
+    bool pending = have_cur;
+    if constexpr (KNOWN) {
+      pending |= TILE_KLAG && phave;
+    } else {
 #pragma unroll
-    for (int i = 0; i < TILE_LAG; ++i) pending |= th[i] < p.ntiles;
+      for (int i = 0; i < TILE_LAG; ++i) pending |= th[i] < p.ntiles;
+    }
     if (!pending) return false;
-    if (last_tile_k != NONE && k > last_tile_k + TILE_LAG + 2) {  // cannot happen; never hang the GPU
+    if (!KNOWN && last_tile_k != NONE && k > last_tile_k + TILE_LAG + 2) {  // cannot happen; never hang the GPU
       if (lane == 0) atomicOr(p.status, (unsigned)GH_ST_TIMEOUT);
       return false;
     }
-    const uint32_t slot = k % TILE_SLOTS, slot2 = (k + TILE_SLOTS - TILE_LAG - GH_TILE_HOLD) % TILE_SLOTS;
-    const uint32_t slotp = (k + TILE_SLOTS - 1) % TILE_SLOTS;  // (GH_TILE_HOLD) the held tile's
+    const uint32_t slot = k % TILE_SLOTS, slot2 = (k + TILE_SLOTS - TILE_LAG) % TILE_SLOTS;
     const uint32_t buf = k % TILE_LAG;
-    // issue priority by the wave's arrival rank at its last tile (0: first of the
-    // workgroup's waves): the waves that arrive last gate the tile's aggregate, so they
-    // issue first (the round-3/4 rule, priority 0 after a polled prefix, was slower)
-    if (rank >= 3) __builtin_amdgcn_s_setprio(3);
-    else if (rank == 2) __builtin_amdgcn_s_setprio(2);
-    else if (rank == 1) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-    // prefix of tile k-LAG: loaded at the top and again mid-decode; the first that
-    // shows it published is used (a load at the top alone often saw it a little before it
-    // was published, and the re-poll then paid a full memory round trip)
-    // (every lane loads the same word, one request; no branch around the load: the
-    // compiler's wait counting over such a branch fell back to vmcnt(0), which then also
-    // waited for the next tile's loads issued behind it)
-    unsigned long long* const pf2 = &p.prefix[have2 ? t2 : 0u];
-    unsigned long long gp0 = 0, gp = 0, gpl = 0;
-    if (!(GH_TILE_ABLATE & 4)) gp0 = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long* pf2 = nullptr;
+    unsigned long long gp0 = 0, gp = 0;
+    if constexpr (!KNOWN) {
+      // issue priority by the wave's arrival rank at its last tile (0: first of the
+      // workgroup's waves): the waves that arrive last gate the tile's aggregate, so they
+      // issue first (the round-3/4 rule, priority 0 after a polled prefix, was slower)
+      if (rank >= 3) __builtin_amdgcn_s_setprio(3);
+      else if (rank == 2) __builtin_amdgcn_s_setprio(2);
+      else if (rank == 1) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
+      // prefix of tile k-LAG: loaded at the top and again mid-decode; the first that
+      // shows it published is used (a load at the top alone often saw it a little before it
+      // was published, and the re-poll then paid a full memory round trip)
+      // (every lane loads the same word, one request; no branch around the load: the
+      // compiler's wait counting over such a branch fell back to vmcnt(0), which then also
+      // waited for the next tile's loads issued behind it)
+      pf2 = &p.prefix[have2 ? t2 : 0u];
+      if (!(GH_TILE_ABLATE & 4)) gp0 = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     auto mid = [&]() {
-      if (!(GH_TILE_ABLATE & 4)) gp = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if constexpr (!KNOWN)
+        if (!(GH_TILE_ABLATE & 4)) gp = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
+    // (KNOWN) this tile's piece offsets, loaded with its words: wave-uniform, to SGPRs
+    const unsigned long long g_at = KNOWN ? rfl_u64(po[0]) : 0ull, g_next = KNOWN ? rfl_u64(po[1]) : 0ull;
+    if constexpr (KNOWN) {
+      // issue priority by the wave's lag behind the workgroup's front (one LDS max and one
+      // read per iteration; LDS operations of a wave complete in order, so the read sees the
+      // wave's own max)
+      asm volatile("ds_max_u32 %0, %1" ::"v"(front_lds), "v"(k) : "memory");
+      const uint32_t lag = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_ld_u32(front_lds)) - k;
+      if (lag >= 3) __builtin_amdgcn_s_setprio(3);
+      else if (lag == 2) __builtin_amdgcn_s_setprio(2);
+      else if (lag == 1) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
+    }
     // ---- decode this tile (its words were loaded during the previous iteration) --------
     // Decoded unconditionally: in the last iterations (no tile) every chain is inactive
     // and the loop stops after group TILE_MIDG, on have_cur (the loads were issued,
@@ -1096,28 +949,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // copy-out instead they had ~3 K cycles, and the next decode waited ~1.3 K cycles for
     // them.  They follow the prefix loads, whose waits therefore do not include them
     // (vmcnt is one in-order queue).
-    if constexpr (GH_TILE_DYN) {
-      // wave 0 posts the tile of iteration k + 1 + TAHEAD (the ticket it took last
-      // iteration) and takes the next ticket; every wave reads the tile of iteration k + 1,
-      // posted at least TAHEAD iterations ago by wave 0, which is never more than three
-      // iterations behind another wave of its workgroup
-      if (wid == 0) {
-        uint32_t tpost = NONE;
-        if (lane == 0 && tk_live) tpost = dyn_base + tk < p.ntiles ? dyn_base + tk : NONE;
-        tpost = (uint32_t)__builtin_amdgcn_readfirstlane((int)tpost);
-        tk_live = tk_live && tpost != NONE;
-        if (lane == 0) lds_st_u32(ring_lds + 4u * ((k + 1u + TILE_TAHEAD) % TILE_SLOTS), tpost);
-      }
-      nxt = lds_ld_u32(ring_lds + 4u * ((k + 1u) % TILE_SLOTS));
-      nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)nxt);
-    }
-    // (GH_TILE_LATEP) a third look at the prefix, after the decode and just BEFORE the
-    // prefetch: vmcnt is one in-order queue, so a poll issued behind the prefetch cannot
-    // be read before the prefetch has landed (~2-3 us under load); this one can
-    if (GH_TILE_LATEP && !(GH_TILE_ABLATE & 4)) gpl = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // (GH_TILE_PF2: the words of the tile after next, into this iteration's register set)
-    load(SS, GH_TILE_PF2 ? nxt + G : nxt);
-    ticket_op();
+    load(nxt);
     TSTAMP(2);
     // ---- wave scans: the segments' offsets in the wave's piece, the piece's length -------
     uint32_t bpos[U], wave_tot = 0;
@@ -1143,6 +975,65 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         wave_tot += ct;
       }
     }
+    if constexpr (KNOWN) {
+      TSTAMP(3);
+      TSTAMP(4);
+      // ---- the guard: the piece's scanned length against the table ------------------------
+      // (the whole defence against a stale or foreign table: a piece that disagrees writes
+      // nothing and fails the decode)
+      const bool ok = have_cur && g_next - g_at == (unsigned long long)wave_tot;
+      const bool staged = ok && wave_tot <= piece_cap;
+      const uint32_t lb = (uint32_t)g_at & 15u;
+      const uint32_t ncp = (!staged || g_at >= p.out_cap) ? 0u : (uint32_t)min<unsigned long long>(wave_tot, p.out_cap - g_at);
+      tile_v4u cv[TILE_NS];
+      uint32_t cb;
+      // (TILE_KLAG = 1) the previous iteration's piece out of the region, before this
+      // one's goes in (the copy-out waits for its LDS reads before it stores)
+      if constexpr (TILE_KLAG == 1)
+        if (!(GH_TILE_ABLATE & 8)) copy_out_piece<TILE_NS, false, true>(p.out, region0, pgoff, pn, lane, cv, cb);
+#if GH_TILE_STAMPS
+      const unsigned long long ta = __builtin_amdgcn_s_memtime();
+#endif
+      // ---- stage this tile's piece at the phase of its output offset ------------------------
+      // a piece larger than the region stores its bytes straight from registers, at once;
+      // one that fails the guard sets GH_ST_OFFSETS
+      if (have_cur && !staged) {
+        if (ok) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) store_direct(p.out, p.out_cap, g_at + bpos[u], ow[u], cnt[u]);
+        } else if (lane == 0) {
+          atomicOr(p.status, (unsigned)GH_ST_OFFSETS);
+        }
+        // (rare path) drain its data-dependent stores here, so that the compiler's wait
+        // for the next tile's loads stays a counted vmcnt on the common path
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+      } else if (have_cur && !(GH_TILE_ABLATE & 2)) {
+        const uint32_t sbase = region0 + STAGE_PAD + lb;
+        uint32_t o[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) o[u] = sbase + bpos[u];
+        stage_wave<U, OW>(ow, cnt, o, min(OW, (GRP * gdone + 3) >> 2));
+      }
+      if (wid == NW - 1 && cur == p.ntiles - 1 && ok && lane == 0) *p.total = g_next;
+#if GH_TILE_STAMPS
+      const unsigned long long tb = __builtin_amdgcn_s_memtime();
+#endif
+      if constexpr (TILE_KLAG == 0) {
+        // the staging stores have landed before the copy-out reads them back
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (!(GH_TILE_ABLATE & 8)) copy_out_piece<TILE_NS, false, true>(p.out, region0, g_at, ncp, lane, cv, cb);
+      } else {
+        pgoff = g_at;
+        pn = ncp;
+        phave = staged;
+      }
+#if GH_TILE_STAMPS
+      // (the chained kernel's columns: copy-out, then stage)
+      const unsigned long long tc = __builtin_amdgcn_s_memtime();
+      ts[5] = ts[4] + (ta - ts[4]) + (tc - tb);
+      ts[6] = ts[5] + (tb - ta);
+#endif
+    } else {
     // ---- arrival at tile k: the last wave to arrive publishes its aggregate ------------
     uint32_t tile_total = 0;
     if (have_cur) {
@@ -1177,6 +1068,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // ---- the prefix of tile k-LAG -> this wave's piece's output offset -------------------
     unsigned long long goff = 0;
     uint32_t n2 = 0;
+    bool rec = false;  // goff is the piece's true offset: recorded for the known-offsets decodes
     if (have2 && (GH_TILE_ABLATE & 4)) {
       goff = ((unsigned long long)t2 * (U * TB * 16) + (uint32_t)wid * (U * 64 * 16)) % (p.out_cap - (U * TB * 32));
       n2 = s_tot[slot2 * NW + wid];
@@ -1188,48 +1080,45 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
       bool polled = false, got = true;  // (polled: GH_TILE_STAMPS builds)
       (void)polled;
       if (!granule_ok(p, g, 2)) g = rfl_u64(gp);
-      if (GH_TILE_LATEP && !granule_ok(p, g, 2)) g = rfl_u64(gpl);
-      {
-        if (!granule_ok(p, g, 2)) {
-          polled = true;
-          if (wid == 0 && lane == 0) atomicAdd(p.stats, 1ull);
-          unsigned long long t0w = 0;
-          // (two or three polls in flight measured slower: 0.440 vs 0.433 ms, round 5)
-          unsigned long long pv = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          for (uint32_t spins = 1;; ++spins) {
-            bool found = false;
-            if (lds_ld_u32(ptile_lds + 4u * slot2) == t2) {
-              asm volatile("" ::: "memory");
-              g = s_pfx[slot2];
+      if (!granule_ok(p, g, 2)) {
+        polled = true;
+        if (wid == 0 && lane == 0) atomicAdd(p.stats, 1ull);
+        unsigned long long t0w = 0;
+        // (two or three polls in flight measured slower: 0.440 vs 0.433 ms, round 5)
+        unsigned long long pv = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (uint32_t spins = 1;; ++spins) {
+          bool found = false;
+          if (lds_ld_u32(ptile_lds + 4u * slot2) == t2) {
+            asm volatile("" ::: "memory");
+            g = s_pfx[slot2];
+            found = true;
+          } else {
+            g = rfl_u64(pv);
+            if (granule_ok(p, g, 2)) {
+              if (lane == 0) {  // post: the value, then its tile (LDS order)
+                s_pfx[slot2] = g;
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_st_u32(ptile_lds + 4u * slot2, t2);
+              }
               found = true;
             } else {
-              g = rfl_u64(pv);
-              if (granule_ok(p, g, 2)) {
-                if (lane == 0) {  // post: the value, then its tile (LDS order)
-                  s_pfx[slot2] = g;
-                  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                  lds_st_u32(ptile_lds + 4u * slot2, t2);
-                }
-                found = true;
-              } else if (GH_TILE_POLLDIV <= 1 || ((spins + (uint32_t)wid) % GH_TILE_POLLDIV) == 0u) {
-                pv = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              }
+              pv = __hip_atomic_load(pf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            if (found) break;
-            if ((spins & 63u) == 0u) {  // bounded like poll_granule: 4 s of the 100 MHz clock
-              if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & GH_ST_TIMEOUT) break;
-              const unsigned long long t = wall_clock64();
-              if (t0w == 0) {
-                t0w = t;
-              } else if (t - t0w > 400000000ull) {
-                if (lane == 0) atomicOr(p.status, (unsigned)GH_ST_TIMEOUT);
-                break;
-              }
-            }
-            __builtin_amdgcn_s_sleep(1);
           }
-          got = granule_ok(p, g, 2);  // false only after a timeout (then nothing is written)
+          if (found) break;
+          if ((spins & 63u) == 0u) {  // bounded like poll_granule: 4 s of the 100 MHz clock
+            if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & GH_ST_TIMEOUT) break;
+            const unsigned long long t = wall_clock64();
+            if (t0w == 0) {
+              t0w = t;
+            } else if (t - t0w > 400000000ull) {
+              if (lane == 0) atomicOr(p.status, (unsigned)GH_ST_TIMEOUT);
+              break;
+            }
+          }
+          __builtin_amdgcn_s_sleep(1);
         }
+        got = granule_ok(p, g, 2);  // false only after a timeout (then nothing is written)
       }
       // the tile's offsets were in LDS before its aggregate left, and the aggregate before
       // its prefix: read them only now (no compiler hoisting above the check)
@@ -1237,13 +1126,24 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
       goff = (g & GRAN_VMASK) + s_off[slot2 * NW + wid];
       if (GH_TILE_ABLATE & 32) goff &= ~15ull;  // (diagnostic: 16-byte aligned pieces, wrong output)
       n2 = s_tot[slot2 * NW + wid];
-      if (wid == NW - 1 && t2 == p.ntiles - 1 && got && lane == 0) *p.total = goff + n2;
+      rec = got;
+      if (wid == NW - 1 && t2 == p.ntiles - 1 && got && lane == 0) {
+        *p.total = goff + n2;
+        p.piece_off[16ull * p.ntiles] = goff + n2;  // the table's last entry
+      }
 #if GH_TILE_STAMPS
       if (wid == 0 && lane == 0) p.tstamps[p.ntiles + t2] = __builtin_amdgcn_s_memrealtime() | ((unsigned long long)polled << 63);
 #endif
       n2 = (!got || goff >= p.out_cap) ? 0u : (uint32_t)min<unsigned long long>(n2, p.out_cap - goff);
     }
     TSTAMP(4);
+    // ---- record the piece's offset (before the out_cap clamp) ------------------------------
+    // Unconditional, like the copy-out's stores: lane 0 stores entry 16 t2 + wid, every other
+    // lane, and every lane of a wave with no piece, at the dropped out-of-range offset.
+    {
+      const uint32_t ro = (rec && lane == 0) ? 8u * (16u * t2 + (uint32_t)wid) : OOB_OFF;
+      __builtin_amdgcn_raw_buffer_store_b64(tile_v2u{(uint32_t)goff, (uint32_t)(goff >> 32)}, rs_po, (int)ro, 0, 0);
+    }
     // ---- copy this wave's piece of tile k-LAG out ----------------------------------------
     // Unconditional (nothing to copy: n2 = 0, every store dropped): the same store count
     // on every path lets the compiler wait for the prefetched loads with a counted vmcnt
@@ -1258,59 +1158,44 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // a piece larger than the region (data whose shortest codewords cluster) waits for
     // the tile's prefix instead and stores its bytes straight from registers (it has
     // published its arrival, so the prefix cannot depend on it)
-    // (GH_TILE_HOLD: the tile decoded last iteration, held in registers, is staged now and
-    // this one is held in its place)
-    const uint32_t st_t = GH_TILE_HOLD ? prevt : cur;
-    const bool have_st = st_t < p.ntiles;
-    const uint32_t st_tot = GH_TILE_HOLD ? wtp : wave_tot;
-    const uint32_t st_slot = GH_TILE_HOLD ? slotp : slot;
-    const bool staged = have_st && st_tot <= piece_cap;
-    auto stage_or_store = [&](const uint32_t (&sow)[U][OW], const uint32_t (&scnt)[U], const uint32_t (&sbpos)[U],
-                              int sgd) {
-      if (have_st && !staged) {
-        unsigned long long goffc = 0;
-        bool got = true;
-        if (lane == 0) {
-          unsigned long long g = __hip_atomic_load(&p.prefix[st_t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (!granule_ok(p, g, 2)) g = poll_granule(p, &p.prefix[st_t], 2);
-          got = granule_ok(p, g, 2);  // false only after a timeout (then nothing is written)
-          asm volatile("" ::: "memory");
-          goffc = (g & GRAN_VMASK) + s_off[st_slot * NW + wid];
-          if (wid == NW - 1 && st_t == p.ntiles - 1 && got) *p.total = goffc + st_tot;
+    const bool staged = have_cur && wave_tot <= piece_cap;
+    if (have_cur && !staged) {
+      unsigned long long goffc = 0;
+      bool got = true;
+      if (lane == 0) {
+        unsigned long long g = __hip_atomic_load(&p.prefix[cur], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!granule_ok(p, g, 2)) g = poll_granule(p, &p.prefix[cur], 2);
+        got = granule_ok(p, g, 2);  // false only after a timeout (then nothing is written)
+        asm volatile("" ::: "memory");
+        goffc = (g & GRAN_VMASK) + s_off[slot * NW + wid];
+        if (got) p.piece_off[16ull * cur + (uint32_t)wid] = goffc;
+        if (wid == NW - 1 && cur == p.ntiles - 1 && got) {
+          *p.total = goffc + wave_tot;
+          p.piece_off[16ull * p.ntiles] = goffc + wave_tot;
         }
-        goffc = rfl_u64(goffc);
-        if (__builtin_amdgcn_readfirstlane(got ? 1 : 0)) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) store_direct(p.out, p.out_cap, goffc + sbpos[u], sow[u], scnt[u]);
-        }
-        // (rare path) drain its data-dependent loads and stores here, so that the
-        // compiler's wait for the next tile's loads stays a counted vmcnt on the common path
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-      } else if (have_st && !(GH_TILE_ABLATE & 2)) {
-        const uint32_t sbase = region0 + buf * NW * p.stage_bytes + STAGE_PAD;
-        uint32_t o[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) o[u] = sbase + sbpos[u];
-        // no segment of the wave holds more than GRP * gdone codewords: rounds above its
-        // last dword are skipped
-        stage_wave<U, OW>(sow, scnt, o, min(OW, (GRP * sgd + 3) >> 2));
       }
-    };
-    if constexpr (GH_TILE_HOLD) {
-      stage_or_store(owp, cntp, bposp, gdp);
+      goffc = rfl_u64(goffc);
+      if (__builtin_amdgcn_readfirstlane(got ? 1 : 0)) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        cntp[u] = cnt[u];
-        bposp[u] = bpos[u];
-#pragma unroll
-        for (int k2 = 0; k2 < OW; ++k2) owp[u][k2] = ow[u][k2];
+        for (int u = 0; u < U; ++u) store_direct(p.out, p.out_cap, goffc + bpos[u], ow[u], cnt[u]);
       }
-      wtp = wave_tot;
-      gdp = gdone;
-    } else {
-      stage_or_store(ow, cnt, bpos, gdone);
+      // (rare path) drain its data-dependent loads and stores here, so that the
+      // compiler's wait for the next tile's loads stays a counted vmcnt on the common path
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    } else if (have_cur && !(GH_TILE_ABLATE & 2)) {
+      const uint32_t sbase = region0 + buf * NW * p.stage_bytes + STAGE_PAD;
+      uint32_t o[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) o[u] = sbase + bpos[u];
+      // no segment of the wave holds more than GRP * gdone codewords: rounds above its
+      // last dword are skipped
+      stage_wave<U, OW>(ow, cnt, o, min(OW, (GRP * gdone + 3) >> 2));
     }
     TSTAMP(6);
+#pragma unroll
+    for (int i = TILE_LAG - 1; i > 0; --i) th[i] = th[i - 1];
+    th[0] = staged ? cur : NONE;
+    }
 #if GH_TILE_STAMPS
     TSTAMP(7);
     TSTAMP(8);
@@ -1322,20 +1207,12 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                          (uint32_t)(ts[8] - ts[7]));
     }
 #endif
-#pragma unroll
-    for (int i = TILE_LAG - 1; i > 0; --i) th[i] = th[i - 1];
-    th[0] = staged ? st_t : NONE;
-    if constexpr (GH_TILE_HOLD) prevt = have_cur ? cur : NONE;
     cur = nxt < p.ntiles ? nxt : NONE;
-    if constexpr (!GH_TILE_DYN) nxt += G;
+    nxt += G;
     return true;
   };
-  for (uint32_t k = 0;; k += NSET) {
-    if (!body(std::integral_constant<int, 0>{}, k)) break;
-    if constexpr (NSET == 2) {
-      if (!body(std::integral_constant<int, NSET - 1>{}, k + 1)) break;
-    }
-  }
+  for (uint32_t k = 0;; ++k)
+    if (!body(k)) break;
 #if GH_TILE_STAMPS
   if (tid == 0) {
     wring[2] = __builtin_amdgcn_s_memtime();

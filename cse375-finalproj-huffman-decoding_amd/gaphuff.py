@@ -39,6 +39,8 @@ GH_ST_BADCODE = 1
 GH_ST_TIMEOUT = 2
 GH_ST_LAYOUT = 4
 GH_ST_RANGE, GH_ST_DSTSMALL, GH_ST_PIECES = 8, 16, 32  # device-planned gather
+GH_ST_OFFSETS = 64  # a piece disagreed with the recorded piece offsets
+GH_OFFS_NONE, GH_OFFS_RECORDED, GH_OFFS_READY = 0, 1, 2  # gh_ctx_offsets_state
 GH_GATHER_MAX_RANGES = 1 << 24
 
 # Every symbol include/gaphuff.h declares (checked by tests/test_abi.py).
@@ -51,7 +53,7 @@ EXPORTED = (
     "gh_ectx_create", "gh_ectx_destroy", "gh_ectx_load", "gh_ectx_plan", "gh_ectx_encode",
     "gh_ectx_download", "gh_ctx_device", "gh_sync_gaps", "gh_ctx_load_raw",
     "gh_ctx_load_file", "gh_ctx_save_file", "gh_dev_alloc", "gh_dev_free", "gh_dev_copy",
-    "gh_raw_parse", "gh_bw_copy", "gh_ctx_kernel_shape", "gh_kernel_shapes",
+    "gh_raw_parse", "gh_bw_copy", "gh_ctx_kernel_shape", "gh_kernel_shapes", "gh_ctx_offsets_state",
     "gh_index_bytes", "gh_index_parse", "gh_index_locate", "gh_ctx_build_index",
     "gh_gather_plan", "gh_ctx_gather", "gh_encode_index", "gh_ectx_index",
     "gh_encode_plan_from_counts", "gh_encode_bound", "gh_slice_extent", "gh_encode_slice",
@@ -261,6 +263,7 @@ def lib() -> ctypes.CDLL:
             "gh_ectx_download": ([P, P, U64], I),
             "gh_ctx_device": ([P, ctypes.POINTER(I)], I),
             "gh_ctx_kernel_shape": ([P, ctypes.c_char_p, ctypes.c_size_t], I),
+            "gh_ctx_offsets_state": ([P, ctypes.POINTER(ctypes.c_int)], I),
             "gh_kernel_shapes": ([ctypes.c_char_p, ctypes.c_size_t], I),
             "gh_sync_gaps": ([I, P, U32, P, U64, P, P, ctypes.POINTER(gh_sync_report)], I),
             "gh_ctx_load_raw": ([P, P, U32, U64, P, U64, U64, ctypes.POINTER(gh_sync_report)], I),
@@ -880,6 +883,13 @@ class Decoder(_Handle):
     def kernel_shape(self) -> str:
         """Name of the kernel instantiation(s) the last load picked (gh_ctx_kernel_shape)."""
         return _name(lib().gh_ctx_kernel_shape, self._h, cap=256)
+
+    def offsets_state(self) -> int:
+        """State of the loaded shard's known piece offsets (gh_ctx_offsets_state):
+        GH_OFFS_NONE, GH_OFFS_RECORDED, or GH_OFFS_READY when the next decode reads them."""
+        st = ctypes.c_int()
+        _check(lib().gh_ctx_offsets_state(self._h, ctypes.byref(st)))
+        return int(st.value)
 
     def build_index(self, log2_stride: int = 8):
         """Seek index of the loaded stream (the load must cover all its segments), built on

@@ -276,6 +276,8 @@ typedef struct gh_report {
 #define GH_ST_BADCODE 1u    /* a bit pattern outside the code space was met       */
 #define GH_ST_TIMEOUT 2u    /* look-back spin gave up (never expected)            */
 #define GH_ST_LAYOUT 4u     /* kernel LDS layout assumption violated (never expected) */
+#define GH_ST_OFFSETS 64u   /* a piece disagreed with the recorded piece offsets; it was
+                               not written (never expected; 8, 16, 32: the gathers' bits) */
 
 /* Create a context on HIP device `device` (ordinal among visible devices). */
 int gh_ctx_create(int device, gh_ctx** out);
@@ -317,6 +319,20 @@ int gh_ctx_device(gh_ctx* ctx, int* device);
  * "ws_count<U,TB,GL,fb=F>+ws_write<U,TB,GL,NS,fb=F>" (wave split); empty for an empty
  * shard.  GH_E_SMALL when cap is too small, GH_E_STATE before a load. */
 int gh_ctx_kernel_shape(gh_ctx* ctx, char* buf, size_t cap);
+/* Known piece offsets of the loaded shard (tile kernel).  Where every wave's piece goes
+ * in the output is a function of the loaded shard alone: the first decodes after a load
+ * work it out (a chain of prefixes across the workgroups) and record it; once a wait the
+ * host makes anyway (gh_ctx_report, gh_ctx_download, ...) has seen such a decode finish
+ * with status 0, later decodes of the same load read the offsets instead.  *state:
+ * NONE after a load (always, for shards the tile kernel does not take), RECORDED once a
+ * recording decode is enqueued, READY when the next decode will use the offsets.  A
+ * decode that reports a status bit goes back to NONE.  GH_TILE_OFFS=0 in the environment
+ * at load time keeps every decode recording (tests, A/B timing).  The name of
+ * gh_ctx_kernel_shape does not change with the state. */
+#define GH_OFFS_NONE 0
+#define GH_OFFS_RECORDED 1
+#define GH_OFFS_READY 2
+int gh_ctx_offsets_state(gh_ctx* ctx, int* state);
 /* Every kernel name a load can pick (the count and write kernels of the wave split
  * separately), one per line.  Needs no device. */
 int gh_kernel_shapes(char* buf, size_t cap);
