@@ -24,6 +24,7 @@
 #include "gh_internal.hpp"
 #include "gh_pm_flat.hpp"
 #include "gh_planes.hpp"
+#include "gh_planes_gather.hpp"
 #include "gh_raw_trans.hpp"
 
 namespace gh {
@@ -1167,6 +1168,69 @@ extern "C" int gh_planes_join_host(const gh_planes_item* item, const void* const
     case 4: planes_join_t<4>(dst, item->nelem, pl); break;
     default: planes_join_t<8>(dst, item->nelem, pl); break;
   }
+  return GH_OK;
+}
+
+// Element gather: the tensors' descriptors and the host plan (gaphuff.h, "element gather"), the
+// loop form of what gh_pgather_scan_kernel and gh_pgather_expand_kernel do with the same
+// arithmetic (gh_planes_gather.hpp).
+int gh::pgather_descs(const gh_planes_item* items, uint32_t ntensors, std::vector<PlanesTensor>& desc,
+                      uint32_t* nstreams, uint64_t* stored_bytes, uint32_t* max_coded) {
+  std::vector<gh_planes_slot> slots((size_t)PLANES_MAX_E * std::max(ntensors, 1u));
+  if (int rc = gh_planes_layout(items, ntensors, slots.data(), nstreams, stored_bytes)) return rc;
+  desc.assign(ntensors, PlanesTensor{});
+  *max_coded = 0;
+  for (uint32_t t = 0; t < ntensors; ++t) {
+    const gh_planes_item& it = items[t];
+    if (it.nelem >= PG_MAX_TENSOR_BYTES / it.elem_size)
+      return fail(GH_E_ARG, "tensor " + std::to_string(t) + ": 2^40 bytes or more");
+    PlanesTensor& d = desc[t];
+    d.nelem = it.nelem;
+    d.elem = it.elem_size;
+    d.mask = it.coded_mask;
+    *max_coded = std::max(*max_coded, pg_popc(d.mask));
+    for (uint32_t p = 0; p < PLANES_MAX_E; ++p) {
+      d.stream[p] = slots[PLANES_MAX_E * t + p].stream;
+      d.off[p] = slots[PLANES_MAX_E * t + p].stored_off;
+    }
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_pgather_plan(const gh_planes_item* items, uint32_t ntensors, const uint32_t* stream_status,
+                               const gh_erange* ranges, uint32_t nranges, gh_brange* branges, uint64_t cap,
+                               uint64_t* nbranges, uint64_t* stage_off, uint64_t* dst_off, uint64_t* out_bytes,
+                               uint32_t* bad_ranges) {
+  if (nbranges) *nbranges = 0;
+  if (out_bytes) *out_bytes = 0;
+  if (bad_ranges) *bad_ranges = 0;
+  if (!nbranges || !out_bytes || !bad_ranges || (ntensors && !items) || (nranges && (!ranges || !stage_off || !dst_off)) ||
+      (cap && !branges))
+    return fail(GH_E_ARG, "null argument");
+  if (nranges > PG_MAX_RANGES) return fail(GH_E_ARG, "gh_pgather_plan: more than 2^21 ranges in one call");
+  std::vector<PlanesTensor> desc;
+  uint32_t ns = 0, maxc = 0;
+  uint64_t stored_bytes = 0;
+  if (int rc = pgather_descs(items, ntensors, desc, &ns, &stored_bytes, &maxc)) return rc;
+  uint64_t nb = 0, stage = 0, dst = 0;
+  uint32_t bad = 0;
+  for (uint32_t i = 0; i < nranges; ++i) {
+    const PgLoc loc = pg_locate([&](uint32_t t) -> const PlanesTensor& { return desc[t]; },
+                                [&](uint32_t s) { return stream_status ? stream_status[s] : 0u; }, ntensors, ranges[i]);
+    if (loc.ncoded == PG_BAD)
+      return fail(GH_E_ARG, "range " + std::to_string(i) + ": no such tensor, or elements outside [0, nelem] of its tensor");
+    if (nb + loc.ncoded <= cap) pg_emit(desc[ranges[i].tensor], ranges[i], branges + nb);
+    stage_off[i] = stage;
+    dst_off[i] = dst;
+    nb += loc.ncoded;
+    stage += loc.stage;
+    dst += loc.dst;
+    bad += loc.flagged;
+  }
+  *nbranges = nb;
+  *out_bytes = dst;
+  *bad_ranges = bad;
+  if (nb > cap) return fail(GH_E_SMALL, "byte-range buffer smaller than the plan");
   return GH_OK;
 }
 

@@ -39,6 +39,7 @@
 #include "gh_internal.hpp"
 #include "gh_lut.hpp"
 #include "gh_planes.hpp"
+#include "gh_planes_gather.hpp"
 #include "gh_raw_trans.hpp"
 #include "gh_units.hpp"
 
@@ -55,6 +56,7 @@ constexpr uint32_t EPOCH_MAX = (1u << 24) - 1;
 #include "gh_batch_raw.hip"
 #include "gh_batch_gather.hip"
 #include "gh_planes_join.hip"
+#include "gh_planes_gather.hip"
 #include "gh_mtile.hip"
 
 }  // namespace gh
@@ -1677,6 +1679,17 @@ struct BatchPlanes {
   bool enqueued = false, timed = false;
 };
 
+// The element gather's state in a gh_batch (gh_pgather_*).  desc: the tensors' descriptors, as
+// uploaded (last_desc: their host copy; a call with the same list uploads nothing); per: the
+// per-range arrays (loc: PgLoc; stage_off, dst_off: u64; slot, unit0: u32); words: PgatherParams's.
+struct BatchPGather {
+  DevBuf desc, words, branges, per, staging, ranges;  // (ranges: gh_pgather's upload)
+  std::vector<uint8_t> last_desc;
+  EventPair ev_x, ev_j;  // around the memset, scan and expand; around the range join
+  uint64_t nslots = 0;
+  bool enqueued = false, timed = false;
+};
+
 struct gh_batch {
   DevBuf payload, gaps, tables, desc, unit0, syms, items;  // the loaded batch
   DevBuf seg_cnt, unit_tot, unit_off, symbols;             // decode scratch
@@ -1693,6 +1706,7 @@ struct gh_batch {
   bool indexed = false;  // seg_cnt / unit_off / status are (being) made by a decode or an index since the load
   BatchGather g;
   BatchPlanes pl;
+  BatchPGather pg;
   BatchQueue q;  // (last: its destructor waits for the decode before the buffers above go)
 };
 
@@ -1717,7 +1731,8 @@ static int batch_load(gh_batch* b, const std::vector<gh_stream>& ss, bool device
   const uint32_t ns = (uint32_t)ss.size();
   GH_HIP(hipSetDevice(b->q.device));
   if (int rc = b->q.quiesce()) return rc;  // the previous batch's decode reads what is replaced
-  b->loaded = b->own_out = b->indexed = b->g.enqueued = b->pl.enqueued = b->raw = false;
+  b->loaded = b->own_out = b->indexed = b->g.enqueued = b->pl.enqueued = b->pg.enqueued = b->raw = false;
+  b->pg.last_desc.clear();
   std::vector<uint64_t> n(ns), w(ns), g(ns);
   std::vector<BatchDesc> desc(ns);
   std::vector<gh_sym> syms;
@@ -2327,6 +2342,166 @@ extern "C" int gh_planes_wait(gh_batch* b, gh_planes_report* rep) {
     return fail(GH_E_CORRUPT, std::to_string(bad) + " tensor(s) have a coded plane the decode flagged (gh_batch_status "
                                                     "names its stream); their bytes were left as they were");
   return GH_OK;
+}
+
+// ---- element gather (gaphuff.h; kernels: gh_planes_gather.hip; arithmetic: gh_planes_gather.hpp) ----
+// memset, locate, scan, expand; the batched gather's five; the range join
+constexpr uint32_t PGATHER_LAUNCHES = 4 + BATCH_GATHER_LAUNCHES + 1;
+static_assert(PGATHER_LAUNCHES == GH_PGATHER_LAUNCHES, "the header states the launch count");
+constexpr uint32_t PGATHER_WORDS = 16;
+
+// A member of the batch's queue as the batched gather is, which it runs between its own kernels.
+extern "C" int gh_pgather_device(gh_batch* b, const gh_planes_item* items, uint32_t ntensors, const void* d_stored,
+                                 uint64_t stored_len, const gh_erange* d_ranges, uint32_t nranges, void* d_dst,
+                                 uint64_t dst_len, void* hip_stream, int timed) {
+  if (!b || (ntensors && !items)) return fail(GH_E_ARG, "null argument");
+  if (!b->loaded || !b->indexed)
+    return fail(GH_E_STATE, "gh_pgather_device without gh_batchdec_index or gh_batch_decode since the load");
+  if (nranges == 0) return GH_OK;
+  if ((uintptr_t)d_stored & 15u) return fail(GH_E_ARG, "stored arena not 16-byte aligned");
+  std::vector<PlanesTensor> desc;
+  uint32_t ns = 0, maxc = 0;
+  uint64_t stored_bytes = 0;
+  if (int rc = pgather_descs(items, ntensors, desc, &ns, &stored_bytes, &maxc)) return rc;
+  if (ns != b->nstreams) return fail(GH_E_ARG, "the tensors' coded planes are not the loaded batch's streams");
+  if (stored_bytes && !d_stored) return fail(GH_E_ARG, "null stored arena");
+  if (stored_len < stored_bytes) return fail(GH_E_SMALL, "stored arena smaller than the stored planes");
+  for (uint32_t t = 0; t < ntensors; ++t)
+    for (uint32_t p = 0; p < items[t].elem_size; ++p)
+      if (desc[t].stream[p] != GH_PLANES_STORED && b->n[desc[t].stream[p]] != items[t].nelem)
+        return fail(GH_E_ARG, "tensor " + std::to_string(t) + ": nelem differs from its stream's n in the loaded batch");
+  if (!d_ranges || !d_dst) return fail(GH_E_ARG, "null argument");
+  if (nranges > PG_MAX_RANGES) return fail(GH_E_ARG, "gh_pgather_device: more than 2^21 ranges in one call");
+  // a plan that stands has at most this many units: every range ceil(len / 1024), the lens' bytes within dst_len
+  const uint64_t unit_bound = (uint64_t)nranges + dst_len / PLANES_UNIT_ELEMS;
+  if (unit_bound >= PLANES_MAX_UNITS) return fail(GH_E_ARG, "gh_pgather_device: the destination reaches 2^31 work units");
+  GH_HIP(hipSetDevice(b->q.device));
+  BatchPGather& pg = b->pg;
+  if (int rc = pg.ev_x.create()) return rc;
+  if (int rc = pg.ev_j.create()) return rc;
+  // the host does not know how many byte ranges the device will cut: the inner gather gets this
+  // many slots, the ones past the device's count empty
+  const uint64_t nslots = (uint64_t)maxc * nranges;
+  const size_t dbytes = sizeof(PlanesTensor) * (size_t)ntensors;
+  const bool same_desc = pg.last_desc.size() == dbytes && (!dbytes || !std::memcmp(pg.last_desc.data(), desc.data(), dbytes));
+  // The staging buffer: dst_len bytes hold every staged plane (C <= E).  No padding past it: a
+  // lane loads 16 bytes only where all 16 lie inside its range's plane, every other lane byte by byte.
+  const uint64_t per_bytes = (sizeof(PgLoc) + 24ull) * nranges + 8;  // loc, stage_off, dst_off (u64), slot, unit0 (u32; unit0 has nranges + 1)
+  if (!same_desc || pg.staging.capacity() < std::max<uint64_t>(dst_len, 16) || pg.per.capacity() < per_bytes ||
+      pg.branges.capacity() < std::max<uint64_t>(nslots * sizeof(gh_brange), 16) || !pg.words) {
+    if (b->q.enqueued) GH_HIP(hipEventSynchronize(b->q.done));  // the last gather in flight uses the old buffers
+    if (!same_desc) {
+      pg.last_desc.clear();
+      if (int rc = upload_at_least(pg.desc, desc.data(), dbytes)) return rc;
+      pg.last_desc.assign((const uint8_t*)desc.data(), (const uint8_t*)desc.data() + dbytes);
+    }
+    if (int rc = pg.staging.reserve(std::max<uint64_t>(dst_len, 16))) return rc;
+    if (int rc = pg.per.reserve(per_bytes)) return rc;
+    if (int rc = pg.branges.reserve(std::max<uint64_t>(nslots * sizeof(gh_brange), 16))) return rc;
+    if (int rc = pg.words.reserve(4 * PGATHER_WORDS)) return rc;
+  }
+  PgatherParams pp{};
+  pp.ranges = d_ranges;
+  pp.desc = pg.desc.get<PlanesTensor>();
+  pp.stream_status = b->flags.get<unsigned int>() + 4;
+  pp.branges = pg.branges.get<gh_brange>();
+  pp.loc = pg.per.get<PgLoc>();
+  pp.stage_off = (unsigned long long*)(pp.loc + nranges);
+  pp.dst_off = pp.stage_off + nranges;
+  pp.slot = (uint32_t*)(pp.dst_off + nranges);
+  pp.unit0 = pp.slot + nranges;
+  pp.words = pg.words.get<unsigned int>();
+  pp.stage = pg.staging.get<uint8_t>();
+  pp.stored = (const uint8_t*)d_stored;
+  pp.dst = (uint8_t*)d_dst;
+  pp.dst_len = dst_len;
+  pp.nslots = nslots;
+  pp.nranges = nranges;
+  pp.ntensors = ntensors;
+  const uint32_t grid_r = (uint32_t)ceil_div((uint64_t)nranges, (uint64_t)GP_TB);
+  void* pa[1] = {&pp};
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)b->q.stream;
+  GH_HIP(hipStreamWaitEvent(st, b->q.done, 0));  // (indexed: the queue has a run)
+  if (timed) GH_HIP(hipEventRecord(pg.ev_x.a, st));
+  GH_HIP(hipMemsetAsync(pp.words, 0, 4 * PGATHER_WORDS, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_pgather_locate_kernel, dim3(grid_r), dim3(GP_TB), pa, 0, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_pgather_scan_kernel, dim3(1), dim3(PGS_TB), pa, 0, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_pgather_expand_kernel, dim3(grid_r), dim3(GP_TB), pa, 0, st));
+  GH_HIP(hipGetLastError());
+  if (timed) GH_HIP(hipEventRecord(pg.ev_x.b, st));
+  GH_HIP(hipEventRecord(b->q.done, st));
+  // (a list without coded planes has no slot and no inner gather: its status word is words[8], zero)
+  if (nslots)
+    if (int rc = gh_batchdec_gather_device(b, pp.branges, (uint32_t)nslots, pg.staging.get(), dst_len, st, timed)) return rc;
+  pp.inner_status = nslots ? b->g.words.get<unsigned int>() : pp.words + 8;
+  // GH_PLANES_GRID=k (tests): k workgroups, so that one wave walks many units and ranges
+  const uint32_t grid = unit_grid("GH_PLANES_GRID", unit_bound, PJ_WAVES, b->q.num_cu);
+  if (timed) GH_HIP(hipEventRecord(pg.ev_j.a, st));
+  GH_HIP(hipLaunchKernel((const void*)gh_pgather_join_kernel, dim3(grid), dim3(PJ_TB), pa, 0, st));
+  GH_HIP(hipGetLastError());
+  if (timed) GH_HIP(hipEventRecord(pg.ev_j.b, st));
+  GH_HIP(hipEventRecord(b->q.done, st));
+  pg.enqueued = true;
+  pg.timed = timed != 0;
+  pg.nslots = nslots;
+  return GH_OK;
+}
+
+extern "C" int gh_pgather_wait(gh_batch* b, gh_pgather_report* rep) {
+  if (rep) *rep = gh_pgather_report{};
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded || !b->pg.enqueued) return fail(GH_E_STATE, "gh_pgather_wait without an element gather since the load");
+  GH_HIP(hipSetDevice(b->q.device));
+  GH_HIP(hipEventSynchronize(b->q.done));
+  unsigned int w[PGATHER_WORDS] = {}, iw[8] = {};
+  GH_HIP(hipMemcpy(w, b->pg.words.get(), sizeof(w), hipMemcpyDeviceToHost));
+  if (b->pg.nslots) GH_HIP(hipMemcpy(iw, b->g.words.get(), sizeof(iw), hipMemcpyDeviceToHost));
+  float all = 0, ex = 0, jo = 0;
+  if (b->pg.timed) {
+    GH_HIP(hipEventElapsedTime(&all, b->pg.ev_x.a, b->pg.ev_j.b));
+    if (int rc = b->pg.ev_x.elapsed(&ex)) return rc;
+    if (int rc = b->pg.ev_j.elapsed(&jo)) return rc;
+  }
+  // (the inner gather's range and size refusals follow this gather's own: its plan is this one's)
+  const uint32_t status = w[0] | (iw[0] & (uint32_t)GH_ST_PIECES) | (w[6] ? (uint32_t)GH_ST_BADCODE : 0u);
+  if (rep) {
+    if (!(w[0] & GH_ST_RANGE)) std::memcpy(&rep->out_bytes, w + 2, 8);
+    rep->npieces = iw[1];
+    rep->bad_ranges = w[6];
+    rep->status = status;
+    rep->kernel_ms = all;
+    rep->launches = PGATHER_LAUNCHES;
+    rep->expand_ms = ex;
+    rep->join_ms = jo;
+  }
+  if (status & GH_ST_RANGE) return fail(GH_E_ARG, "element gather: a range names no tensor of the list or elements outside [0, nelem] of its tensor");
+  if (status & GH_ST_DSTSMALL) return fail(GH_E_SMALL, "element gather: destination smaller than the ranges' bytes");
+  if (status & GH_ST_PIECES) return fail(GH_E_CORRUPT, "element gather: the inner plan exceeds the piece bound");
+  if (status & GH_ST_BADCODE)
+    return fail(GH_E_CORRUPT, std::to_string(w[6]) + " range(s) name a tensor with a coded plane the index pass flagged "
+                                                     "(gh_batch_status names its stream); their bytes were left as they were");
+  return GH_OK;
+}
+
+extern "C" int gh_pgather(gh_batch* b, const gh_planes_item* items, uint32_t ntensors, const void* d_stored,
+                          uint64_t stored_len, const gh_erange* ranges, uint32_t nranges, void* d_dst, uint64_t dst_len,
+                          void* hip_stream, gh_pgather_report* rep) {
+  if (rep) *rep = gh_pgather_report{};
+  if (!b) return fail(GH_E_ARG, "null batch");
+  if (!b->loaded || !b->indexed)
+    return fail(GH_E_STATE, "gh_pgather without gh_batchdec_index or gh_batch_decode since the load");
+  if (nranges && !ranges) return fail(GH_E_ARG, "null argument");
+  GH_HIP(hipSetDevice(b->q.device));
+  if (b->pg.enqueued) GH_HIP(hipEventSynchronize(b->q.done));  // (the last gather may still read the old upload)
+  if (int rc = upload_at_least(b->pg.ranges, ranges, sizeof(gh_erange) * (uint64_t)nranges)) return rc;
+  if (int rc = gh_pgather_device(b, items, ntensors, d_stored, stored_len, b->pg.ranges.get<gh_erange>(), nranges, d_dst,
+                                 dst_len, hip_stream, 1))
+    return rc;
+  if (nranges == 0) {
+    if (rep) rep->launches = PGATHER_LAUNCHES;
+    return GH_OK;
+  }
+  return gh_pgather_wait(b, rep);
 }
 
 // Decode time of a set of shards: decodes on one device run in turn (DevChain), so a

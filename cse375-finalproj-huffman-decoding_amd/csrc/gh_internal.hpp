@@ -113,6 +113,15 @@ int ebatch_in_plan(const uint64_t* n, uint32_t nstreams, EBatchInPlan& out);
 // gives: GH_E_ARG otherwise).
 int ebatch_out_plan(const uint64_t* w, const uint64_t* g, uint32_t nstreams, EBatchOutPlan& out);
 
+// The tensors of an element gather as its kernels see them (gaphuff.h, "element gather"): by
+// gh_planes_layout, with data null and off[p] a stored plane's stored_off (0 for a coded plane).
+// Host arithmetic only (gh_core.cpp), shared by gh_pgather_plan and gh_pgather_device.
+// GH_E_ARG as gh_planes_layout, and for a tensor of 2^40 bytes or more; *max_coded: the largest
+// number of coded planes of a tensor.
+struct PlanesTensor;
+int pgather_descs(const gh_planes_item* items, uint32_t ntensors, std::vector<PlanesTensor>& desc,
+                  uint32_t* nstreams, uint64_t* stored_bytes, uint32_t* max_coded);
+
 // Encoder plan from plan->n and plan->count[] (symbol order, package-merge lengths,
 // canonical codes, sizes, header version); shared by the host and GPU encoders.
 int plan_from_counts(gh_encode_plan* plan, int force_version);

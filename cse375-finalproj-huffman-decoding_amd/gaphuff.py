@@ -42,6 +42,8 @@ GH_ST_RANGE, GH_ST_DSTSMALL, GH_ST_PIECES = 8, 16, 32  # device-planned gather
 GH_ST_OFFSETS = 64  # a piece disagreed with the recorded piece offsets
 GH_OFFS_NONE, GH_OFFS_RECORDED, GH_OFFS_READY = 0, 1, 2  # gh_ctx_offsets_state
 GH_GATHER_MAX_RANGES = 1 << 24
+GH_PGATHER_MAX_RANGES = GH_GATHER_MAX_RANGES // 8
+GH_PGATHER_LAUNCHES = 10
 
 # Every symbol include/gaphuff.h declares (checked by tests/test_abi.py).
 EXPORTED = (
@@ -77,6 +79,7 @@ EXPORTED = (
     "gh_batchraw_gaps_host", "gh_batchraw_kernel_shape", "gh_batchraw_kernel_shapes",
     "gh_planes_layout", "gh_planes_split_host", "gh_planes_join_host", "gh_planes_load", "gh_planes_load_device",
     "gh_planes_load_times", "gh_planes_join_device", "gh_planes_wait", "gh_planes_image_bytes", "gh_planes_image_write", "gh_planes_parse",
+    "gh_pgather_plan", "gh_pgather_device", "gh_pgather_wait", "gh_pgather",
 )
 GH_EBATCH_UNIT_BYTES = 1024
 GH_PLANES_STORED = 0xFFFFFFFF
@@ -201,6 +204,16 @@ class gh_planes_slot(ctypes.Structure):
 class gh_planes_report(ctypes.Structure):
     _fields_ = [("out_bytes", ctypes.c_uint64), ("ntensors", ctypes.c_uint32), ("bad_tensors", ctypes.c_uint32),
                 ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
+
+
+class gh_erange(ctypes.Structure):
+    _fields_ = [("tensor", ctypes.c_uint64), ("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64)]
+
+
+class gh_pgather_report(ctypes.Structure):
+    _fields_ = [("out_bytes", ctypes.c_uint64), ("npieces", ctypes.c_uint64), ("bad_ranges", ctypes.c_uint32),
+                ("status", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32),
+                ("expand_ms", ctypes.c_float), ("join_ms", ctypes.c_float)]
 
 
 class gh_planes_image(ctypes.Structure):
@@ -374,6 +387,12 @@ def lib() -> ctypes.CDLL:
             "gh_planes_image_bytes": ([U32, P, ctypes.POINTER(U64)], I),
             "gh_planes_image_write": ([ctypes.POINTER(gh_planes_item), ctypes.POINTER(P), P, P, U64], I),
             "gh_planes_parse": ([P, ctypes.c_size_t, ctypes.POINTER(gh_planes_image)], I),
+            "gh_pgather_plan": ([ctypes.POINTER(gh_planes_item), U32, P, P, U32, P, U64, ctypes.POINTER(U64), P, P,
+                                 ctypes.POINTER(U64), ctypes.POINTER(U32)], I),
+            "gh_pgather_device": ([P, ctypes.POINTER(gh_planes_item), U32, P, U64, P, U32, P, U64, P, I], I),
+            "gh_pgather_wait": ([P, ctypes.POINTER(gh_pgather_report)], I),
+            "gh_pgather": ([P, ctypes.POINTER(gh_planes_item), U32, P, U64, P, U32, P, U64, P,
+                            ctypes.POINTER(gh_pgather_report)], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -1286,6 +1305,59 @@ class BatchDecoder(_Handle):
         :class:`GapHuffError` (with the report as ``.report``) when a tensor was skipped."""
         return self._wait(lib().gh_planes_wait, gh_planes_report())
 
+    def gather_elements_device(self, items, stored_ptr: int, stored_len: int, ranges_ptr: int, nranges: int,
+                               dst_ptr: int, dst_len: int, hip_stream: int = 0, timed: bool = True) -> None:
+        """Enqueue the gather of ``nranges`` (tensor, lo, hi) ELEMENT ranges held in device memory
+        at ``ranges_ptr`` (a contiguous int64 / uint64 [n, 3] array) into the ``dst_len`` device
+        bytes at ``dst_ptr`` and return without waiting (gh_pgather_device).  ``items`` are
+        :meth:`join_planes_device`'s (the address is ignored), ``stored_ptr`` the stored arena.
+        Needs an :meth:`index` or a :meth:`decode` since the load, no output arena.  What only
+        the device finds is raised by :meth:`elements_wait`."""
+        arr, n = _planes_items(items)
+        _check(lib().gh_pgather_device(self._h, arr, n, ctypes.c_void_p(stored_ptr or None), stored_len,
+                                       ctypes.c_void_p(ranges_ptr or None), nranges, ctypes.c_void_p(dst_ptr or None),
+                                       dst_len, ctypes.c_void_p(hip_stream or None), int(timed)))
+
+    def elements_wait(self) -> gh_pgather_report:
+        """Wait for the last element gather and return its report; raises :class:`GapHuffError`
+        (with the report as ``.report``) on a device-side refusal or a range on a flagged tensor."""
+        return self._wait(lib().gh_pgather_wait, gh_pgather_report())
+
+    def gather_elements(self, items, stored, ranges) -> list:
+        """The elements of each ``(tensor, lo, hi)`` range, one numpy array per range in request
+        order, viewed as unsigned integers of the tensor's element size (gh_pgather).  ``items``:
+        ``(address, nelem, elem_size, coded_mask)`` of the loaded tensor list; ``stored``: its
+        stored arena in host memory (np.uint8, as :func:`planes_layout` lays it out).  Runs
+        :meth:`index` first when the batch is neither indexed nor decoded."""
+        items = list(items)
+        r = _branges(ranges)
+        if not self._indexed:
+            self.index()
+        ok = bool(r.size) and (r[:, 0] < len(items)).all() and (r[:, 2] >= r[:, 1]).all()
+        es = np.asarray([items[int(t)][2] for t in r[:, 0]], dtype=np.int64) if ok else np.zeros(0, np.int64)
+        lens = (r[:, 2] - r[:, 1]).astype(np.int64) * es if ok else np.zeros(0, np.int64)
+        total = int(lens.sum())
+        out = np.zeros(total, dtype=np.uint8)
+        stored = _u8(stored)
+        with DeviceBuffer(max(total, 16), self.device) as buf, DeviceBuffer(max(stored.size, 16), self.device) as st:
+            if stored.size:
+                st.upload(stored)
+            arr, n = _planes_items(items)
+            rep = gh_pgather_report()
+            rc = lib().gh_pgather(self._h, arr, n, st.ptr, stored.size, _ptr(r) if r.size else None, r.shape[0],
+                                  buf.ptr, total, None, ctypes.byref(rep))
+            if rc != GH_OK:
+                e = GapHuffError(rc, lib().gh_last_error().decode(errors="replace"))
+                e.report = rep
+                raise e
+            if total:
+                buf.download(out)
+        ends = np.cumsum(lens)
+        return [out[int(e - l): int(e)].view(_UINT_OF[int(k)]) for e, l, k in zip(ends, lens, es)]
+
+
+_UINT_OF = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+
 
 def decode_batch(images, device: int = 0) -> list:
     """Decode many compressed.huff images as one batch; returns their bytes in order."""
@@ -1490,6 +1562,33 @@ def planes_layout(items):
     return out, int(ns.value), int(sb.value)
 
 
+def planes_gather_plan(items, ranges, status=None):
+    """The element gather's plan from host arrays (gh_pgather_plan; needs no device): ``items``
+    are ``(address, nelem, elem_size, coded_mask)``, ``ranges`` (tensor, lo, hi) element triples,
+    ``status`` the batch's per-stream status words or None.  Returns ``(branges, stage_off,
+    dst_off, out_bytes, bad_ranges)``: the (stream, lo, hi) byte ranges of the inner batched
+    gather as a uint64 ``[m, 3]`` array and every range's byte offset in the staging buffer and in
+    the destination."""
+    arr, n = _planes_items(items)
+    r = _branges(ranges)
+    st = None if status is None else np.ascontiguousarray(status, dtype=np.uint32)
+    nr = r.shape[0]
+    so, do = np.zeros(nr, dtype=np.uint64), np.zeros(nr, dtype=np.uint64)
+    nb, ob, bad = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+
+    def call(br):
+        return lib().gh_pgather_plan(arr, n, _ptr(st) if st is not None and st.size else None,
+                                     _ptr(r) if nr else None, nr, _ptr(br) if br.size else None, br.shape[0],
+                                     ctypes.byref(nb), _ptr(so) if nr else None, _ptr(do) if nr else None,
+                                     ctypes.byref(ob), ctypes.byref(bad))
+    rc = call(np.zeros((0, 3), dtype=np.uint64))
+    if rc not in (GH_OK, -9):
+        _check(rc)
+    br = np.zeros((int(nb.value), 3), dtype=np.uint64)
+    _check(call(br))
+    return br, so, do, int(ob.value), int(bad.value)
+
+
 def planes_split_host(a, elem_size: Optional[int] = None) -> list:
     """The byte planes of ``a`` by the CPU twin of the split kernel (gh_planes_split_host): a
     list of ``elem_size`` np.uint8 arrays.  ``a``: a numpy array of 1/2/4/8-byte elements, or
@@ -1618,6 +1717,34 @@ def decode_tensors(images, device: int = 0) -> list:
             b.planes_wait()
             whole = dst.download(np.empty(int(offs[-1]), dtype=np.uint8)) if offs[-1] else np.zeros(0, np.uint8)
         return [whole[int(o): int(o) + n].copy() for o, n in zip(offs, sizes)]
+
+
+def _planes_streams(parsed):
+    """(shapes, streams, stored arena) of parsed containers, by :func:`planes_layout`."""
+    shapes = [(0, im.nelem, im.elem_size, im.coded_mask) for im in parsed]
+    slots, _, stored_bytes = planes_layout(shapes)
+    stored = np.zeros(stored_bytes, dtype=np.uint8)
+    streams = []
+    for im, sl in zip(parsed, slots):
+        for p in range(im.elem_size):
+            if sl[p][0] != GH_PLANES_STORED:
+                streams.append(im.planes[p])
+            else:
+                stored[sl[p][1]: sl[p][1] + im.nelem] = im.planes[p]
+    return shapes, streams, stored
+
+
+def decode_tensor_ranges(images, ranges, device: int = 0) -> list:
+    """The elements of each ``(tensor, lo, hi)`` range of byte-plane containers, one numpy array
+    per range (unsigned integers of the tensor's element size), without decoding the tensors:
+    loads the coded planes, uploads the stored planes, runs the index pass and one element gather
+    (:meth:`BatchDecoder.gather_elements`)."""
+    with BatchDecoder(device) as b:
+        parsed = [im if isinstance(im, PlanesImage) else parse_planes(im) for im in images]
+        shapes, streams, stored = _planes_streams(parsed)
+        b.load(streams)
+        b.index()
+        return [a.copy() for a in b.gather_elements(shapes, stored, ranges)]
 
 
 # --------------------------------------------------------------------------- random access

@@ -1,7 +1,7 @@
 // bin/decoder <compressed.huff | raw container> <output> [--gpus N] [--shards S] [--reps R] [--json]
 //             [--verify FILE] [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]
 //             [--index FILE --ranges FILE]
-// bin/decoder --batch LIST [--ranges FILE OUT]
+// bin/decoder --batch LIST [--ranges FILE OUT | --elements FILE OUT]
 // --batch LIST (a text file, one input<TAB>output per line) decodes all inputs as one batch
 // (gh_batch_*: one fixed set of launches however many streams) and writes every output.
 // When every input is a raw container the batch is loaded by gh_batchraw_load (the gap arrays
@@ -13,6 +13,10 @@
 // of LIST, blank lines not counted) indexes the batch without decoding it and gathers only the
 // named byte ranges (gh_batchdec_*); their concatenation in file order goes to OUT and the
 // per-input outputs of LIST are not written (its lines may then omit <TAB>output).
+// --batch LIST --elements FILE OUT (every input a byte-plane container; FILE: one `TENSOR LO:HI`
+// per line, TENSOR the 0-based line of LIST, LO:HI in elements) indexes the batch without decoding
+// it and gathers only the named element ranges (gh_pgather_*), interleaved as in the tensors;
+// their concatenation in file order goes to OUT.  --ranges stays refused for containers.
 // --shards S (default: one per GPU) splits the gap segments into S shards, shard k on
 // device k mod N, each streaming its own payload range and writing at its offset.
 // A raw-stream container (bin/encoder --raw, GH_RAW_MAGIC) is decoded by the
@@ -236,11 +240,123 @@ static int planes_batch_main(const char* list_file, const std::vector<std::strin
   return done(rc ? 1 : 0);
 }
 
+// --batch LIST --elements FILE OUT on a list of byte-plane containers (img[i], all read): the
+// coded planes loaded and indexed, the stored planes uploaded, the element ranges of FILE (one
+// `TENSOR LO:HI` per line) gathered by one gh_pgather call, their bytes written to OUT.
+static int planes_elements_main(const char* list_file, const std::vector<std::string>& in, const std::vector<size_t>& line_of,
+                                const std::vector<std::vector<uint8_t>>& img, const char* ranges_file, const char* range_out) {
+  const size_t nt = in.size();
+  std::vector<gh_planes_image> im(nt);
+  std::vector<gh_planes_item> items(nt);
+  std::vector<gh_planes_slot> slots(8 * std::max<size_t>(nt, 1));
+  int rc;
+  for (size_t i = 0; i < nt; ++i) {
+    if ((rc = gh_planes_parse(img[i].data(), img[i].size(), &im[i]))) {
+      std::fprintf(stderr, "decoder: %s: line %zu: %s: ", list_file, line_of[i], in[i].c_str());
+      return die("bad byte-plane container", rc);
+    }
+    items[i] = gh_planes_item{nullptr, im[i].nelem, im[i].elem_size, im[i].coded_mask};
+  }
+  uint32_t ns = 0;
+  uint64_t stored_bytes = 0;
+  if ((rc = gh_planes_layout(items.data(), (uint32_t)nt, slots.data(), &ns, &stored_bytes))) return die("layout", rc);
+  std::vector<gh_stream> streams(ns);
+  std::vector<uint8_t> stored((size_t)stored_bytes, 0);
+  for (size_t i = 0; i < nt; ++i)
+    for (uint32_t p = 0; p < im[i].elem_size; ++p) {
+      const gh_planes_slot& sl = slots[8 * i + p];
+      if (sl.stream != GH_PLANES_STORED) streams[sl.stream] = im[i].stream[p];
+      else if (im[i].nelem) std::memcpy(stored.data() + sl.stored_off, im[i].plane[p], (size_t)im[i].nelem);
+    }
+  std::vector<gh_erange> ranges;
+  std::vector<uint8_t> rtext;
+  if (!read_file(ranges_file, rtext)) { std::fprintf(stderr, "decoder: Could not open ranges file %s\n", ranges_file); return 1; }
+  rtext.push_back(0);
+  uint64_t total = 0;
+  for (const char* p = (const char*)rtext.data(); *p;) {
+    while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') ++p;
+    if (!*p) break;
+    char* end = nullptr;
+    gh_erange r{};
+    bool ok = *p >= '0' && *p <= '9';
+    if (ok) r.tensor = std::strtoull(p, &end, 10);
+    ok = ok && (*end == ' ' || *end == '\t');
+    if (ok) {
+      p = end;
+      while (*p == ' ' || *p == '\t') ++p;
+      ok = *p >= '0' && *p <= '9';
+    }
+    if (ok) r.lo = std::strtoull(p, &end, 10);
+    ok = ok && *end == ':' && end[1] >= '0' && end[1] <= '9';
+    if (ok) {
+      p = end + 1;
+      r.hi = std::strtoull(p, &end, 10);
+      ok = *end == 0 || *end == ' ' || *end == '\t' || *end == '\r' || *end == '\n';
+    }
+    if (!ok || ranges.size() >= GH_PGATHER_MAX_RANGES) {
+      std::fprintf(stderr, "decoder: %s: range %zu: expected TENSOR LO:HI\n", ranges_file, ranges.size() + 1);
+      return 1;
+    }
+    if (r.tensor >= nt || r.lo > r.hi || r.hi > im[r.tensor].nelem) {
+      std::fprintf(stderr, "decoder: %s: range %zu: no such tensor, or elements outside [0, nelem] of it\n", ranges_file, ranges.size() + 1);
+      return 1;
+    }
+    total += (r.hi - r.lo) * im[r.tensor].elem_size;
+    ranges.push_back(r);
+    p = end;
+  }
+  if (gh_device_count() < 1) return die("no HIP device", GH_E_NODEV);
+  gh_batch* b = nullptr;
+  void *d_dst = nullptr, *d_stored = nullptr;
+  auto done = [&](int r) {
+    if (d_dst) gh_dev_free(d_dst);
+    if (d_stored) gh_dev_free(d_stored);
+    gh_batch_destroy(b);
+    return r;
+  };
+  if ((rc = gh_batch_create(0, &b))) return die("device init", rc);
+  const double t0 = now_ms();
+  if ((rc = gh_batch_load(b, streams.data(), ns))) return done(die("batch load", rc));
+  const double t1 = now_ms();
+  if ((rc = gh_dev_alloc(0, std::max<uint64_t>(total, 16), &d_dst)) ||
+      (rc = gh_dev_alloc(0, std::max<uint64_t>(stored_bytes, 16), &d_stored)) ||
+      (stored_bytes && (rc = gh_dev_copy(d_stored, stored.data(), stored_bytes))))
+    return done(die("device allocation", rc));
+  gh_pgather_report rep{};
+  if ((rc = gh_batchdec_index(b, nullptr, 1)) == GH_OK)
+    rc = gh_pgather(b, items.data(), (uint32_t)nt, d_stored, stored_bytes, ranges.data(), (uint32_t)ranges.size(), d_dst, total,
+                    nullptr, &rep);
+  const double t2 = now_ms();
+  if (rc == GH_E_CORRUPT && rep.bad_ranges) {
+    std::vector<uint32_t> status(std::max<uint32_t>(ns, 1), 0);
+    if (gh_batch_status(b, status.data(), nullptr, ns) == GH_OK)
+      for (size_t i = 0; i < nt; ++i)
+        for (uint32_t p = 0; p < im[i].elem_size; ++p) {
+          const uint32_t sidx = slots[8 * i + p].stream;
+          if (sidx != GH_PLANES_STORED && status[sidx])
+            std::fprintf(stderr, "decoder: %s: line %zu: %s: plane %u: corrupt stream (status 0x%x)\n", list_file, line_of[i],
+                         in[i].c_str(), p, status[sidx]);
+        }
+  }
+  std::vector<uint8_t> bytes((size_t)total);
+  if (rc == GH_OK && total) rc = gh_dev_copy(bytes.data(), d_dst, total);
+  if (rc) return done(die("element gather", rc));
+  FILE* f = std::fopen(range_out, "wb");
+  bool okw = f && std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+  if (f) okw = std::fclose(f) == 0 && okw;
+  if (!okw) { std::fprintf(stderr, "decoder: cannot write %s\n", range_out); return done(1); }
+  std::printf("Element gather: %zu tensors, %zu ranges, %llu pieces, %llu bytes; load %.3f ms, kernels %.3f ms, call %.3f ms\n", nt,
+              ranges.size(), (unsigned long long)rep.npieces, (unsigned long long)total, t1 - t0, rep.kernel_ms, t2 - t1);
+  return done(0);
+}
+
 // --batch LIST: every line of the text file is `input<TAB>output`; all inputs are decoded as
 // one batch (gh_batch_*) and every output file is written.  A corrupt stream: exit code 1,
 // its line named, no output written for it.
-// With ranges_file / range_out: --batch LIST --ranges FILE OUT, the byte ranges alone.
-static int batch_main(const char* list_file, const char* ranges_file = nullptr, const char* range_out = nullptr) {
+// With ranges_file / range_out: --batch LIST --ranges FILE OUT, the byte ranges alone; with
+// `elements` as well: --batch LIST --elements FILE OUT, element ranges of byte-plane containers.
+static int batch_main(const char* list_file, const char* ranges_file = nullptr, const char* range_out = nullptr,
+                      bool elements = false) {
   std::vector<uint8_t> text;
   if (!read_file(list_file, text)) { std::fprintf(stderr, "decoder: Could not open batch list %s\n", list_file); return 1; }
   std::vector<std::string> in, out;
@@ -313,6 +429,13 @@ static int batch_main(const char* list_file, const char* ranges_file = nullptr, 
       std::fprintf(stderr, "decoder: %s: line %zu: %s: ", list_file, line_of[i], in[i].c_str());
       return die("bad compressed stream", rc);
     }
+  }
+  if (elements) {
+    if (!planes) {
+      std::fprintf(stderr, "decoder: %s: --elements takes byte-plane containers only (--ranges gathers bytes of compressed streams)\n", list_file);
+      return 1;
+    }
+    return planes_elements_main(list_file, in, line_of, img, ranges_file, range_out);
   }
   if (planes) {
     if (ranges_file) {
@@ -437,13 +560,16 @@ int main(int argc, char** argv) {
   if (argc == 3 && !std::strcmp(argv[1], "--batch")) return batch_main(argv[2]);
   if (argc == 6 && !std::strcmp(argv[1], "--batch") && !std::strcmp(argv[3], "--ranges"))
     return batch_main(argv[2], argv[4], argv[5]);
+  if (argc == 6 && !std::strcmp(argv[1], "--batch") && !std::strcmp(argv[3], "--elements"))
+    return batch_main(argv[2], argv[4], argv[5], true);
   if (argc < 3) {
     std::fprintf(stderr,
                  "Usage: bin/decoder input output [--gpus N] [--shards S] [--reps R] [--json] [--verify FILE]\n"
                  "       [--write-index FILE [--index-stride K]] [--index FILE --range LO:HI]\n"
                  "       [--index FILE --ranges FILE]\n"
                  "       bin/decoder --batch LIST   (LIST: one input<TAB>output per line)\n"
-                 "       bin/decoder --batch LIST --ranges FILE OUT   (FILE: one STREAM LO:HI per line)\n");
+                 "       bin/decoder --batch LIST --ranges FILE OUT   (FILE: one STREAM LO:HI per line)\n"
+                 "       bin/decoder --batch LIST --elements FILE OUT   (byte-plane containers; FILE: one TENSOR LO:HI per line)\n");
     return 2;
   }
   int ngpus = 1, reps = 1, nshards = 0;

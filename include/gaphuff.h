@@ -1006,6 +1006,85 @@ int gh_planes_join_device(gh_batch* b, const gh_planes_item* items, uint32_t nte
  * since the load. */
 int gh_planes_wait(gh_batch* b, gh_planes_report* rep);
 
+/* ---- element gather: element ranges of compressed tensors in a fixed launch count -------- */
+/* The batched gather for byte planes: element ranges (tensor, lo, hi) of a resident gh_batch
+ * that holds the coded planes of a tensor list, interleaved as in the original tensors, without
+ * a full decode and without the batch's output arena: gh_batch_load -> gh_batchdec_index ->
+ * element gather works with no write kernel ever having run.  No reference counterpart.  (The
+ * gh_planes_*, gh_batch_*, gh_batchdec_*, gh_batchraw_* and gh_ebatch_* names are closed sets
+ * pinned by tests; these carry gh_pgather_.)
+ *
+ * items / ntensors / d_stored / stored_len are gh_planes_join_device's (items[t].data is
+ * ignored).  Output layout: range i's (hi_i - lo_i) * E_i bytes start at sum_{j<i} (hi_j - lo_j)
+ * * E_j of d_dst, E_j the elem_size of the tensor range j names: tight, in request order, any
+ * byte alignment of d_dst.  Ranges may be empty, overlap, repeat, mix element sizes and name the
+ * tensors in any order.
+ *
+ * One call is GH_PGATHER_LAUNCHES launches however many ranges there are: a memset, a locate
+ * kernel, a one-workgroup scan and an expand kernel turn every element range into one byte range
+ * (stream, lo, hi) per coded plane of its tensor; the batched gather (gh_batchdec_gather_device,
+ * its memset and four kernels, as it is) decodes those into a batch-owned staging buffer; one
+ * range-join kernel interleaves the staged planes with the stored planes' bytes into d_dst.
+ * The call runs the batched gather inside: a later gh_batchdec_gather_wait reports that inner
+ * gather.  Limits (GH_E_ARG beyond them): GH_PGATHER_MAX_RANGES ranges per call (8 byte ranges
+ * per element range at the most, GH_GATHER_MAX_RANGES in all); tensors below 2^40 bytes; fewer
+ * than 2^31 - nranges KiB of destination. */
+#define GH_PGATHER_MAX_RANGES (GH_GATHER_MAX_RANGES / 8)
+#define GH_PGATHER_LAUNCHES 10u
+typedef struct gh_erange { uint64_t tensor, lo, hi; } gh_erange;   /* a contiguous int64[n,3] tensor, element units */
+typedef struct gh_pgather_report {
+  uint64_t out_bytes;   /* sum of (hi - lo) * elem_size over the valid ranges                */
+  uint64_t npieces;     /* pieces of the inner batched gather                                */
+  uint32_t bad_ranges;  /* element ranges whose tensor has a flagged coded plane             */
+  uint32_t status;      /* GH_ST_RANGE | GH_ST_DSTSMALL | GH_ST_PIECES | GH_ST_BADCODE       */
+  float kernel_ms;      /* HIP events: all kernels of the call                               */
+  uint32_t launches;    /* kernels + memsets of one call: GH_PGATHER_LAUNCHES                */
+  float expand_ms;      /* of kernel_ms: the memset and the three plan kernels               */
+  float join_ms;        /* of kernel_ms: the range join (the rest is the batched gather)     */
+} gh_pgather_report;
+/* The device's plan from host arrays, with no device: the byte ranges in range-major, then plane
+ * order into branges[0 .. cap), stage_off[i] / dst_off[i] (nranges entries each) the byte offset
+ * of range i in the staging buffer (the prefix of (hi - lo) * C, C the tensor's coded planes: the
+ * dst0 gh_batchdec_plan gives range i's first byte range) and in d_dst.  stream_status[s]: the
+ * batch's status words (NULL: none is flagged).  *nbranges / *out_bytes / *bad_ranges are always
+ * written (a first call with cap = 0 sizes the buffer; GH_E_SMALL then).  GH_E_ARG: null
+ * pointers, what gh_planes_layout refuses, tensor >= ntensors, lo > hi or hi > nelem (the counts
+ * are then 0).  A range whose tensor has a flagged coded plane keeps its bytes in both layouts
+ * and its byte ranges and counts once in *bad_ranges; the return stays GH_OK.  A tensor without
+ * coded planes gives no byte ranges. */
+int gh_pgather_plan(const gh_planes_item* items, uint32_t ntensors, const uint32_t* stream_status,
+                    const gh_erange* ranges, uint32_t nranges, gh_brange* branges, uint64_t cap,
+                    uint64_t* nbranges, uint64_t* stage_off, uint64_t* dst_off, uint64_t* out_bytes,
+                    uint32_t* bad_ranges);
+/* Enqueue the gather of d_ranges[0 .. nranges) (device memory) into d_dst (device memory,
+ * dst_len bytes) on hip_stream (NULL = the batch's stream), and return.  It runs after every
+ * earlier decode, index or gather of the batch, whatever their streams.  d_ranges, d_stored and
+ * d_dst must stay untouched until the wait.  The staging buffer (dst_len bytes: C <= E), the
+ * byte ranges and the per-range offsets are the batch's; the call blocks only to grow them or to
+ * upload a tensor list that differs from the previous call's: a repeated call with the same
+ * items and the same or a smaller nranges and dst_len allocates nothing and only enqueues.
+ * timed != 0 brackets the kernels with HIP events.  nranges = 0: GH_OK, nothing is launched.
+ * GH_E_STATE before an index or decode since the load; GH_E_ARG: null pointers, more than
+ * GH_PGATHER_MAX_RANGES ranges, a layout whose nstreams or any n differs from the loaded
+ * batch's, a misaligned d_stored; GH_E_SMALL: stored_len < stored_bytes. */
+int gh_pgather_device(gh_batch* b, const gh_planes_item* items, uint32_t ntensors, const void* d_stored,
+                      uint64_t stored_len, const gh_erange* d_ranges, uint32_t nranges, void* d_dst,
+                      uint64_t dst_len, void* hip_stream, int timed);
+/* Wait for the batch's last element gather and report it (rep may be NULL; it is filled before
+ * an error is returned).  GH_E_ARG: some range had tensor >= ntensors, lo > hi or hi > nelem
+ * (GH_ST_RANGE); GH_E_SMALL: the ranges' bytes exceed dst_len (GH_ST_DSTSMALL); GH_E_CORRUPT:
+ * the inner plan would exceed its piece buffer (GH_ST_PIECES); after these three not one byte of
+ * d_dst has been written.  GH_E_CORRUPT also when a range's tensor has a coded plane whose
+ * stream status word is non-zero (GH_ST_BADCODE in the report): such a range keeps its bytes in
+ * the layout and leaves them as they were, every other range is exact, and bad_ranges counts
+ * them, once per element range.  GH_E_STATE when no element gather was enqueued since the load. */
+int gh_pgather_wait(gh_batch* b, gh_pgather_report* rep);
+/* The same with the ranges in host memory: uploads them, then gh_pgather_device (timed) and
+ * gh_pgather_wait.  Synchronous.  rep may be NULL. */
+int gh_pgather(gh_batch* b, const gh_planes_item* items, uint32_t ntensors, const void* d_stored,
+               uint64_t stored_len, const gh_erange* ranges /* host */, uint32_t nranges, void* d_dst,
+               uint64_t dst_len, void* hip_stream, gh_pgather_report* rep);
+
 /* The container, one tensor per image, little-endian: u64 GH_PLANES_MAGIC, u32 elem_size, u32
  * coded_mask, u64 nelem, elem_size x u64 plane_bytes; then the planes in order, each at the
  * next 8-byte aligned offset.  A coded plane is a whole compressed.huff image, a stored plane
