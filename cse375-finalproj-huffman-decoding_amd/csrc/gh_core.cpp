@@ -25,6 +25,7 @@
 #include "gh_pm_flat.hpp"
 #include "gh_planes.hpp"
 #include "gh_planes_gather.hpp"
+#include "gh_pmask.hpp"
 #include "gh_raw_trans.hpp"
 
 namespace gh {
@@ -1167,6 +1168,82 @@ extern "C" int gh_planes_join_host(const gh_planes_item* item, const void* const
     case 2: planes_join_t<2>(dst, item->nelem, pl); break;
     case 4: planes_join_t<4>(dst, item->nelem, pl); break;
     default: planes_join_t<8>(dst, item->nelem, pl); break;
+  }
+  return GH_OK;
+}
+
+// Plane choice (gaphuff.h, "plane choice"): bits and nsyms of a plane's code by the host plan,
+// sizes and decisions by csrc/gh_pmask.hpp, the text the decide kernel compiles too.
+// One tensor of nelem > 0 elements from its e x 256 counts.
+static int pmask_tensor(const uint64_t* counts, uint64_t nelem, uint32_t e, const std::string& who, uint32_t* mask,
+                        uint64_t* plane_bytes) {
+  for (uint32_t p = 0; p < e; ++p) {
+    const uint64_t* c = counts + 256ull * p;
+    uint64_t sum = 0;
+    bool ok = true;
+    for (uint32_t v = 0; v < 256; ++v) ok = planes_add(sum, c[v], &sum) && ok;
+    if (!ok || sum != nelem) return fail(GH_E_ARG, who + "plane " + std::to_string(p) + ": the counts do not sum to nelem");
+    gh_encode_plan plan;
+    if (int rc = gh_encode_plan_from_counts(c, 0, &plan)) return fail(rc, who + gh_last_error());
+    const uint64_t fb = pmask_file_bytes(plan.bits, plan.nsyms, nelem);
+    if (plane_bytes) plane_bytes[p] = fb;
+    if (pmask_coded(fb, nelem)) *mask |= 1u << p;
+  }
+  return GH_OK;
+}
+
+// The checks both host entry points share; clears the outputs.
+static int pmask_check(const gh_planes_item* items, uint32_t ntensors, uint32_t* masks, uint64_t* plane_bytes) {
+  if (ntensors && (!items || !masks)) return fail(GH_E_ARG, "null argument");
+  uint32_t q0 = 0;
+  for (uint32_t t = 0; t < ntensors; ++t) {
+    const std::string who = "tensor " + std::to_string(t) + ": ";
+    if (!planes_elem_ok(items[t].elem_size)) return fail(GH_E_ARG, who + "element size not 1, 2, 4 or 8");
+    if (!pmask_next_q0(q0, items[t].elem_size, &q0)) return fail(GH_E_ARG, who + "more than 2^24 candidate planes");
+  }
+  for (uint32_t t = 0; t < ntensors; ++t) masks[t] = 0;
+  if (plane_bytes) std::memset(plane_bytes, 0, sizeof(uint64_t) * PLANES_MAX_E * (size_t)ntensors);
+  return GH_OK;
+}
+
+extern "C" int gh_pmask_from_counts(const uint64_t* counts, const gh_planes_item* items, uint32_t ntensors,
+                                    uint32_t* masks, uint64_t* plane_bytes) {
+  if (ntensors && !counts) return fail(GH_E_ARG, "null argument");
+  if (int rc = pmask_check(items, ntensors, masks, plane_bytes)) return rc;
+  uint32_t q0 = 0;
+  for (uint32_t t = 0; t < ntensors; ++t) {
+    const gh_planes_item& it = items[t];
+    const uint64_t* c = counts + 256ull * q0;
+    pmask_next_q0(q0, it.elem_size, &q0);
+    if (!it.nelem) {  // (its counts must still be empty)
+      for (uint32_t k = 0; k < 256u * it.elem_size; ++k)
+        if (c[k]) return fail(GH_E_ARG, "tensor " + std::to_string(t) + ": the counts do not sum to nelem");
+      continue;
+    }
+    if (int rc = pmask_tensor(c, it.nelem, it.elem_size, "tensor " + std::to_string(t) + ": ", &masks[t],
+                              plane_bytes ? plane_bytes + (size_t)PLANES_MAX_E * t : nullptr))
+      return rc;
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_pmask_host(const gh_planes_item* items, uint32_t ntensors, uint32_t* masks, uint64_t* plane_bytes) {
+  if (int rc = pmask_check(items, ntensors, masks, plane_bytes)) return rc;
+  std::vector<uint64_t> counts(256 * PLANES_MAX_E);
+  for (uint32_t t = 0; t < ntensors; ++t) {
+    const gh_planes_item& it = items[t];
+    const std::string who = "tensor " + std::to_string(t) + ": ";
+    if (!it.nelem) continue;
+    if (!it.data) return fail(GH_E_ARG, who + "null pointer");
+    const uint32_t e = it.elem_size;
+    if (it.nelem > UINT64_MAX / e) return fail(GH_E_ARG, who + "nelem * elem_size overflows 64 bits");
+    std::fill(counts.begin(), counts.end(), 0);
+    const uint8_t* src = (const uint8_t*)it.data;
+    for (uint64_t i = 0; i < it.nelem; ++i)
+      for (uint32_t p = 0; p < e; ++p) ++counts[256u * p + src[planes_src_index(i, e, p)]];
+    if (int rc = pmask_tensor(counts.data(), it.nelem, e, who, &masks[t],
+                              plane_bytes ? plane_bytes + (size_t)PLANES_MAX_E * t : nullptr))
+      return rc;
   }
   return GH_OK;
 }

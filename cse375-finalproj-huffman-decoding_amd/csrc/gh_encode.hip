@@ -34,6 +34,8 @@
 // kernels are in gh_ebatch.hip, its host side at the end of this file.
 // Byte planes (gh_planes_load, gh_planes_load_device): a batched encode whose streams are the
 // coded byte planes of typed tensors; the split kernel is in gh_planes_split.hip.
+// Plane choice (gh_pmask_device): which planes to code, from the tensors' own bytes; its
+// kernels are in gh_pmask.hip.
 // Sliced encode (gh_ectx_encode_slice): the same kernels on an input that is one slice of
 // a longer stream; the block scan starts at the slice's first stream bit and the write
 // kernel's SLICE variant indexes its outputs from the slice's origin; the index kernel's
@@ -62,6 +64,7 @@
 #include "gh_internal.hpp"
 #include "gh_planes.hpp"
 #include "gh_pm_flat.hpp"
+#include "gh_pmask.hpp"
 #include "gh_units.hpp"
 #include "gh_wave.hpp"
 
@@ -680,6 +683,7 @@ __global__ __launch_bounds__(MERGE_TB) void gh_enc_merge_kernel(const EncMergePa
 
 #include "gh_ebatch.hip"
 #include "gh_planes_split.hip"
+#include "gh_pmask.hip"
 
 }  // namespace gh
 
@@ -1286,6 +1290,13 @@ struct gh_ebatch {
   float hist_ms = 0, code_ms = 0, plan_host_ms = 0;
   bool loaded = false, planned = false;
   bool counts_on_device = false;  // a device plan: plans[i].count[] is filled by the first plan_of
+  // gh_pmask_device: buffers, events and results of its own (the batch's state is not touched)
+  DevBuf pm_desc;                 // PMaskTensor per tensor, then unit0 and q0 (ntensors + 1 each)
+  DevBuf pm_counts;               // 256 u64 per candidate plane, then plane_bytes and masks
+  DevBuf pm_recs, pm_tables;      // the code kernel's outputs (the tables are scratch)
+  Event pm_ev[4];                 // before the histogram, after it, after the code, after the decide
+  uint32_t pm_nplanes = 0;
+  bool pm_done = false;
   BatchQueue q;  // (last: its destructor waits for the encode before the buffers above go)
 };
 
@@ -1504,6 +1515,124 @@ extern "C" int gh_planes_load_times(gh_ebatch* b, float* kernel_ms) {
   *kernel_ms = 0;
   if (!b->loaded) return fail(GH_E_STATE, "gh_planes_load_times before a load");
   return b->split_timed ? b->ev_split.elapsed(kernel_ms) : (int)GH_OK;
+}
+
+// ---- plane choice (gaphuff.h; kernels: gh_pmask.hip; rule: gh_pmask.hpp) ---------------------
+constexpr bool PMASK_MERGE_DEFAULT = true;  // ("Plane choice": the measurement)
+
+extern "C" int gh_pmask_device(gh_ebatch* b, const gh_planes_item* items, uint32_t ntensors, uint32_t* masks,
+                               uint64_t* plane_bytes, void* hip_stream, gh_pmask_report* rep) {
+  if (rep) *rep = gh_pmask_report{};
+  if (!b || (ntensors && (!items || !masks))) return fail(GH_E_ARG, "null argument");
+  // the numbering and the unit prefix
+  std::vector<uint32_t> pre(2 * ((size_t)ntensors + 1));  // unit0, then q0
+  uint32_t* unit0 = pre.data();
+  uint32_t* q0 = pre.data() + ntensors + 1;
+  uint64_t units = 0;
+  uint32_t nplanes = 0;
+  for (uint32_t t = 0; t < ntensors; ++t) {
+    const std::string who = "tensor " + std::to_string(t) + ": ";
+    if (!planes_elem_ok(items[t].elem_size)) return fail(GH_E_ARG, who + "element size not 1, 2, 4 or 8");
+    if (items[t].nelem && !items[t].data) return fail(GH_E_ARG, who + "null pointer");
+    unit0[t] = (uint32_t)units;
+    q0[t] = nplanes;
+    units += planes_units(items[t].nelem);  // (< 2^31 + 2^54)
+    if (units >= PLANES_MAX_UNITS) return fail(GH_E_ARG, who + "the list reaches 2^31 work units");
+    if (!pmask_next_q0(nplanes, items[t].elem_size, &nplanes)) return fail(GH_E_ARG, who + "more than 2^24 candidate planes");
+  }
+  unit0[ntensors] = (uint32_t)units;
+  q0[ntensors] = nplanes;
+  b->pm_nplanes = 0;  // (gh_pmask_counts sees the last call that succeeded, or nothing)
+  b->pm_done = !ntensors;
+  if (!ntensors) return GH_OK;
+  GH_HIP(hipSetDevice(b->q.device));
+  // one upload: the tensors' descriptors, then the two prefixes
+  const size_t dbytes = sizeof(PMaskTensor) * (size_t)ntensors;
+  std::vector<uint8_t> up(dbytes + 4 * pre.size());
+  PMaskTensor* d = (PMaskTensor*)up.data();
+  for (uint32_t t = 0; t < ntensors; ++t) d[t] = PMaskTensor{(const uint8_t*)items[t].data, items[t].nelem, q0[t], items[t].elem_size};
+  std::memcpy(up.data() + dbytes, pre.data(), 4 * pre.size());
+  if (int rc = upload_at_least(b->pm_desc, up.data(), up.size())) return rc;
+  // counts[nplanes][256], plane_bytes[8 ntensors] (u64), masks[ntensors]: zeroed by one memset,
+  // the last two read back by one copy
+  const uint64_t cbytes = 2048ull * nplanes, obytes = (8ull * PLANES_MAX_E + 4ull) * ntensors;
+  if (int rc = b->pm_counts.reserve(cbytes + obytes)) return rc;
+  if (int rc = b->pm_recs.reserve(sizeof(EBatchCodeRec) * (uint64_t)nplanes)) return rc;
+  if (int rc = b->pm_tables.reserve(1024ull * nplanes)) return rc;
+  for (Event& e : b->pm_ev)
+    if (int rc = e.create()) return rc;
+  PMaskParams hp{};
+  hp.desc = b->pm_desc.get<PMaskTensor>();
+  hp.unit0 = (const uint32_t*)(b->pm_desc.get<uint8_t>() + dbytes);
+  hp.counts = b->pm_counts.get<unsigned long long>();
+  hp.ntensors = ntensors;
+  hp.nunits = unit0[ntensors];
+  const uint32_t* d_q0 = hp.unit0 + ntensors + 1;
+  unsigned long long* d_pb = (unsigned long long*)(b->pm_counts.get<uint8_t>() + cbytes);
+  uint32_t* d_masks = (uint32_t*)(d_pb + (uint64_t)PLANES_MAX_E * ntensors);
+  const hipStream_t st = b->q.stream;
+  // after what the producer's stream holds now, then the four launches on the batch's stream
+  if (int rc = b->q.follow(hip_stream)) return rc;
+  GH_HIP(hipMemsetAsync(b->pm_counts.get(), 0, cbytes + obytes, st));
+  GH_HIP(hipEventRecord(b->pm_ev[0], st));
+  if (hp.nunits) {
+    // GH_PLANES_GRID=k (tests): k workgroups, so that one wave walks many units and tensors;
+    // else at most the workgroups the LDS keeps resident (five of 32 KiB per CU)
+    const uint32_t grid = getenv("GH_PLANES_GRID") ? unit_grid("GH_PLANES_GRID", hp.nunits, PM_WAVES, b->q.num_cu)
+                                                   : (uint32_t)std::clamp<uint64_t>(ceil_div(hp.nunits, PM_WAVES), 1,
+                                                                                    5ull * (uint64_t)b->q.num_cu);
+    const char* em = getenv("GH_PMASK_MERGE");  // (tests, measurements)
+    if (em ? atoi(em) != 0 : PMASK_MERGE_DEFAULT)
+      hipLaunchKernelGGL(gh_pmask_hist_kernel<true>, dim3(grid), dim3(PM_TB), 0, st, hp);
+    else
+      hipLaunchKernelGGL(gh_pmask_hist_kernel<false>, dim3(grid), dim3(PM_TB), 0, st, hp);
+    GH_HIP(hipGetLastError());
+  }
+  GH_HIP(hipEventRecord(b->pm_ev[1], st));
+  {
+    // GH_EBATCH_GRID=k (tests): k workgroups walk all planes
+    const uint32_t grid = unit_grid("GH_EBATCH_GRID", nplanes, 1, b->q.num_cu);
+    hipLaunchKernelGGL(gh_ebatch_code_kernel, dim3(grid), dim3(EB_TB), 0, st, hp.counts, b->pm_tables.get<uint32_t>(),
+                       b->pm_recs.get<EBatchCodeRec>(), nplanes);
+    GH_HIP(hipGetLastError());
+  }
+  GH_HIP(hipEventRecord(b->pm_ev[2], st));
+  hipLaunchKernelGGL(gh_pmask_decide_kernel, dim3((nplanes + 255u) / 256u), dim3(256), 0, st,
+                     b->pm_recs.get<EBatchCodeRec>(), hp.desc, d_q0, ntensors, nplanes, d_pb, d_masks);
+  GH_HIP(hipGetLastError());
+  GH_HIP(hipEventRecord(b->pm_ev[3], st));
+  // the one read-back: sizes, then masks
+  std::vector<uint8_t> back(obytes);
+  GH_HIP(hipMemcpyAsync(back.data(), d_pb, obytes, hipMemcpyDeviceToHost, st));
+  GH_HIP(hipStreamSynchronize(st));
+  const uint64_t* pb = (const uint64_t*)back.data();
+  std::memcpy(masks, back.data() + 8ull * PLANES_MAX_E * ntensors, 4ull * ntensors);
+  if (plane_bytes) std::memcpy(plane_bytes, pb, 8ull * PLANES_MAX_E * ntensors);
+  if (rep) {
+    rep->ntensors = ntensors;
+    rep->launches = GH_PMASK_LAUNCHES;
+    for (uint32_t t = 0; t < ntensors; ++t) {
+      rep->raw_bytes += items[t].nelem * items[t].elem_size;
+      rep->coded_planes += (uint32_t)__builtin_popcount(masks[t]);
+      for (uint32_t p = 0; p < items[t].elem_size; ++p)
+        rep->chosen_bytes += pmask_chosen_bytes(pb[(size_t)PLANES_MAX_E * t + p], items[t].nelem);
+    }
+    GH_HIP(hipEventElapsedTime(&rep->hist_ms, b->pm_ev[0], b->pm_ev[1]));
+    GH_HIP(hipEventElapsedTime(&rep->code_ms, b->pm_ev[1], b->pm_ev[2]));
+    GH_HIP(hipEventElapsedTime(&rep->decide_ms, b->pm_ev[2], b->pm_ev[3]));
+  }
+  b->pm_nplanes = nplanes;
+  b->pm_done = true;
+  return GH_OK;
+}
+
+extern "C" int gh_pmask_counts(gh_ebatch* b, uint32_t plane, uint64_t counts[256]) {
+  if (!b || !counts) return fail(GH_E_ARG, "null argument");
+  if (!b->pm_done) return fail(GH_E_STATE, "gh_pmask_counts before a gh_pmask_device");
+  if (plane >= b->pm_nplanes) return fail(GH_E_ARG, "no such candidate plane");
+  GH_HIP(hipSetDevice(b->q.device));
+  GH_HIP(hipMemcpy(counts, b->pm_counts.get<uint8_t>() + 2048ull * plane, 2048, hipMemcpyDeviceToHost));
+  return GH_OK;
 }
 
 static EBatchParams ebatch_params(const gh_ebatch* b) {

@@ -44,6 +44,7 @@ GH_OFFS_NONE, GH_OFFS_RECORDED, GH_OFFS_READY = 0, 1, 2  # gh_ctx_offsets_state
 GH_GATHER_MAX_RANGES = 1 << 24
 GH_PGATHER_MAX_RANGES = GH_GATHER_MAX_RANGES // 8
 GH_PGATHER_LAUNCHES = 10
+GH_PMASK_LAUNCHES = 4
 
 # Every symbol include/gaphuff.h declares (checked by tests/test_abi.py).
 EXPORTED = (
@@ -80,6 +81,7 @@ EXPORTED = (
     "gh_planes_layout", "gh_planes_split_host", "gh_planes_join_host", "gh_planes_load", "gh_planes_load_device",
     "gh_planes_load_times", "gh_planes_join_device", "gh_planes_wait", "gh_planes_image_bytes", "gh_planes_image_write", "gh_planes_parse",
     "gh_pgather_plan", "gh_pgather_device", "gh_pgather_wait", "gh_pgather",
+    "gh_pmask_from_counts", "gh_pmask_host", "gh_pmask_device", "gh_pmask_counts",
 )
 GH_EBATCH_UNIT_BYTES = 1024
 GH_PLANES_STORED = 0xFFFFFFFF
@@ -214,6 +216,12 @@ class gh_pgather_report(ctypes.Structure):
     _fields_ = [("out_bytes", ctypes.c_uint64), ("npieces", ctypes.c_uint64), ("bad_ranges", ctypes.c_uint32),
                 ("status", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("launches", ctypes.c_uint32),
                 ("expand_ms", ctypes.c_float), ("join_ms", ctypes.c_float)]
+
+
+class gh_pmask_report(ctypes.Structure):
+    _fields_ = [("raw_bytes", ctypes.c_uint64), ("chosen_bytes", ctypes.c_uint64), ("ntensors", ctypes.c_uint32),
+                ("coded_planes", ctypes.c_uint32), ("hist_ms", ctypes.c_float), ("code_ms", ctypes.c_float),
+                ("decide_ms", ctypes.c_float), ("launches", ctypes.c_uint32)]
 
 
 class gh_planes_image(ctypes.Structure):
@@ -393,6 +401,10 @@ def lib() -> ctypes.CDLL:
             "gh_pgather_wait": ([P, ctypes.POINTER(gh_pgather_report)], I),
             "gh_pgather": ([P, ctypes.POINTER(gh_planes_item), U32, P, U64, P, U32, P, U64, P,
                             ctypes.POINTER(gh_pgather_report)], I),
+            "gh_pmask_from_counts": ([P, ctypes.POINTER(gh_planes_item), U32, P, P], I),
+            "gh_pmask_host": ([ctypes.POINTER(gh_planes_item), U32, P, P], I),
+            "gh_pmask_device": ([P, ctypes.POINTER(gh_planes_item), U32, P, P, P, ctypes.POINTER(gh_pmask_report)], I),
+            "gh_pmask_counts": ([P, U32, P], I),
             "gh_version": ([], ctypes.c_char_p),
             "gh_last_error": ([], ctypes.c_char_p),
         }
@@ -1449,6 +1461,32 @@ class BatchEncoder(_Handle):
         _check(lib().gh_planes_load_times(self._h, ctypes.byref(ms)))
         return ms.value
 
+    def choose_masks_device(self, items, hip_stream: int = 0):
+        """Every tensor's coded planes from its own bytes, on the GPU (gh_pmask_device): ``items``
+        are ``(device address, nelem, elem_size[, coded_mask])``, any byte alignment (a mask is
+        ignored).  Returns ``(masks, plane_bytes)`` as :func:`choose_planes_masks` does.
+        Synchronous; the batch's load, plan and encode state stay as they are."""
+        arr, n = _planes_items([(it[0], it[1], it[2], 0) for it in items])
+        masks, pb = np.zeros(n, dtype=np.uint32), np.zeros((n, 8), dtype=np.uint64)
+        self._pmask_rep = gh_pmask_report()
+        _check(lib().gh_pmask_device(self._h, arr, n, _ptr(masks) if n else None, _ptr(pb) if n else None,
+                                     ctypes.c_void_p(hip_stream or None), ctypes.byref(self._pmask_rep)))
+        return masks, pb
+
+    def pmask_report(self) -> gh_pmask_report:
+        """The report of the last :meth:`choose_masks_device`."""
+        rep = getattr(self, "_pmask_rep", None)
+        if rep is None:
+            raise GapHuffError(-8, "pmask_report before a choose_masks_device")
+        return rep
+
+    def pmask_counts(self, q: int) -> np.ndarray:
+        """The 256 byte counts of candidate plane ``q`` (tensor order, then plane order, over all
+        planes of every tensor) as the last :meth:`choose_masks_device` left them (gh_pmask_counts)."""
+        out = np.zeros(256, dtype=np.uint64)
+        _check(lib().gh_pmask_counts(self._h, q, _ptr(out)))
+        return out
+
     def plan(self, force_version: int = 0, threads: int = 0) -> None:
         """Every stream's histogram (one launch) and host plan (gh_ebatch_plan); synchronous."""
         _check(lib().gh_ebatch_plan(self._h, force_version, threads))
@@ -1562,6 +1600,35 @@ def planes_layout(items):
     return out, int(ns.value), int(sb.value)
 
 
+def choose_planes_masks(arrays):
+    """Every tensor's coded planes from its own bytes, on the CPU (gh_pmask_host; needs no
+    device): plane ``p`` is coded iff its compressed.huff image is smaller than its ``nelem`` raw
+    bytes.  Returns ``(masks, plane_bytes)``: ``masks[t]`` (np.uint32) is what ``coded_masks``
+    takes, ``plane_bytes[t][p]`` (np.uint64 ``[n, 8]``) the image size of every plane, chosen or
+    not (0 for ``p >= elem_size`` and for an empty tensor)."""
+    arrs, items = _planes_host_items(arrays, [0] * len(arrays))
+    arr, n = _planes_items(items)
+    masks, pb = np.zeros(n, dtype=np.uint32), np.zeros((n, 8), dtype=np.uint64)
+    _check(lib().gh_pmask_host(arr, n, _ptr(masks) if n else None, _ptr(pb) if n else None))
+    return masks, pb
+
+
+def planes_masks_from_counts(counts, shapes):
+    """:func:`choose_planes_masks` from byte counts (gh_pmask_from_counts; needs no device):
+    ``counts`` is a uint64 ``[nplanes, 256]`` array in candidate order (tensor order, then plane
+    order, over all planes of every tensor), ``shapes`` one ``(nelem, elem_size)`` per tensor."""
+    shapes = list(shapes)
+    c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1, 256)
+    # (a bad elem_size is the library's to refuse; the rows it would read must exist)
+    if all(e in (1, 2, 4, 8) for _, e in shapes) and c.shape[0] != sum(e for _, e in shapes):
+        raise GapHuffError(-1, "one row of 256 counts per plane of every tensor")
+    arr, n = _planes_items([(0, nelem, e, 0) for nelem, e in shapes])
+    masks, pb = np.zeros(n, dtype=np.uint32), np.zeros((n, 8), dtype=np.uint64)
+    _check(lib().gh_pmask_from_counts(_ptr(c) if c.size else None, arr, n, _ptr(masks) if n else None,
+                                      _ptr(pb) if n else None))
+    return masks, pb
+
+
 def planes_gather_plan(items, ranges, status=None):
     """The element gather's plan from host arrays (gh_pgather_plan; needs no device): ``items``
     are ``(address, nelem, elem_size, coded_mask)``, ``ranges`` (tensor, lo, hi) element triples,
@@ -1663,12 +1730,25 @@ def parse_planes(image) -> PlanesImage:
 def encode_tensors(arrays, coded_masks=None, device: int = 0, device_plan: bool = False) -> list:
     """Encode typed tensors (numpy arrays of 1/2/4/8-byte elements) as one batch on the GPU and
     return their containers.  ``coded_masks``: one mask per tensor; default the top plane alone
-    (the one plane for 1-byte elements).  ``device_plan``: build the codes on the GPU."""
-    arrs, items = _planes_host_items(arrays, coded_masks)
-    slots, _, stored_bytes = planes_layout(items)
+    (the one plane for 1-byte elements); ``"auto"``: every tensor's own best mask, chosen on the
+    GPU from the uploaded tensors (:meth:`BatchEncoder.choose_masks_device`).  ``device_plan``:
+    build the codes on the GPU."""
+    auto = isinstance(coded_masks, str)
+    if auto and coded_masks != "auto":
+        raise GapHuffError(-1, "coded_masks: a list of masks, None or \"auto\"")
+    arrs, items = _planes_host_items(arrays, None if auto else coded_masks)
     with BatchEncoder(device) as b:
         bufs = [DeviceBuffer(max(a.nbytes, 16), device).upload(a.reshape(-1).view(np.uint8)) if a.size
                 else DeviceBuffer(16, device) for a in arrs]
+        try:
+            if auto:
+                masks, _ = b.choose_masks_device([(buf.addr, it[1], it[2]) for buf, it in zip(bufs, items)])
+                items = [(it[0], it[1], it[2], int(m)) for it, m in zip(items, masks)]
+            slots, _, stored_bytes = planes_layout(items)
+        except BaseException:
+            for buf in bufs:
+                buf.close()
+            raise
         with DeviceBuffer(max(stored_bytes, 16), device) as st:
             try:
                 b.load_planes_device([(buf.addr, it[1], it[2], it[3]) for buf, it in zip(bufs, items)], st.addr,

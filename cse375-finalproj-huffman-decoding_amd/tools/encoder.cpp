@@ -18,10 +18,12 @@
 // on the GPU (gh_ebatch_*: each input with its own code, a fixed set of launches however
 // many inputs) and writes every output.  --device-plan builds the codes on the GPU too
 // (gh_batchenc_plan_device): the same files.
-// bin/encoder --batch LIST --planes E[:MASK] [--gpu D] [--device-plan]
+// bin/encoder --batch LIST --planes E[:MASK|:auto] [--gpu D] [--device-plan]
 // --planes E[:MASK] treats every input as a tensor of E-byte elements (E = 1, 2, 4, 8): the
 // byte planes MASK names (default: the top plane alone) are the batch's streams, the others
 // are stored, and every output is a byte-plane container (gaphuff.h "byte planes").
+// --planes E:auto gives every input its own mask: the planes whose image is smaller than their
+// raw bytes (gh_pmask_host, gaphuff.h "plane choice").
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -53,8 +55,10 @@ static bool read_file(const char* path, std::vector<uint8_t>& out) {
 // --batch reads it); all inputs are encoded as one batch (gh_ebatch_*), each with its own
 // code, and every output file is written.  device_plan: gh_batchenc_plan_device instead of
 // gh_ebatch_plan.  planes_e != 0: every input is a tensor of planes_e-byte elements whose planes
-// in planes_mask are coded (gh_planes_load), and every output a byte-plane container.
-static int batch_main(const char* list_file, int device, bool device_plan, uint32_t planes_e, uint32_t planes_mask) {
+// in planes_mask are coded (gh_planes_load), and every output a byte-plane container;
+// planes_auto: every tensor's own mask by gh_pmask_host.
+static int batch_main(const char* list_file, int device, bool device_plan, uint32_t planes_e, uint32_t planes_mask,
+                      bool planes_auto) {
   std::vector<uint8_t> text;
   if (!read_file(list_file, text)) {
     std::fprintf(stderr, "encoder: Could not open batch list %s\n", list_file);
@@ -107,6 +111,14 @@ static int batch_main(const char* list_file, int device, bool device_plan, uint3
   uint32_t nstreams = (uint32_t)ns;
   if (planes_e) {
     for (size_t i = 0; i < ns; ++i) items[i] = gh_planes_item{data[i].data(), n[i] / planes_e, planes_e, planes_mask};
+    if (planes_auto) {
+      std::vector<uint32_t> masks(std::max<size_t>(ns, 1));
+      if (gh_pmask_host(items.data(), (uint32_t)ns, masks.data(), nullptr)) {
+        std::fprintf(stderr, "encoder: --planes: %s\n", gh_last_error());
+        return 1;
+      }
+      for (size_t i = 0; i < ns; ++i) items[i].coded_mask = masks[i];
+    }
     uint64_t stored_bytes = 0;
     if (gh_planes_layout(items.data(), (uint32_t)ns, slots.data(), &nstreams, &stored_bytes)) {
       std::fprintf(stderr, "encoder: --planes: %s\n", gh_last_error());
@@ -176,9 +188,12 @@ static int batch_main(const char* list_file, int device, bool device_plan, uint3
   gh_ebatch_destroy(b);
   char code[48] = "";
   if (device_plan) std::snprintf(code, sizeof(code), "code kernel %.3f, ", code_ms);
-  if (planes_e)
-    std::printf("Planes: %zu tensors of %u-byte elements, mask 0x%x: %u coded planes, %zu stored bytes, %llu container "
-                "bytes\n", ns, planes_e, planes_mask, nstreams, stored.size(), (unsigned long long)out_total);
+  if (planes_e) {
+    char mask[24] = "auto";
+    if (!planes_auto) std::snprintf(mask, sizeof(mask), "0x%x", planes_mask);
+    std::printf("Planes: %zu tensors of %u-byte elements, mask %s: %u coded planes, %zu stored bytes, %llu container "
+                "bytes\n", ns, planes_e, mask, nstreams, stored.size(), (unsigned long long)out_total);
+  }
   std::printf("Batch: %u streams, %llu bytes -> %llu bytes; load %.3f ms, plan %.3f ms (histogram %.3f, %shost %.3f), "
               "kernel %.3f ms, call %.3f ms\n",
               rep.nstreams, (unsigned long long)rep.in_bytes, (unsigned long long)rep.out_bytes, t1 - t0, t2 - t1,
@@ -189,7 +204,7 @@ static int batch_main(const char* list_file, int device, bool device_plan, uint3
 int main(int argc, char** argv) {
   if (argc >= 3 && !std::strcmp(argv[1], "--batch")) {
     int device = 0;
-    bool device_plan = false, bad = false;
+    bool device_plan = false, bad = false, planes_auto = false;
     uint32_t planes_e = 0, planes_mask = 0;
     for (int i = 3; i < argc; ++i) {
       if (!std::strcmp(argv[i], "--gpu") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -198,16 +213,21 @@ int main(int argc, char** argv) {
         char* end = nullptr;
         planes_e = (uint32_t)std::strtoul(argv[++i], &end, 0);
         planes_mask = planes_e >= 1 && planes_e <= 8 ? 1u << (planes_e - 1) : 0u;
-        if (*end == ':') planes_mask = (uint32_t)std::strtoul(end + 1, &end, 0);
+        if (!std::strcmp(end, ":auto")) {
+          planes_auto = true;
+          end += 5;
+        } else if (*end == ':') {
+          planes_mask = (uint32_t)std::strtoul(end + 1, &end, 0);
+        }
         if (*end || (planes_e != 1 && planes_e != 2 && planes_e != 4 && planes_e != 8) || planes_mask >> planes_e) bad = true;
       } else bad = true;
     }
     if (bad) {
-      std::fprintf(stderr, "Usage: bin/encoder --batch LIST [--planes E[:MASK]] [--gpu D] [--device-plan]   (LIST: one "
-                           "input<TAB>output per line; E: 1, 2, 4 or 8; MASK < 1 << E)\n");
+      std::fprintf(stderr, "Usage: bin/encoder --batch LIST [--planes E[:MASK|:auto]] [--gpu D] [--device-plan]   (LIST: "
+                           "one input<TAB>output per line; E: 1, 2, 4 or 8; MASK < 1 << E)\n");
       return 2;
     }
-    return batch_main(argv[2], device, device_plan, planes_e, planes_mask);
+    return batch_main(argv[2], device, device_plan, planes_e, planes_mask, planes_auto);
   }
   if (argc < 3) {
     std::printf("Usage: bin/encoder input output\n");

@@ -1085,6 +1085,52 @@ int gh_pgather(gh_batch* b, const gh_planes_item* items, uint32_t ntensors, cons
                uint64_t stored_len, const gh_erange* ranges /* host */, uint32_t nranges, void* d_dst,
                uint64_t dst_len, void* hip_stream, gh_pgather_report* rep);
 
+/* ---- plane choice: every tensor's coded planes from its own bytes ----------------------- */
+/* Which planes of a tensor are worth coding, by exact size.  For plane p < E of tensor t with
+ * nelem > 0, fb(t, p) is gh_encode_plan_from_counts(counts of the plane's bytes, 0).file_bytes:
+ * the size of the compressed.huff image gh_encode_write makes of the plane.  The plane is coded
+ * iff fb(t, p) < nelem; a tie is stored; a tensor with nelem = 0 gets mask 0.  Containers align
+ * planes to 8 bytes and fb < nelem implies round_up8(fb) <= round_up8(nelem), so the chosen
+ * mask gives a container no larger than any other mask's and never larger than the all-stored
+ * one.  One definition for CPU and GPU (csrc/gh_pmask.hpp).  No reference counterpart.  (The
+ * gh_planes_*, gh_pgather_*, gh_batch*_ and gh_ebatch_* names are closed sets pinned by tests;
+ * these carry gh_pmask_.)
+ *
+ * Candidate planes are numbered in tensor order, then plane order, over ALL E planes of every
+ * tensor: q = q0[t] + p, q0[t] the sum of E_j for j < t.  items[t].coded_mask and, where the
+ * call takes counts, items[t].data are ignored.  masks[t]: the chosen mask; plane_bytes[8 t + p]
+ * (may be NULL): fb(t, p) of every candidate, chosen or not, 0 for p >= E and for nelem = 0. */
+#define GH_PMASK_LAUNCHES 4u   /* memset of the counts, histogram, code, decide */
+typedef struct gh_pmask_report {
+  uint64_t raw_bytes, chosen_bytes;   /* sum nelem*E; sum over planes of min-by-rule size */
+  uint32_t ntensors, coded_planes;    /* planes the rule codes */
+  float hist_ms, code_ms, decide_ms;  /* HIP events */
+  uint32_t launches;                  /* GH_PMASK_LAUNCHES */
+} gh_pmask_report;
+/* The masks from byte counts, counts[q][256] in candidate order.  No device.  GH_E_ARG: null
+ * pointers (all may be NULL when ntensors = 0), an elem_size outside {1, 2, 4, 8}, a plane whose
+ * counts do not sum to nelem, more than 2^24 candidate planes. */
+int gh_pmask_from_counts(const uint64_t* counts, const gh_planes_item* items, uint32_t ntensors, uint32_t* masks,
+                         uint64_t* plane_bytes);
+/* The same from tensors in host memory: scalar histograms of exactly nelem * elem_size bytes
+ * per tensor, at any alignment, then the function above.  No device. */
+int gh_pmask_host(const gh_planes_item* items, uint32_t ntensors, uint32_t* masks, uint64_t* plane_bytes);
+/* The same from tensors in device memory (any alignment; exactly nelem * elem_size bytes of
+ * each are read), in GH_PMASK_LAUNCHES launches however many tensors there are: a memset of
+ * the counts, one histogram kernel over units of 1024 elements, the batched encode's code kernel
+ * on the nplanes histograms, one decide kernel; then one read-back of the masks and sizes (4 +
+ * 64 bytes per tensor) into masks / plane_bytes (host memory).  Synchronous; follows hip_stream
+ * as gh_ebatch_load_device does (the kernels run on the batch's stream after what hip_stream
+ * holds now).  It works in buffers of its own inside the batch and leaves the batch's load,
+ * plan and encode state untouched: legal before any load, and between a plan and an encode.
+ * ntensors = 0: GH_OK, nothing is launched.  GH_E_ARG: null pointers, what gh_pmask_from_counts
+ * refuses, 2^31 or more units of 1024 elements.  rep may be NULL. */
+int gh_pmask_device(gh_ebatch* b, const gh_planes_item* items, uint32_t ntensors, uint32_t* masks,
+                    uint64_t* plane_bytes, void* hip_stream, gh_pmask_report* rep);
+/* The byte counts of candidate plane `plane` as the last gh_pmask_device left them.
+ * GH_E_STATE before one; GH_E_ARG: no such candidate. */
+int gh_pmask_counts(gh_ebatch* b, uint32_t plane, uint64_t counts[256]);
+
 /* The container, one tensor per image, little-endian: u64 GH_PLANES_MAGIC, u32 elem_size, u32
  * coded_mask, u64 nelem, elem_size x u64 plane_bytes; then the planes in order, each at the
  * next 8-byte aligned offset.  A coded plane is a whole compressed.huff image, a stored plane
